@@ -3,7 +3,11 @@
 iterations/s to 1e-10, next to the reference's omp/ path (restated in oracle/,
 kind "port") on the host cores of the same box.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times the K steps, writes the
+outputs of the last timed step when --dump-outputs is given, and prints the
+line.  Every other figure (below) is measured only with --full.
 
 N = 1  (configs[1], SURVEY.md 8(d) "P2"): a step = one `Csr::apply` (y = A x) on
        the 1M-row 5-pt Poisson matrix.  Inputs are resident in HBM before the
@@ -12,28 +16,37 @@ N = 1  (configs[1], SURVEY.md 8(d) "P2"): a step = one `Csr::apply` (y = A x) on
        serve the 80 MB problem on-die -- with the automatic strategy and no
        caller flag (what Csr::apply through the reference interface passes): the
        library's residency tracker sees the other copies go by and selects the
-       nontemporal matrix streams itself.  The warm figure (same matrix
-       every step = the reference's benchmark/spmv methodology, automatic
-       strategy) is reported under "warm", CG on P2 under "cg", and the one-GPU
-       anchor of the multi-GPU curve (P3: 256^3 7-pt Poisson, SpMV + CG to
-       1e-10) under "p3".
+       nontemporal matrix streams itself.  With --full: the streaming ceiling
+       (roofline.practical_ceiling_us), the warm figure (same matrix every
+       step = the reference's benchmark/spmv methodology, automatic strategy)
+       under "warm", CG on P2 under "cg", the one-GPU anchor of the multi-GPU
+       curve (P3: 256^3 7-pt Poisson, SpMV + CG to 1e-10) under "p3", configs
+       3 and 4, the scattered-column classes, the CPU baseline and the
+       bit-exact check against the oracle.
 N > 1  (configs[4], "P3", one process per GPU under torch.distributed): STRONG
        scaling of the row-partitioned 16.7M-row 256^3 7-pt Poisson problem:
        a step = one distributed apply (pack -> halo exchange over RCCL || local
        SpMV -> non-local rows), `value` = 2 nnz(global) / max-over-ranks time;
-       "cg" = row-partitioned CG to 1e-10 without an iteration cap (native fused
-       driver, csrc/dist_cg.hip, over its own RCCL communicator).
+       with --full, "cg" = row-partitioned CG to 1e-10 without an iteration cap
+       (native fused driver, csrc/dist_cg.hip, over its own RCCL communicator)
+       and the one-GPU anchor (n1_same_run, parallel_efficiency).
        GKOMI_BENCH_FORCE_DIST=1 runs that code path with a world of one rank.
        Without WORLD_SIZE in the environment `--gpus N` starts the N rank processes
        itself (python -m torch.distributed.run, as child processes, before this
        process makes any GPU call) and exits with their code; with fewer than N
        devices it says so and exits 2.
 
-Timing: every timed region is EXACTLY K steps between barrier + synchronize on both
-sides (max over ranks).  The line's `value` is the MEDIAN region of as many regions as it
-takes to cover >= 0.05 s of measured steps (the reference's own floor,
-benchmark/utils/general.hpp:96-117; at least 3, at most 400 regions); best and all-region
-statistics are reported next to it.
+Timing: the headline is ONE timed region of exactly K steps between barrier +
+synchronize on both sides (max over ranks); `value` and `ms_per_step` come from its
+host wall clock.  With --full, `timing_spread` adds further regions of K steps until
+>= 0.05 s of steps are covered (the reference's own floor,
+benchmark/utils/general.hpp:96-117; at least 3, at most 400 regions), and the other
+legs report the MEDIAN region of that same policy.
+
+--dump-outputs DIR: after the timed steps, what the last of them computed (y, as a
+caller of the timed path receives it) goes to DIR/y.npy (N > 1: DIR/y_rank<r>.npy,
+each rank's rows, a fixed seeded sample of them beyond 64 MB in all).  The inputs are
+generated deterministically, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -56,6 +69,7 @@ GRID = 1000            # P2: 1000 x 1000 grid
 T_START = time.perf_counter()
 TRIALS = 3
 GKOMI_CSR_STREAMING = 1 << 24
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def algorithmic_bytes(nrows, ncols, nnz):
@@ -82,6 +96,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--strategy", type=int, default=0, help="C-ABI strategy word of the cold leg (0 = automatic)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: timing spread, streaming ceiling, warm, CG, P3, "
+                         "configs 3 and 4, scattered-column classes, CPU baseline and oracle parity (N > 1: CG and "
+                         "the one-GPU anchor); the --no-* options below switch legs of a --full run off")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cg", action="store_true")
     ap.add_argument("--no-p3", action="store_true")
@@ -92,10 +112,11 @@ def parse():
     ap.add_argument("--no-irregular", action="store_true",
                     help="skip the scattered-column classes (uniform random / power-law rows, 1 M rows: SuiteSparse's graph-like class)")
     ap.add_argument("--min-region-seconds", type=float, default=0.05,
-                    help="floor on the total length of the timed regions of K steps each (more regions, never more steps)")
+                    help="--full: floor on the total length of the timed regions of K steps each (more regions, never "
+                         "more steps per region)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-n1-anchor", action="store_true",
-                    help="N > 1: skip rank 0's one-GPU measurement of the same matrix (n1_same_run)")
+                    help="N > 1 with --full: skip rank 0's one-GPU measurement of the same matrix (n1_same_run)")
     ap.add_argument("--rehearse-line", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, initialise the process group, report the rank count, exit (launch rehearsal; "
@@ -222,6 +243,17 @@ def time_loop(torch, fn, steps, barrier):
     return t1 - t0, e0.elapsed_time(e1) * 1e-3
 
 
+def dump_output(directory, name, t, max_bytes=DUMP_BYTES):
+    """--dump-outputs: the device array `t` as DIR/<name>.npy in float64.  Beyond `max_bytes` a fixed sample of its
+    rows (seed 0, kept in row order): the same rows on every run with the same arguments."""
+    a = t.detach().cpu().numpy().astype(np.float64, copy=False)
+    keep = max(1, max_bytes // (8 * max(1, a[0].size)))
+    if a.shape[0] > keep:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with no WORLD_SIZE: start N rank processes (one per GPU) as CHILDREN of this
     process -- which has made no GPU call and never will -- and exit with their code.  A process that has
@@ -317,12 +349,12 @@ def rehearse_line(args, world, rank):
         anchor = {"workload": f"{g}^3 7-pt Poisson on one GPU (rehearsal)", "spmv_gflops": 1000.0, "spmv_us": 2e-3 * nnz_global,
                   "spmv_frac_of_8tbs": 0.5, "cg": {"iters_per_sec": 100.0, "iterations": 500}}
     dist.barrier()
-    steps = max(10, args.steps // 4)
+    steps = args.steps
     t = torch.tensor([steps * 2e-9 * nnz_global / (world * 1000.0) * (1.0 + 0.1 * rank)], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall = float(t.item())
     out = {"metric": p3_metric(g), "value": round(2.0 * nnz_global * steps / wall / 1e9, 2), "unit": "GFLOP/s", "n_gpus": world,
-           "steps": steps, "warmup": max(3, args.warmup // 4), "ms_per_step": round(wall / steps * 1e3, 5),
+           "steps": steps, "warmup": args.warmup, "ms_per_step": round(wall / steps * 1e3, 5),
            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
            "rehearsal": True, "cg": {"iters_per_sec": 100.0 * world * 0.8, "iterations": 500}}
     if rank == 0:
@@ -337,6 +369,8 @@ def main():
         return
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)   # does not return
     if args.rendezvous_only and args.rehearse_line:
@@ -535,13 +569,14 @@ def main():
         progress("P2: timing the cold SpMV")
         for i in range(args.warmup):
             step_cold(i)
-        (wall, ev), regions = timed_region(step_cold, args.steps)
+        wall, ev = time_loop(torch, step_cold, args.steps, barrier)
+        if args.dump_outputs:   # the y of the last timed step, before anything else writes to it
+            dump_output(args.dump_outputs, "y", copies[(args.steps - 1) % ncopies][4])
         out = {
             "metric": "CSR SpMV GFLOP/s (fp64, 1M-row 5-pt Poisson per GPU)",
             "value": round(flops_per_launch * args.steps / wall / 1e9, 2), "unit": "GFLOP/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(wall / args.steps * 1e3, 5),
-            "timing": f"median of {len(regions)} timed regions of {args.steps} steps each "
-                      f"(>= {args.min_region_seconds} s of measured steps)", "timing_spread": spread(regions, args.steps),
+            "timing": f"one timed region of {args.steps} steps",
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": "benchmark/spmv: CSR fp64/int32 y=Ax on 1000x1000 5-pt Poisson "
                                    "(n=1e6, nnz=4996000), x=sin(0.01 i)",
@@ -561,43 +596,47 @@ def main():
                                               "(tools/profile.sh), not re-measured in this run") if traffic_file else None,
                            "kernel": "csr_split_kernel", "bytes_per_launch": bytes_per_launch,
                            "us_per_launch": round(kern_s * 1e6, 3),
-                           "clock": "HIP events on the launch stream around the K steps of the median region "
+                           "clock": "HIP events on the launch stream around the K steps of the timed region "
                                     "(achieved, frac, us_per_launch); value / ms_per_step use the host wall clock of "
                                     "the same region",
                            "frac_by_wall_clock": round(bytes_per_launch * args.steps / wall / 1e9 / HBM_PEAK_GBS, 4)}
-        # the practical ceiling of THIS box for the same bytes: a pure 16-B streaming kernel over the same
-        # rotating copies (no gather, no LDS, no dependent access), best grid of four, same region policy
-        progress("P2: streaming ceiling for the same byte mix")
-        ceiling = {}
-        for blocks in (1024, 2048, 4096, 8192):
-            stepm = lambda i, blocks=blocks: gk.diag_stream_csr_bytes(stream, blocks, n, nnz, copies[i % ncopies][0],
-                                                                      copies[i % ncopies][1], copies[i % ncopies][2],
-                                                                      copies[i % ncopies][3], copies[i % ncopies][4])
-            for i in range(ncopies):
-                stepm(i)
-            (_, mev), mreg = timed_region(stepm, args.steps)
-            ceiling[blocks] = mev / args.steps * 1e6
-        best_blocks = min(ceiling, key=ceiling.get)
-        out["roofline"]["practical_ceiling_us"] = round(ceiling[best_blocks], 3)
-        out["roofline"]["practical_ceiling_gbs"] = round(bytes_per_launch / ceiling[best_blocks] / 1e3, 1)
-        out["roofline"]["frac_of_practical_ceiling"] = round(ceiling[best_blocks] / (kern_s * 1e6), 4)
-        out["roofline"]["practical_ceiling_note"] = (
-            f"gkomi_diag_stream_csr_bytes ({best_blocks} workgroups; all grids: "
-            + ", ".join(f"{b}: {t:.2f} us" for b, t in ceiling.items())
-            + "): the same 79 952 004 B as pure coalesced 16-B streams, cold over the same copies, same run")
-        for c in copies:   # the probe overwrote y
-            launch(c, cold_strategy)
-        for i in range(args.warmup):
-            step_warm(i)
-        (wwall, wev), wregions = timed_region(step_warm, args.steps)
-        out["warm"] = {"gflops": round(flops_per_launch * args.steps / wwall / 1e9, 2),
-                       "gbs": round(bytes_per_launch * args.steps / wev / 1e9, 1),
-                       "us_per_launch": round(wev / args.steps * 1e6, 3), "timing_spread": spread(wregions, args.steps),
-                       "note": "same matrix every step (benchmark/spmv methodology), automatic strategy; the 80 MB "
-                               "working set is Infinity-Cache resident"}
+        if args.full:
+            # the spread of the headline: further regions of K steps under the region policy of the other legs
+            _, regions = timed_region(step_cold, args.steps)
+            out["timing_spread"] = spread(regions, args.steps)
+            # the practical ceiling of THIS box for the same bytes: a pure 16-B streaming kernel over the same
+            # rotating copies (no gather, no LDS, no dependent access), best grid of four, same region policy
+            progress("P2: streaming ceiling for the same byte mix")
+            ceiling = {}
+            for blocks in (1024, 2048, 4096, 8192):
+                stepm = lambda i, blocks=blocks: gk.diag_stream_csr_bytes(stream, blocks, n, nnz, copies[i % ncopies][0],
+                                                                          copies[i % ncopies][1], copies[i % ncopies][2],
+                                                                          copies[i % ncopies][3], copies[i % ncopies][4])
+                for i in range(ncopies):
+                    stepm(i)
+                (_, mev), mreg = timed_region(stepm, args.steps)
+                ceiling[blocks] = mev / args.steps * 1e6
+            best_blocks = min(ceiling, key=ceiling.get)
+            out["roofline"]["practical_ceiling_us"] = round(ceiling[best_blocks], 3)
+            out["roofline"]["practical_ceiling_gbs"] = round(bytes_per_launch / ceiling[best_blocks] / 1e3, 1)
+            out["roofline"]["frac_of_practical_ceiling"] = round(ceiling[best_blocks] / (kern_s * 1e6), 4)
+            out["roofline"]["practical_ceiling_note"] = (
+                f"gkomi_diag_stream_csr_bytes ({best_blocks} workgroups; all grids: "
+                + ", ".join(f"{b}: {t:.2f} us" for b, t in ceiling.items())
+                + "): the same 79 952 004 B as pure coalesced 16-B streams, cold over the same copies, same run")
+            for c in copies:   # the probe overwrote y
+                launch(c, cold_strategy)
+            for i in range(args.warmup):
+                step_warm(i)
+            (wwall, wev), wregions = timed_region(step_warm, args.steps)
+            out["warm"] = {"gflops": round(flops_per_launch * args.steps / wwall / 1e9, 2),
+                           "gbs": round(bytes_per_launch * args.steps / wev / 1e9, 1),
+                           "us_per_launch": round(wev / args.steps * 1e6, 3), "timing_spread": spread(wregions, args.steps),
+                           "note": "same matrix every step (benchmark/spmv methodology), automatic strategy; the 80 MB "
+                                   "working set is Infinity-Cache resident"}
 
-        progress("P2: CG solves")
-        if not args.no_cg:
+        if args.full and not args.no_cg:
+            progress("P2: CG solves")
             A2 = as_csr(n, copies[0])
             sb, b = sinus_system(A2)
             cg_bytes = 11 * 8 * n + (12 * nnz + 4 * (n + 1))  # per iteration: 11 n values + matrix
@@ -633,13 +672,14 @@ def main():
             out["cg_rhs_ones"] = cg_entry(*timed_cg(A2, ones))
             launch(copies[0], cold_strategy)
             torch.cuda.synchronize()
-        got_p2 = copies[0][4].cpu().numpy().copy()
+        if args.full:
+            got_p2 = copies[0][4].cpu().numpy().copy()
 
-        if not args.no_p3:
+        if args.full and not args.no_p3:
             del copies[1:]
             out["p3"] = p3_one_gpu()
 
-        if not args.no_config4:
+        if args.full and not args.no_config4:
             # BASELINE config 4's shape (GMRES(30) + ParILU on a 1.26M-row 7-point convection-diffusion system):
             # an extra entry, never allowed to take the headline line down with it
             try:
@@ -710,7 +750,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 out["config4"] = {"error": repr(e)}
 
-        if not args.no_config3:
+        if args.full and not args.no_config3:
             # BASELINE config 3 (benchmark/solver: CG + block-Jacobi(32) on thermal2, 1.2 M rows) on SURVEY 8(d)'s
             # stand-ins; what benchmark/solver/solver.cpp:488-534 reports: generate time, apply time, iterations --
             # plus the apply's roofline (8 x stored block elements + 4 (#blocks + 1) + 16 n bytes)
@@ -765,7 +805,7 @@ def main():
             except Exception as e:  # noqa: BLE001 - an extra entry, never allowed to take the headline down
                 out["config3"] = {"error": repr(e)}
 
-        if not args.no_irregular:
+        if args.full and not args.no_irregular:
             # north_star names SuiteSparse; its graph-like matrices are this class (no files offline: stand-ins of
             # tools/spmv_classes.json): the automatic CSR strategy and the opt-in column-partitioned copy (csrp)
             try:
@@ -806,7 +846,7 @@ def main():
             except Exception as e:  # noqa: BLE001 - an extra entry, never allowed to take the headline down
                 out["irregular"] = {"error": repr(e)}
 
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             progress("CPU baseline (3 child processes)")
             base = cpu_baseline(args.cpu_seconds)
             out["cpu_baseline"] = base
@@ -825,7 +865,7 @@ def main():
         # the curve's own N = 1 point: the whole matrix on rank 0's GPU (1.7 GB), SpMV + CG, before anything
         # distributed is built; the other ranks wait at the barrier
         anchor = None
-        if rank == 0 and not args.no_n1_anchor:
+        if rank == 0 and args.full and not args.no_n1_anchor:
             try:
                 anchor = p3_one_gpu(local=True)
             except Exception as ex:  # noqa: BLE001 - the line says so instead of dying
@@ -859,16 +899,21 @@ def main():
             step = lambda i: A.apply(comm, x, y)
         else:
             step = lambda i: M.apply(x, y)
-        for i in range(max(3, args.warmup // 4)):
+        for i in range(args.warmup):
             step(i)
-        steps = max(10, args.steps // 4)
-        (wall, ev), regions = timed_region(step, steps)
+        steps = args.steps
+        wall, ev = time_loop(torch, step, steps, barrier)
+        t = torch.tensor([wall, ev], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        wall, ev = float(t[0].item()), float(t[1].item())
+        if args.dump_outputs:   # each rank's rows of y after the last timed step
+            dump_output(args.dump_outputs, f"y_rank{rank}", y, DUMP_BYTES // world)
         local_bytes = algorithmic_bytes(n_loc, n_loc + M.non_local[1], nnz_local)
         out = {
             "metric": p3_metric(g),
             "value": round(2.0 * nnz_global * steps / wall / 1e9, 2), "unit": "GFLOP/s", "n_gpus": world,
-            "steps": steps, "warmup": max(3, args.warmup // 4), "ms_per_step": round(wall / steps * 1e3, 5),
-            "timing": f"median of {len(regions)} timed regions of {steps} steps each", "timing_spread": spread(regions, steps),
+            "steps": steps, "warmup": args.warmup, "ms_per_step": round(wall / steps * 1e3, 5),
+            "timing": f"one timed region of {steps} steps, max over ranks",
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"distributed-solver: row-partitioned y=Ax and CG on {g}^3 7-pt Poisson "
                                    f"(n={n_global}, nnz={nnz_global}), {world} contiguous row slabs, RCCL halo exchange",
@@ -881,7 +926,10 @@ def main():
                          "kernel": "distributed apply (rank 0's share: local block + non-local rows)",
                          "bytes_per_launch": local_bytes, "us_per_launch": round(ev / steps * 1e6, 3)},
         }
-        if not args.no_cg:
+        if args.full:
+            _, regions = timed_region(step, steps)
+            out["timing_spread"] = spread(regions, steps)
+        if args.full and not args.no_cg:
             # sinus right-hand side of benchmark/solver: b = A s / |s|, s_i = sin(i)
             s_loc = np.sin(np.arange(lo, hi, dtype=np.float64))
             nrm = torch.tensor([float(np.sum(s_loc * s_loc))], dtype=torch.float64, device=device)

@@ -67,3 +67,21 @@ def test_attach_anchor_without_an_anchor_says_so():
     import bench
     out = bench.attach_anchor({"value": 5.0}, None, 4)
     assert out["n1_same_run"] is None and out["parallel_efficiency"] is None
+
+
+def test_dump_output_is_float64_and_a_fixed_sample_beyond_its_budget(tmp_path):
+    """--dump-outputs: the whole array when it fits the budget, else the same seeded rows (in row order) on every
+    run, so that two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(1000, dtype=torch.float64).reshape(-1, 1)
+    bench.dump_output(str(tmp_path / "a"), "y", small)
+    assert np.array_equal(np.load(tmp_path / "a" / "y.npy"), small.numpy())
+    big = torch.arange(100000, dtype=torch.float64).reshape(-1, 1)
+    for d in ("b", "c"):
+        bench.dump_output(str(tmp_path / d), "y", big, max_bytes=8000)
+    b, c = np.load(tmp_path / "b" / "y.npy"), np.load(tmp_path / "c" / "y.npy")
+    assert b.dtype == np.float64 and b.shape == (1000, 1) and b.nbytes <= 8000
+    assert np.array_equal(b, c) and np.all(np.diff(b[:, 0]) > 0)

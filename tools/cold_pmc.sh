@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/r04_cold_pmc
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --no-p3 --no-config3 --no-config4 --no-cg --steps 100 --warmup 10 --min-region-seconds 0.0"
+ARGS="--full --no-cpu-baseline --no-p3 --no-config3 --no-config4 --no-cg --steps 100 --warmup 10 --min-region-seconds 0.0"
 timeout -k 10 300 rocprofv3 --pmc TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_sum --output-format csv -d $OUT/level -- python3 $ROOT/bench.py $ARGS > $OUT/level.log 2>&1 || { tail -5 $OUT/level.log; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py $ARGS > $OUT/trace.log 2>&1 || { tail -5 $OUT/trace.log; exit 1; }
 python3 - $OUT <<'PY'

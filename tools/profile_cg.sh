@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --no-cpu-baseline --steps 50 --warmup 10 ${@:2} > $OUT/trace.log 2> $OUT/trace.err || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 50 --warmup 10 ${@:2} > $OUT/trace.log 2> $OUT/trace.err || exit 1
 python3 - $OUT <<'PY'
 import csv, glob, os, sys
 out = sys.argv[1]

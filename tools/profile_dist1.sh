@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export GKOMI_BENCH_FORCE_DIST=1
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --p3-grid 128 --no-cpu-baseline > $OUT/trace.log 2> $OUT/trace.err || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --p3-grid 128 --no-cpu-baseline > $OUT/trace.log 2> $OUT/trace.err || exit 1
 python3 - $OUT <<'PY'
 import csv, glob, os, sys
 out = sys.argv[1]
