@@ -276,6 +276,51 @@ int gkomi_cg_solve_f32(gkomi_stream_t s, int64_t n, int64_t nnz, const int32_t* 
                        float* x, int64_t max_iters, float reduction, int baseline,
                        void* workspace, size_t workspace_bytes, double* host_info);
 
+/* ---- mixed precision: convert_precision<double <-> float>, a device-resident Cg<float>, and
+ * Ir<double> with that Cg<float> as its inner solver; csrc/mixed.hip.
+ *
+ * components::convert_precision (core/components/precision_conversion_kernels.hpp:53,
+ * common/unified/components/precision_conversion_kernels.cpp): out(i, j) = static_cast of
+ * in(i, j) -- round to nearest even, beyond FLT_MAX -> +-inf, NaN stays NaN, +-0 keep their
+ * sign, float subnormals kept; f32 -> f64 exact.  The padding between rows of `out` is not
+ * touched.  A CSR value array converts as nnz x 1. */
+int gkomi_dense_convert_f64_to_f32(gkomi_stream_t s, int64_t nrows, int64_t ncols,
+                                   const double* in, int64_t in_stride, float* out,
+                                   int64_t out_stride);
+int gkomi_dense_convert_f32_to_f64(gkomi_stream_t s, int64_t nrows, int64_t ncols,
+                                   const float* in, int64_t in_stride, double* out,
+                                   int64_t out_stride);
+/* Cg<float>::apply_dense_impl (core/solver/cg.cpp:107-193) as three launches per iteration
+ * (the design of gkomi_cg_solve_f64_i32 mode 1): criterion on the device, the host follows
+ * the solve without a blocking copy per iteration.  One right-hand side, Identity
+ * preconditioner, Combined(Iteration(max_iters), ResidualNorm(reduction, baseline)), x the
+ * initial guess (16-B aligned, GKOMI_ENOTSUPPORTED otherwise).  Vectors and matrix are float,
+ * partial sums double.  host_info[4] = { iterations, converged, ||r||, baseline norm }. */
+size_t gkomi_cg_fused_workspace_bytes_f32(int64_t n);
+int gkomi_cg_solve_fused_f32_i32(gkomi_stream_t s, int64_t n, int64_t nnz,
+                                 const int32_t* row_ptrs, const int32_t* col_idxs,
+                                 const float* vals, const float* b, float* x,
+                                 int64_t max_iters, double reduction, int baseline,
+                                 void* workspace, size_t workspace_bytes, double* host_info);
+/* Ir<double>::apply_dense_impl (core/solver/ir.cpp:188-277) with Cg<float> as the inner solver
+ * (precision_dispatch, include/ginkgo/core/base/precision_dispatch.hpp:73-96): per outer
+ * iteration r = b - A x in double (the automatic CSR apply), Combined(Iteration(max_iters),
+ * ResidualNorm(reduction, baseline)) on ||r||, the fused Cg<float> above on (float) r with
+ * (float) r as its initial guess (inner_max_iters, inner_reduction, inner_baseline), then
+ * x += relaxation_factor * (double) d.  vals_f32: the caller's float copy of vals.  nrhs must
+ * be 1 (GKOMI_ENOTSUPPORTED otherwise).  The host looks at the device once per outer iteration.
+ * host_info[6] = { outer iterations, converged, final ||r||, baseline norm, total inner
+ * iterations, inner solves stopped by their iteration cap }. */
+size_t gkomi_ir_mixed_workspace_bytes(int64_t n);
+int gkomi_ir_mixed_solve_f64_i32(gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t nnz,
+                                 const int32_t* row_ptrs, const int32_t* col_idxs,
+                                 const double* vals, const float* vals_f32, int spmv_strategy,
+                                 int64_t max_row_nnz_hint, const double* b, double* x,
+                                 int64_t max_iters, double reduction, int baseline,
+                                 int64_t inner_max_iters, double inner_reduction,
+                                 int inner_baseline, double relaxation_factor, void* workspace,
+                                 size_t workspace_bytes, double* host_info);
+
 /* ---- column-partitioned copy: an analysis-based CSR strategy for scattered columns --
  * Role: the reference's `sparselib` strategy (hipSPARSE csrmv behind an analysis,
  * hip/matrix/csr_kernels.hip.cpp:293-330) -- a second representation built once per

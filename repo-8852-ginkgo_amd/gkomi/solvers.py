@@ -148,6 +148,35 @@ def ir_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, relaxation_factor=1.0, 
             "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
 
 
+def ir_mixed(gk, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=100, reduction=1e-12, baseline="rhs_norm",
+             inner_max_iters=100, inner_reduction=1e-2, inner_baseline="rhs_norm", relaxation_factor=1.0,
+             strategy=0, max_row_nnz=-1):
+    """Ir<double> with Cg<float> as its inner solver (mixed-precision iterative refinement), x as the
+    initial guess: the outer residual and x stay in double, each correction comes from the fused float
+    CG.  vals is the float64 value array; its float copy is made here for this call (one pass over the
+    values).  Returns dict(x, iterations, converged, residual_norm, baseline_norm, rel_residual,
+    inner_iterations, inner_capped)."""
+    b2 = b.reshape(n, 1)
+    if x is None:
+        x = torch.zeros_like(b2)
+    x2 = x.reshape(n, 1)
+    assert b2.is_contiguous() and x2.is_contiguous()
+    nnz = int(vals.numel())
+    stream = torch.cuda.current_stream().cuda_stream
+    vals_f32 = torch.empty(nnz, dtype=torch.float32, device=vals.device)
+    gk.dense_convert_f64_to_f32(stream, nnz, 1, vals, 1, vals_f32, 1)
+    nbytes = gk.ir_mixed_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
+    info = np.zeros(6, dtype=np.float64)
+    gk.ir_mixed_solve_f64_i32(stream, n, 1, nnz, row_ptrs, col_idxs, vals, vals_f32, strategy, max_row_nnz, b2, x2,
+                              max_iters, reduction, BASELINES[baseline], inner_max_iters, inner_reduction,
+                              BASELINES[inner_baseline], relaxation_factor, ws, nbytes, info)
+    res, base = float(info[2]), float(info[3])
+    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]), "converged": bool(info[1]),
+            "residual_norm": res, "baseline_norm": base, "rel_residual": res / (base if base != 0 else 1.0),
+            "inner_iterations": int(info[4]), "inner_capped": int(info[5])}
+
+
 def solve_op(gk, solver, matrix, b, x=None, max_iters=1000, reduction=1e-10, baseline="rhs_norm", precond=None,
              krylov_dim=100, check_every=8, fused=False):
     """Any solver in {"cg", "gmres", "bicgstab", "fcg", "cgs"} on a system matrix in

@@ -446,6 +446,25 @@ template <typename T>
 std::shared_ptr<T> share(std::shared_ptr<T> p) { return p; }
 template <typename T>
 std::unique_ptr<T> give(std::unique_ptr<T>&& p) { return std::move(p); }
+// give(an lvalue): hands the object over, like the reference's std::move wrapper (utils_helper.hpp)
+template <typename T>
+std::unique_ptr<T> give(std::unique_ptr<T>& p) { return std::move(p); }
+// gko::clone(exec, obj) (utils_helper.hpp): a copy of *obj on exec
+template <typename Ptr>
+auto clone(std::shared_ptr<const Executor> exec, const Ptr& p) -> decltype(p->clone(exec)) { return p->clone(std::move(exec)); }
+template <typename Ptr>
+auto clone(const Ptr& p) -> decltype(p->clone()) { return p->clone(); }
+namespace detail {
+// components::convert_precision<double <-> float> (core/components/precision_conversion_kernels.hpp:53)
+inline int convert_precision(int64_t nrows, int64_t ncols, const double* in, int64_t in_stride, float* out, int64_t out_stride)
+{
+    return gkomi_dense_convert_f64_to_f32(nullptr, nrows, ncols, in, in_stride, out, out_stride);
+}
+inline int convert_precision(int64_t nrows, int64_t ncols, const float* in, int64_t in_stride, double* out, int64_t out_stride)
+{
+    return gkomi_dense_convert_f32_to_f64(nullptr, nrows, ncols, in, in_stride, out, out_stride);
+}
+}  // namespace detail
 template <typename T, typename U>
 T* as(U* p)
 {
@@ -747,6 +766,22 @@ public:
         d->copy_from(this);
         return d;
     }
+    // Dense<double> <-> Dense<float> (core/matrix/dense.cpp convert_to(Dense<next_precision>*)): components::convert_precision
+    template <typename W, typename = typename std::enable_if<!std::is_same<W, V>::value>::type>
+    void convert_to(Dense<W>* result) const
+    {
+        kernel("components::convert_precision");
+        if (result->get_size() != size_) {
+            result->values_ = array<W>(result->get_executor(), size_[0] * size_[1]);
+            result->stride_ = size_[1];
+            result->set_size(size_);
+        }
+        GKOMI_CALL(::gko::detail::convert_precision(rows(), cols(), get_const_values(), stride_, result->get_values(), result->get_stride()));
+    }
+    template <typename W, typename = typename std::enable_if<!std::is_same<W, V>::value>::type>
+    void move_to(Dense<W>* result) { convert_to(result); }
+    void convert_to(Dense* result) const { result->copy_from(this); }
+    void move_to(Dense* result) { result->copy_from(this); }
     void scale(const Dense* alpha) { kernel("dense::scale"); GKOMI_CALL(gkomi_dense_scale_f64(nullptr, rows(), cols(), alpha->get_const_values(), alpha->cols(), get_values(), stride_)); }
     void inv_scale(const Dense* alpha) { kernel("dense::inv_scale"); GKOMI_CALL(gkomi_dense_inv_scale_f64(nullptr, rows(), cols(), alpha->get_const_values(), alpha->cols(), get_values(), stride_)); }
     void add_scaled(const Dense* alpha, const Dense* b)
@@ -804,6 +839,8 @@ protected:
     void apply_impl(const LinOp*, const LinOp*, const LinOp*, LinOp*) const override { GKO_NOT_IMPLEMENTED; }
     array<V> values_;
     size_type stride_;
+    template <typename>
+    friend class Dense;
 };
 
 namespace detail_fmt {
@@ -987,6 +1024,26 @@ public:
         data.nonzeros.clear();
         for (size_type r = 0; r < size_[0]; ++r) for (I k = rp[r]; k < rp[r + 1]; ++k) data.nonzeros.push_back({static_cast<I>(r), ci[k], v[k]});
     }
+    // Csr<double, int32> <-> Csr<float, int32> (core/matrix/csr.cpp convert_to(Csr<next_precision>*)): the indices copied,
+    // the values through components::convert_precision (nnz x 1), the strategy carried over
+    template <typename W, typename = typename std::enable_if<!std::is_same<W, V>::value>::type>
+    void convert_to(Csr<W, I>* result) const
+    {
+        static_assert(std::is_same<I, int32>::value, "precision conversion: int32 indices");
+        detail::require_device(exec_, "components::convert_precision");
+        const size_type nnz = get_num_stored_elements();
+        auto rexec = result->get_executor();
+        array<I> rp(rexec, size_[0] + 1), ci(rexec, nnz);
+        array<W> v(rexec, nnz);
+        exec_->copy(size_[0] + 1, get_const_row_ptrs(), rp.get_data());
+        exec_->copy(nnz, get_const_col_idxs(), ci.get_data());
+        GKOMI_CALL(::gko::detail::convert_precision(static_cast<int64_t>(nnz), 1, get_const_values(), 1, v.get_data(), 1));
+        result->adopt(size_, std::move(rp), std::move(ci), std::move(v));
+        result->set_strategy(std::make_shared<typename Csr<W, I>::strategy_type>(strategy_->get_name(), strategy_->get_code()));
+        result->max_row_nnz_ = max_row_nnz_;
+    }
+    template <typename W, typename = typename std::enable_if<!std::is_same<W, V>::value>::type>
+    void move_to(Csr<W, I>* result) { convert_to(result); }
     void convert_to(Coo<V, I>* result) const;
     void convert_to(Ell<V, I>* result) const;
     void convert_to(Sellp<V, I>* result) const;
@@ -1123,6 +1180,8 @@ protected:
     mutable std::unique_ptr<gkomi_csr_colpart, colpart_deleter> colpart_;
     mutable array<char> colpart_plan_;
     mutable bool colpart_dirty_{false};
+    template <typename, typename>
+    friend class Csr;
 };
 
 // core/matrix/csr_builder.hpp:47-83: intrusive access to a Csr's arrays for kernels that rebuild them
@@ -1962,6 +2021,8 @@ public:
         return f;
     }
     std::unique_ptr<Solver> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Solver>(new Solver(static_cast<const typename Solver::Factory*>(this), std::move(A))); }
+    template <typename M>
+    std::unique_ptr<Solver> generate(std::unique_ptr<M>&& A) const { return generate(std::shared_ptr<const LinOp>(std::move(A))); }
     std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
     stop::criterion_settings settings() const
     {
@@ -1991,6 +2052,8 @@ public:
     // filled by the last apply
     int64_t get_last_iteration_count() const noexcept { return last_iters_; }
     bool has_converged() const noexcept { return last_converged_; }
+    // what the criteria of the factory amount to (the role of get_stop_criterion_factory())
+    const stop::criterion_settings& get_stop_settings() const noexcept { return settings_; }
 protected:
     friend class detail::factory_base<Cg>;
     Cg(const Factory* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings())
@@ -2007,6 +2070,18 @@ protected:
         auto A = dynamic_cast<const matrix::Csr<float, int32>*>(A_.get());
         auto db = dynamic_cast<const matrix::Dense<float>*>(b);
         auto dx = dynamic_cast<matrix::Dense<float>*>(x);
+        auto db64 = A ? dynamic_cast<const matrix::Dense<double>*>(b) : nullptr;
+        auto dx64 = A ? dynamic_cast<matrix::Dense<double>*>(x) : nullptr;
+        if (db64 && dx64) {
+            // Dense<double> operands: through temporary float copies (precision_dispatch, precision_dispatch.hpp:73-96)
+            auto bf = matrix::Dense<float>::create(exec_, db64->get_size());
+            auto xf = matrix::Dense<float>::create(exec_, dx64->get_size());
+            db64->convert_to(bf.get());
+            dx64->convert_to(xf.get());
+            solve_as(float{}, bf.get(), xf.get());
+            xf->convert_to(dx64);
+            return;
+        }
         if (!A || !db || !dx || precond_ || settings_.implicit || db->get_size()[1] != 1 || db->get_stride() != 1 || dx->get_stride() != 1) {
             GKO_NOT_SUPPORTED("Cg<float>: Csr<float, int32> system, Dense<float> vectors of one contiguous column, Iteration + ResidualNorm, no preconditioner");
         }
@@ -2255,6 +2330,9 @@ public:
     std::shared_ptr<const LinOp> get_solver() const { return inner_; }
     int64_t get_last_iteration_count() const noexcept { return last_iters_; }
     bool has_converged() const noexcept { return last_converged_; }
+    // inner iterations of the last apply, summed over its inner solves: known when it ran as the native
+    // mixed-precision driver (-1 otherwise)
+    int64_t get_last_inner_iteration_count() const noexcept { return last_inner_iters_; }
 protected:
     friend class detail::factory_base<Ir>;
     Ir(const Factory* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings()), relaxation_factor_(f->relaxation_factor_)
@@ -2262,8 +2340,40 @@ protected:
         if (size_[0] != size_[1]) throw DimensionMismatch(__FILE__, __LINE__, "Ir needs a square system matrix");
         inner_ = f->precond_ ? f->precond_ : (f->precond_factory_ ? std::shared_ptr<const LinOp>(f->precond_factory_->generate_impl(A_)) : nullptr);
     }
+    // Ir<double> over a generated Cg<float> on a Csr<float, int32> (the float copy of the Csr<double, int32> system),
+    // both with Iteration + ResidualNorm, no inner preconditioner, one column: mixed-precision iterative refinement as one
+    // native driver (gkomi_ir_mixed_solve_f64_i32).  false: not this configuration, the general path runs.
+    bool mixed_as(float, const LinOp*, LinOp*) const { return false; }
+    bool mixed_as(double, const LinOp* b, LinOp* x) const
+    {
+        auto inner = dynamic_cast<const Cg<float>*>(inner_.get());
+        if (!inner || inner->get_preconditioner() || settings_.implicit || settings_.reduction_factor < 0) return false;
+        const auto& is = inner->get_stop_settings();
+        if (is.implicit || is.reduction_factor < 0) return false;
+        auto A = dynamic_cast<const matrix::Csr<double, int32>*>(A_.get());
+        auto Af = dynamic_cast<const matrix::Csr<float, int32>*>(inner->get_system_matrix().get());
+        auto db = dynamic_cast<const matrix::Dense<double>*>(b);
+        auto dx = dynamic_cast<matrix::Dense<double>*>(x);
+        if (!A || !Af || !db || !dx || db->get_size()[1] != 1 || db->get_stride() != 1 || dx->get_stride() != 1) return false;
+        if (Af->get_size() != A->get_size() || Af->get_num_stored_elements() != A->get_num_stored_elements()) return false;
+        ::gko::detail::require_device(exec_, "ir::apply");
+        const int64_t n = size_[0];
+        array<char> ws(exec_, gkomi_ir_mixed_workspace_bytes(n));
+        double info[6] = {};
+        GKOMI_CALL(gkomi_ir_mixed_solve_f64_i32(nullptr, n, 1, A->get_num_stored_elements(), A->get_const_row_ptrs(), A->get_const_col_idxs(),
+                                                A->get_const_values(), Af->get_const_values(), A->get_strategy()->get_code(), A->get_max_row_nnz(),
+                                                db->get_const_values(), dx->get_values(), settings_.max_iters, settings_.reduction_factor,
+                                                detail::baseline_code(settings_.baseline), is.max_iters, is.reduction_factor,
+                                                detail::baseline_code(is.baseline), relaxation_factor_, ws.get_data(), ws.get_num_elems(), info));
+        last_iters_ = static_cast<int64_t>(info[0]);
+        last_converged_ = info[1] != 0.0;
+        last_inner_iters_ = static_cast<int64_t>(info[4]);
+        return true;
+    }
     void apply_impl(const LinOp* b, LinOp* x) const override
     {
+        last_inner_iters_ = -1;
+        if (mixed_as(V{}, b, x)) return;
         ::gko::detail::require_device(exec_, "ir::apply");
         auto csr = as<const matrix::Csr<V, int32>>(A_.get());
         auto db = matrix::detail_fmt::dense(b); auto dx = matrix::detail_fmt::dense(x);
@@ -2293,6 +2403,7 @@ protected:
     V relaxation_factor_;
     mutable int64_t last_iters_{-1};
     mutable bool last_converged_{false};
+    mutable int64_t last_inner_iters_{-1};
 };
 
 template <typename V = double>
