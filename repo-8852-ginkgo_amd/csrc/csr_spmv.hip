@@ -62,10 +62,6 @@ __device__ __forceinline__ int xcd_chunked_block(int bid, int per)
 // launch is skipped when stop_status[0] says the solver has stopped.
 typedef double nt_double2 __attribute__((ext_vector_type(2)));
 typedef int nt_int2 __attribute__((ext_vector_type(2)));
-// pairs of the nonzero-split kernel: 16/8 bytes per lane, but only element-aligned
-// when the pair was pulled back to the end of the arrays
-typedef double split_double2 __attribute__((ext_vector_type(2), aligned(8)));
-typedef int split_int2 __attribute__((ext_vector_type(2), aligned(4)));
 
 // Index types of the boundary's instantiations that exist here (include/ginkgo/core/base/types.hpp:544-560:
 // {int32, int64}): positions in the nonzero arrays are `pos` (int for int32 matrices: the address arithmetic of
@@ -76,14 +72,12 @@ struct index_traits;
 template <>
 struct index_traits<int32_t> {
     using pos = int;
-    typedef int vec2 __attribute__((ext_vector_type(2)));                  // aligned pairs (stream kernel)
-    typedef int split_vec2 __attribute__((ext_vector_type(2), aligned(4)));  // element-aligned pairs (split kernel)
+    typedef int vec2 __attribute__((ext_vector_type(2)));  // aligned pairs (stream kernel)
 };
 template <>
 struct index_traits<int64_t> {
     using pos = int64_t;
     typedef long vec2 __attribute__((ext_vector_type(2)));
-    typedef long split_vec2 __attribute__((ext_vector_type(2), aligned(8)));
 };
 template <typename I>
 struct index_pair {
@@ -297,6 +291,10 @@ __device__ __forceinline__ double add_products(double sum, const double* prod, i
 #ifndef GKOMI_DOT_PROBE
 #define GKOMI_DOT_PROBE 0
 #endif
+// tools/gather_probe.hip only: 1 replaces the addresses of the gather of b by lane-linear ones.  0 in the product.
+#ifndef GKOMI_GATHER_PROBE
+#define GKOMI_GATHER_PROBE 0
+#endif
 template <typename I, int Block, int Tile, int MaxOver, bool Advanced, bool Swizzle,
           bool Dot = false, bool NT = false, bool ColsFirst = true>
 __global__ __launch_bounds__(Block) void csr_split_kernel(
@@ -316,10 +314,9 @@ __global__ __launch_bounds__(Block) void csr_split_kernel(
     )
 {
     using pos_t = typename index_traits<I>::pos;
-    using isplit2 = typename index_traits<I>::split_vec2;
-    constexpr int pairs = Tile / (2 * Block);
-    static_assert(Tile % (2 * Block) == 0, "tile must be a whole number of pair sweeps");
-    static_assert(MaxOver <= 2 * Block && MaxOver % 2 == 0, "one extra pair per lane at most");
+    constexpr int sweeps = Tile / Block;
+    static_assert(Tile % Block == 0, "tile must be a whole number of sweeps");
+    static_assert(MaxOver <= Block, "one extra nonzero per lane at most");
     // tools/spmv_timeline.hip only: per-workgroup phase stamps (100 MHz
     // s_memrealtime, comparable across CUs) into a buffer nothing else reads
 #ifdef GKOMI_TIMELINE
@@ -371,41 +368,42 @@ __global__ __launch_bounds__(Block) void csr_split_kernel(
     // here cost the 1M-row matrix's cold apply 1 %: 16.68 -> 16.85 us).
     const bool sparse_rows = srow_first < 0;
 
-    // 1) streaming loads: addresses known from the block index alone.  Branch-
-    //    free (a branch per load makes the compiler drain the loads before it):
-    //    a pair that would start at or behind the last nonzero reads the last
-    //    two nonzeros instead -- valid columns, products nobody adds -- and the
-    //    lane that owns nonzero nnz-1 of an odd nnz picks it out of that pair.
-    double2 v[pairs + 1];
-    index_pair<I> ci[pairs + 1];
-    auto load_cols = [&](int u, pos_t k) {
-        const isplit2* src = reinterpret_cast<const isplit2*>(col_idxs + min(k, nnz - 2));
-        const isplit2 tc = NT ? __builtin_nontemporal_load(src) : *src;
-        ci[u] = index_pair<I>{static_cast<I>(k == nnz - 1 ? tc.y : tc.x), static_cast<I>(tc.y)};
+    // 1) streaming loads: addresses known from the block index alone, ONE
+    //    nonzero per lane: lane l of a wave-instruction takes nonzero base + l, so
+    //    the gather of b below spans 64 consecutive nonzeros per instruction (about
+    //    15 distinct 64-B lines per 128 nonzeros on the 5-pt stencil, against 24
+    //    when every lane held a pair and both gather instructions of the pair
+    //    spanned the same 128).  Branch-free (a branch per load makes the compiler
+    //    drain the loads before it): a nonzero at or behind the last one reads the
+    //    last one instead -- a valid column, a product nobody adds.
+    double v[sweeps + 1];
+    I ci[sweeps + 1];
+    auto load_col = [&](int u, pos_t k) {
+        const I* src = col_idxs + min(k, nnz - 1);
+        ci[u] = NT ? __builtin_nontemporal_load(src) : *src;
     };
-    auto load_vals = [&](int u, pos_t k) {
-        const split_double2* src = reinterpret_cast<const split_double2*>(vals + min(k, nnz - 2));
-        const split_double2 tv = NT ? __builtin_nontemporal_load(src) : *src;
-        v[u] = make_double2(k == nnz - 1 ? tv.y : tv.x, tv.y);
+    auto load_val = [&](int u, pos_t k) {
+        const double* src = vals + min(k, nnz - 1);
+        v[u] = NT ? __builtin_nontemporal_load(src) : *src;
     };
-    // the pairs behind the tile (rows that start in the tile and end behind
-    // it); lanes past `over` repeat the last useful pair (one request)
-    const pos_t k_over = t0 + Tile + 2 * min(tid, max(over / 2 - 1, 0));
+    // the nonzeros behind the tile (rows that start in the tile and end behind
+    // it); lanes past `over` repeat the last useful one (one request)
+    const pos_t k_over = t0 + Tile + min(tid, max(over - 1, 0));
     if (ColsFirst) {
 #pragma unroll
-        for (int u = 0; u < pairs; ++u) load_cols(u, t0 + 2 * (tid + u * Block));
-        load_cols(pairs, k_over);
+        for (int u = 0; u < sweeps; ++u) load_col(u, t0 + tid + u * Block);
+        load_col(sweeps, k_over);
 #pragma unroll
-        for (int u = 0; u < pairs; ++u) load_vals(u, t0 + 2 * (tid + u * Block));
-        load_vals(pairs, k_over);
+        for (int u = 0; u < sweeps; ++u) load_val(u, t0 + tid + u * Block);
+        load_val(sweeps, k_over);
     } else {
 #pragma unroll
-        for (int u = 0; u < pairs; ++u) {
-            load_vals(u, t0 + 2 * (tid + u * Block));
-            load_cols(u, t0 + 2 * (tid + u * Block));
+        for (int u = 0; u < sweeps; ++u) {
+            load_val(u, t0 + tid + u * Block);
+            load_col(u, t0 + tid + u * Block);
         }
-        load_vals(pairs, k_over);
-        load_cols(pairs, k_over);
+        load_val(sweeps, k_over);
+        load_col(sweeps, k_over);
     }
 
     // 2) row_ptrs of the rows that start in this tile
@@ -442,29 +440,30 @@ __global__ __launch_bounds__(Block) void csr_split_kernel(
     }
 
     // 3) gather b (every loaded column is a stored one: always in bounds), products -> LDS
-    double2 xv[pairs + 1];
+    double xv[sweeps + 1];
 #pragma unroll
-    for (int u = 0; u <= pairs; ++u) {
-        xv[u].x = b[ci[u].x * b_stride];
-        xv[u].y = b[ci[u].y * b_stride];
+    for (int u = 0; u <= sweeps; ++u) {
+#if GKOMI_GATHER_PROBE
+        // tools/gather_probe.hip only: lane-linear stand-in addresses (8 lines of 64 B per instruction), still
+        // waiting on the loaded column (ci >> 31 is 0 for every valid one); square matrices; wrong results, only the time
+        // counts
+        xv[u] = b[(min(static_cast<int64_t>(row_begin) + tid + u * Block, static_cast<int64_t>(nrows) - 1) +
+                   (ci[u] >> 31)) * b_stride];
+#else
+        xv[u] = b[ci[u] * b_stride];
+#endif
     }
 #pragma unroll
-    for (int u = 0; u <= pairs; ++u) {
-        double2 pr;
-        if (Advanced) {
-            pr.x = (alpha * v[u].x) * xv[u].x;  // reference order: (valpha * val) * b
-            pr.y = (alpha * v[u].y) * xv[u].y;
+    for (int u = 0; u <= sweeps; ++u) {
+        // reference order: (valpha * val) * b
+        const double pr = Advanced ? (alpha * v[u]) * xv[u] : v[u] * xv[u];
+        if (u < sweeps) {
+            prod[tid + u * Block] = pr;
         } else {
-            pr.x = v[u].x * xv[u].x;
-            pr.y = v[u].y * xv[u].y;
-        }
-        if (u < pairs) {
-            *reinterpret_cast<double2*>(prod + 2 * (tid + u * Block)) = pr;
-        } else {
-            // unconditional (lanes past `over` repeat the last useful pair and
+            // unconditional (lanes past `over` repeat the last useful nonzero and
             // store the same product to the same slot): a branch here makes the
-            // compiler sink the pair's loads into it, behind all the others
-            *reinterpret_cast<double2*>(prod + static_cast<int>(k_over - t0)) = pr;
+            // compiler sink the nonzero's loads into it, behind all the others
+            prod[static_cast<int>(k_over - t0)] = pr;
         }
     }
     GKOMI_STAMP(1);
