@@ -180,8 +180,26 @@ class Csr:
         return self._colpart or None
 
     def values_changed(self):
+        """Call after writing to self.vals IN PLACE (same tensor, same pattern) and before the next apply / callback:
+        the column-partitioned copy holds values and is re-gathered here.  Nothing else is cached from the values."""
         if self._colpart:
             self.gk.csr_colpart_refresh_f64(_stream(self.vals), self._colpart[0], self.vals)
+
+    def structure_changed(self):
+        """Call after anything but an in-place write of values and before the next apply / callback: row_ptrs or
+        col_idxs written (a sort or a permutation inside the rows included), any of the three tensors replaced by
+        another, self.strategy changed.  Forgets everything derived from them -- srow, the longest row, the column
+        statistic -- and destroys the column-partitioned copy; the next apply builds them again (the copy with the
+        timed analysis: ask colpart(nb) first to pin a block count)."""
+        self.nnz = int(self.vals.numel())
+        self._max_row_nnz = None
+        self._srow = None
+        self.srow_tile = 0
+        self._gather_flags = None
+        self.gather_footprint = None
+        colpart, self._colpart = self._colpart, None
+        if colpart:
+            self.gk.csr_colpart_destroy(colpart[0])
 
     def apply(self, b, x, alpha=None, beta=None):
         dv = self.vals.device
@@ -281,6 +299,17 @@ class Csr64:
             gk.csr_make_srow_i64(_stream(self.vals), self.nrows, self.nnz, self.row_ptrs, self.srow_tile, self._srow, ne)
         return self._srow
 
+    def values_changed(self):
+        """nothing is cached from the values (no column-partitioned copy for int64 indices): here for symmetry with Csr"""
+
+    def structure_changed(self):
+        """Call after row_ptrs or col_idxs were written or any tensor was replaced, before the next apply / callback:
+        forgets srow and the longest row (see Csr.structure_changed)"""
+        self.nnz = int(self.vals.numel())
+        self._max_row_nnz = None
+        self._srow = None
+        self.srow_tile = 0
+
     def apply(self, b, x, alpha=None, beta=None):
         dv = self.vals.device
         self.gk.csr_spmv_srow_f64_i64(_stream(self.vals), self.nrows, self.ncols, b.shape[1], self.nnz, self.row_ptrs,
@@ -315,8 +344,20 @@ class Coo:
                      self.vals.data_ptr())
         return MatrixCallback(self.gk, "gkomi_coo_matrix_apply_cb", ctx, self)
 
+    def values_changed(self):
+        """nothing is cached from the values: here for symmetry with Csr"""
+
+    def structure_changed(self):
+        """Call after row_idxs was written or any tensor was replaced, before the next apply: forgets whether the rows
+        are sorted, the longest row (the hint of the sorted kernels -- too small a hint gives a wrong product) and the
+        sorted kernels' workspace.  Writes to col_idxs or vals in place need no call."""
+        self.nnz = int(self.vals.numel())
+        self._sorted = None
+        self.max_row_nnz = None
+        self._ws = None
+
     def _sorted_workspace(self, nrhs):
-        """workspace of the atomic-free kernels when row_idxs is sorted (analysed once), else None"""
+        """workspace of the atomic-free kernels when row_idxs is sorted (analysed once, see structure_changed), else None"""
         gk = self.gk
         nb = gk.coo_sorted_workspace_bytes(self.nnz, nrhs)
         ws = getattr(self, "_ws", None)

@@ -880,13 +880,13 @@ struct csr_abi<int32> {
     }
     // the column-partitioned copy of the "gkomi_partitioned" strategy (gkomi_csr_colpart_*): nullptr = does not pay
     static gkomi_csr_colpart* colpart_create(std::shared_ptr<const Executor> exec, int64_t nrows, int64_t ncols, int64_t nnz, const int32* rp,
-                                             const int32* ci, const double* v, array<char>& plan)
+                                             const int32* ci, const double* v, array<char>& plan, int blocks)
     {
-        if (gkomi_csr_colpart_blocks_for(nrows, ncols, nnz) == 0) return nullptr;
-        plan = array<char>(exec, gkomi_csr_colpart_plan_bytes(nrows, nnz, 0));
+        if (blocks == 0 && gkomi_csr_colpart_blocks_for(nrows, ncols, nnz) == 0) return nullptr;
+        plan = array<char>(exec, gkomi_csr_colpart_plan_bytes(nrows, nnz, blocks));
         gkomi_csr_colpart* h = nullptr;  // (0 blocks: the analysis times two block counts and keeps the faster)
-        const int rc = gkomi_csr_colpart_create_f64_i32(nullptr, nrows, ncols, nnz, rp, ci, v, 0, plan.get_data(), plan.get_num_elems(), &h);
-        if (rc == GKOMI_ENOTSUPPORTED) {  // timed against the matrix's own kernel: the copy does not pay
+        const int rc = gkomi_csr_colpart_create_f64_i32(nullptr, nrows, ncols, nnz, rp, ci, v, blocks, plan.get_data(), plan.get_num_elems(), &h);
+        if (rc == GKOMI_ENOTSUPPORTED && blocks == 0) {  // timed against the matrix's own kernel: the copy does not pay
             plan = array<char>(exec, 0);
             return nullptr;
         }
@@ -906,7 +906,7 @@ struct csr_abi<int64> {
         return 0;
     }
     static gkomi_csr_colpart* colpart_create(std::shared_ptr<const Executor>, int64_t, int64_t, int64_t, const int64*, const int64*, const double*,
-                                             array<char>&)
+                                             array<char>&, int)
     {
         return nullptr;
     }
@@ -923,13 +923,16 @@ public:
     // kernel selection objects (include/ginkgo/core/matrix/csr.hpp:170-705)
     class strategy_type {
     public:
-        explicit strategy_type(std::string name, int code) : name_(std::move(name)), code_(code) {}
+        explicit strategy_type(std::string name, int code, int partition_blocks = 0) : name_(std::move(name)), code_(code), partition_blocks_(partition_blocks) {}
         virtual ~strategy_type() = default;
         const std::string& get_name() const { return name_; }
         int get_code() const { return code_; }
+        // gkomi_partitioned(blocks): the forced block count of the column-partitioned copy, 0 = the timed analysis decides
+        int get_partition_blocks() const { return partition_blocks_; }
     private:
         std::string name_;
         int code_;
+        int partition_blocks_;
     };
     struct classical : strategy_type { classical() : strategy_type("classical", GKOMI_CSR_VECTOR) {} };
     struct load_balance : strategy_type {
@@ -950,8 +953,15 @@ public:
     // the matrix keeps a column-partitioned COPY (gkomi_csr_colpart_*, csrc/csr_colpart.hip) when its column pattern is
     // scattered and its shape fits, and applies one-column products through it (1.3-1.6 x on uniformly random / power-law
     // patterns of ~1 M columns; tolerance parity like load_balance); otherwise the automatic kernels.  The copy holds
-    // values: it is re-gathered after get_values() (non-const) was asked for.
-    struct gkomi_partitioned : strategy_type { gkomi_partitioned() : strategy_type("gkomi_partitioned", GKOMI_CSR_AUTO) {} };
+    // values: it is re-gathered after get_values() (non-const) was asked for, and dropped and rebuilt after anything that
+    // can change the pattern (get_col_idxs(), get_row_ptrs(), sort_by_column_index(), read, set_strategy, ...).
+    // gkomi_partitioned() lets the analysis decide: it TIMES two block counts against the matrix's own kernel and may
+    // decline, so whether a copy exists (and its summation association) can differ from run to run.
+    // gkomi_partitioned(blocks), blocks in {2, 4, 8}, pins it: the copy is built with that many column blocks whatever
+    // the shape, the column statistic or a timing say (reproducible runs, tests); an unusable count throws.
+    struct gkomi_partitioned : strategy_type {
+        explicit gkomi_partitioned(int blocks = 0) : strategy_type("gkomi_partitioned", GKOMI_CSR_AUTO, blocks) {}
+    };
     struct cusparse : strategy_type { cusparse() : strategy_type("cusparse", GKOMI_CSR_AUTO) {} };
 
     static std::unique_ptr<Csr> create(std::shared_ptr<const Executor> exec, const dim<2>& size = dim<2>{}, size_type nnz = 0,
@@ -964,15 +974,19 @@ public:
     {
         return std::unique_ptr<Csr>(new Csr(std::move(exec), dim<2>{}, 0, std::move(strategy)));
     }
+    // The non-const getters tell the matrix that the array is about to change: what is cached from it (srow, the row and
+    // column statistics, the column-partitioned copy) is rebuilt or re-gathered by the NEXT apply.  A pointer obtained
+    // from them is therefore good for writing UNTIL THE NEXT APPLY; to write again after an apply, ask again.  (Writes
+    // through a pointer saved across an apply are not seen by the caches.)
     V* get_values() noexcept { colpart_dirty_ = true; return values_.get_data(); }
     const V* get_const_values() const noexcept { return values_.get_const_data(); }
-    I* get_col_idxs() noexcept { return col_idxs_.get_data(); }
+    I* get_col_idxs() noexcept { invalidate_srow(); return col_idxs_.get_data(); }  // the column statistic and the copy go with srow
     const I* get_const_col_idxs() const noexcept { return col_idxs_.get_const_data(); }
-    I* get_row_ptrs() noexcept { srow_valid_ = false; return row_ptrs_.get_data(); }  // the caller may rewrite them
+    I* get_row_ptrs() noexcept { invalidate_srow(); max_row_nnz_ = -1; return row_ptrs_.get_data(); }  // the caller may rewrite them
     const I* get_const_row_ptrs() const noexcept { return row_ptrs_.get_const_data(); }
     size_type get_num_stored_elements() const noexcept { return values_.get_num_elems(); }
     std::shared_ptr<strategy_type> get_strategy() const noexcept { return strategy_; }
-    void set_strategy(std::shared_ptr<strategy_type> s) { strategy_ = std::move(s); }
+    void set_strategy(std::shared_ptr<strategy_type> s) { strategy_ = std::move(s); invalidate_srow(); }  // the copy and the column statistic depend on it
     int64_t get_max_row_nnz() const noexcept { return max_row_nnz_; }
 
     // Csr::read(matrix_data) (core/matrix/csr.cpp:438-470)
@@ -1039,7 +1053,7 @@ public:
         exec_->copy(nnz, get_const_col_idxs(), ci.get_data());
         GKOMI_CALL(::gko::detail::convert_precision(static_cast<int64_t>(nnz), 1, get_const_values(), 1, v.get_data(), 1));
         result->adopt(size_, std::move(rp), std::move(ci), std::move(v));
-        result->set_strategy(std::make_shared<typename Csr<W, I>::strategy_type>(strategy_->get_name(), strategy_->get_code()));
+        result->set_strategy(std::make_shared<typename Csr<W, I>::strategy_type>(strategy_->get_name(), strategy_->get_code(), strategy_->get_partition_blocks()));
         result->max_row_nnz_ = max_row_nnz_;
     }
     template <typename W, typename = typename std::enable_if<!std::is_same<W, V>::value>::type>
@@ -1154,9 +1168,10 @@ public:
         }
         // the analysis of the gkomi_partitioned strategy: a scattered column pattern (the statistic above) on a shape that fits
         colpart_.reset();
-        if (strategy_->get_name() == "gkomi_partitioned" && gather_footprint_ > (int64_t{3} << 20)) {  // gathers beyond an L2
+        const int blocks = strategy_->get_partition_blocks();  // > 0: pinned, neither the statistic nor a timing is asked
+        if (strategy_->get_name() == "gkomi_partitioned" && nnz >= 2 && (blocks > 0 || gather_footprint_ > (int64_t{3} << 20))) {  // gathers beyond an L2
             colpart_.reset(detail_abi::csr_abi<I>::colpart_create(exec_, static_cast<int64_t>(size_[0]), static_cast<int64_t>(size_[1]), nnz, get_const_row_ptrs(),
-                                                                  get_const_col_idxs(), get_const_values(), colpart_plan_));
+                                                                  get_const_col_idxs(), get_const_values(), colpart_plan_, blocks));
             colpart_dirty_ = false;
         }
         srow_valid_ = true;
