@@ -30,8 +30,6 @@ namespace {
 
 constexpr int block = 256;
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 struct layout {
     size_t keys_in, keys_out, idx_in, idx_out, vals, flags, scan_ws, sort_tmp, total;
 };

@@ -62,12 +62,6 @@ workspace_layout make_layout(int64_t n, int64_t nrhs)
     return l;
 }
 
-#define GKOMI_TRY(expr)          \
-    do {                         \
-        int err_ = (expr);       \
-        if (err_) return err_;   \
-    } while (0)
-
 std::atomic<int64_t> pcg_solves{0};  // solves finished by the single-launch kernel (diagnostics, tests)
 // GKOMI_CG_PERSISTENT at start-up, gkomi_cg_persistent_enable afterwards
 std::atomic<int> pcg_mode{[] {
@@ -301,12 +295,10 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
         GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, orig_tau, nrhs, 1.0));
     }
 
-    long long iterations = -1;
-    int converged = 0;
-
     if (mode == 0) {
         uint8_t host_flags[2] = {0, 0};
         long long iter = -1;
+        int converged = 0;
         while (true) {
             GKOMI_TRY(identity_or_precond(precond, precond_ctx, s, n, nrhs, r, z));
             GKOMI_TRY(gkomi_dense_compute_dot_f64(s, n, nrhs, r, nrhs, z, nrhs, rho, red, red_bytes));
@@ -331,8 +323,9 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
                                           stop_status));
             std::swap(prev_rho, rho);
         }
-        iterations = iter;
         if (host_info != nullptr) {
+            host_info[0] = static_cast<double>(iter);
+            host_info[1] = static_cast<double>(converged);
             // final recurrence residual norms for the report
             GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, r, nrhs, tau, red, red_bytes));
             for (int64_t j = 0; j < nrhs; ++j) {
@@ -343,6 +336,7 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
             }
         }
         GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+        return precond_status(precond, precond_ctx, s);
     } else {
         cg_scalars* scal = reinterpret_cast<cg_scalars*>(ws + l.scalars);
         double* part_a = reinterpret_cast<double*>(ws + l.part_a);
@@ -367,12 +361,7 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
                                            &polled);
             if (done < 0) return -done - 1000;
             if (done == 1) {
-                if (host_info != nullptr) {
-                    host_info[0] = static_cast<double>(polled.stop_iter);
-                    host_info[1] = (polled.status & GKOMI_STATUS_CONVERGED) ? 1.0 : 0.0;
-                    host_info[2] = polled.tau;
-                    host_info[3] = polled.orig_tau;
-                }
+                fill_host_info(host_info, polled.stop_iter, polled.status, polled.tau, polled.orig_tau);
                 return precond_status(precond, precond_ctx, s);
             }
         }
@@ -410,17 +399,11 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
             GKOMI_TRY(check_launch());
         }
         const double* tau_part = precond == nullptr ? part_a : part_b;
-        long long it = 0;
-        bool done = false;
-        // The host does not look at device memory while the solve runs: K1's first thread reports the
-        // iteration it has evaluated (and the one at which the criterion fired) into pinned host memory
-        // (host_watch, internal.hpp), and the host keeps at most min(check_every, host_watch_lag)
-        // iterations ahead of what it has seen -- the queue never drains for a look.  Without that
-        // line (or if its stores never show up) the old way: a blocking look every check_every iterations.
+        // paced by pace_fused_solve (internal.hpp); launches issued after the criterion fired return at once -- unless
+        // a preconditioner's are among them
         host_watch watch;
-        // launches issued after the criterion fired return at once -- unless a preconditioner's are among them
         const long long lag = std::min<long long>(check_every, precond == nullptr ? 4 * host_watch_lag : host_watch_lag);
-        auto issue = [&](long long i) -> int {
+        auto issue = [&](long long i, bool) -> int {  // (the last iteration is enqueued whole as well)
             // (with the Jacobi apply's partials both sums have ng terms; K3's r.r partials, g of them, otherwise)
             hipLaunchKernelGGL(cg_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, p, zz,
                                part_a, ng, tau_part, jac != nullptr ? ng : g, scal, i,
@@ -438,53 +421,16 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
             if (precond != nullptr) GKOMI_TRY(precondition(false));
             return check_launch();
         };
-        while (!done) {
-            bool look = false;
-            if (watch.dev != nullptr) {
-                GKOMI_TRY(issue(it));
-                const bool last = it >= max_iters;  // the launch with it == max_iters stops for sure
-                ++it;
-                if (last) {
-                    look = true;
-                } else if (it - 1 >= lag) {
-                    if (!watch.wait(stream, it - 1 - lag)) {
-                        watch.dev = nullptr;
-                        look = true;
-                    } else {
-                        look = watch.stop_iter() >= 0;
-                    }
-                }
-            } else {
-                for (int c = 0; c < check_every; ++c, ++it) {
-                    GKOMI_TRY(issue(it));
-                    if (it >= max_iters) {
-                        ++it;
-                        break;
-                    }
-                }
-                look = true;
-            }
-            if (!look) continue;
-            GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&polled, scal, sizeof(cg_scalars),
-                                                      hipMemcpyDeviceToHost, stream)));
-            GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-            const cg_scalars* h = &polled;
-            if (h->status & GKOMI_STATUS_ID_MASK) {
-                done = true;
-                iterations = h->stop_iter;
-                converged = (h->status & GKOMI_STATUS_CONVERGED) ? 1 : 0;
-                if (host_info != nullptr) {
-                    host_info[2] = h->tau;
-                    host_info[3] = h->orig_tau;
-                }
-            }
-        }
+        auto look = [&]() -> int {
+            const int err = read_scalars(stream, &polled, scal);
+            return err ? -err : (polled.status & GKOMI_STATUS_ID_MASK) != 0;
+        };
+        bool looked = false;
+        GKOMI_TRY(pace_fused_solve(stream, &watch, max_iters, check_every, lag, issue, look, &looked));
+        if (!looked) GKOMI_TRY(read_scalars(stream, &polled, scal));
+        fill_host_info(host_info, polled.stop_iter, polled.status, polled.tau, polled.orig_tau);
+        return precond_status(precond, precond_ctx, s);
     }
-    if (host_info != nullptr) {
-        host_info[0] = static_cast<double>(iterations);
-        host_info[1] = static_cast<double>(converged);
-    }
-    return precond_status(precond, precond_ctx, s);
 }
 }  // namespace
 

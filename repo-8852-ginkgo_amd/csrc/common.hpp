@@ -24,7 +24,17 @@ inline int check_launch()
     return static_cast<int>(hipGetLastError());
 }
 
+// host code: hand a non-zero status (the library's or HIP's) up to the caller
+#define GKOMI_TRY(expr)        \
+    do {                       \
+        const int e_ = (expr); \
+        if (e_) return e_;     \
+    } while (0)
+
 inline int64_t ceildiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// workspace pieces start on 256-byte boundaries
+inline size_t align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 
 inline int grid_for(int64_t work_items, int block, int64_t cap = max_stream_blocks)
 {

@@ -41,12 +41,6 @@
 #include <climits>
 #include <cstdlib>
 
-#define GKOMI_TRY(expr)          \
-    do {                         \
-        const int err_ = (expr); \
-        if (err_) return err_;   \
-    } while (0)
-
 namespace gkomi {
 namespace {
 

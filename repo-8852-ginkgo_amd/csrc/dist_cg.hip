@@ -27,12 +27,6 @@
 namespace gkomi {
 namespace {
 
-#define GKOMI_TRY(expr)          \
-    do {                         \
-        int err_ = (expr);       \
-        if (err_) return err_;   \
-    } while (0)
-
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // out[0] = sum a[0..na) (+ sum b[0..nb)), fixed order, one workgroup; out[1]
@@ -362,53 +356,41 @@ extern "C" int gkomi_dist_cg_solve_f64(gkomi_stream_t s, const gkomi_comm* comm,
     GKOMI_TRY(reduce_rho_tau(nullptr));
 
     cg_scalars polled{};
-    long long it = 0, iterations = -1;
-    int converged = 0;
-    bool done = false;
-    while (!done) {
-        for (int c = 0; c < check_every; ++c, ++it) {
-            // K1: criterion on the reduced scalars, p = z + (rho / prev_rho) p
-            hipLaunchKernelGGL(cg_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, p, zz, red_a, 1,
-                               red_a + 1, 1, scal, it, static_cast<long long>(max_iters), reduction_factor);
-            // q = A p: halo of p on the wire while the local block runs
-            GKOMI_TRY(start_exchange(stream, comm, ctx, A, p));
-            if (n > 0) {
-                GKOMI_TRY(spmv.launch(stream, p, q, part_c, &scal->status));
-            }
-            GKOMI_TRY(nonlocal_part(stream, ctx, A, q, p, nd > 0 ? part_d : nullptr, scal));
-            // beta = p.q: local partials (+ what the non-local rows added), all-reduce
-            hipLaunchKernelGGL(dist_sum_partials_kernel, dim3(1), dim3(fblock), 0, stream, part_c, n > 0 ? nb : 0,
-                               nd > 0 ? part_d : static_cast<const double*>(nullptr), nd,
-                               static_cast<const double*>(nullptr), 0, red_b, static_cast<const cg_scalars*>(scal));
-            GKOMI_TRY(comm->allreduce_sum_f64(comm->self, s, red_b, 1));
-            // K3: x += (rho / beta) p, r -= (rho / beta) q, partials of r.r
-            hipLaunchKernelGGL(cg_fused_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r, p, q, red_b, 1,
-                               scal, it, precond == nullptr ? part_a : part_b);
-            if (precond != nullptr) {
-                GKOMI_TRY(precond(precond_ctx, s, r, z));
-                hipLaunchKernelGGL(cg_dot2_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, z,
-                                   static_cast<const cg_scalars*>(scal), part_a, static_cast<double*>(nullptr));
-            }
-            GKOMI_TRY(reduce_rho_tau(scal));
-            if (it >= max_iters) {
-                ++it;
-                break;
-            }
+    // paced by pace_fused_solve (internal.hpp) without a host_watch line: every rank looks at the same reduced scalars
+    // after the same iterations, so every rank issues the same launches and collectives
+    auto issue = [&](long long it, bool) -> int {
+        // K1: criterion on the reduced scalars, p = z + (rho / prev_rho) p
+        hipLaunchKernelGGL(cg_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, p, zz, red_a, 1,
+                           red_a + 1, 1, scal, it, static_cast<long long>(max_iters), reduction_factor);
+        // q = A p: halo of p on the wire while the local block runs
+        GKOMI_TRY(start_exchange(stream, comm, ctx, A, p));
+        if (n > 0) {
+            GKOMI_TRY(spmv.launch(stream, p, q, part_c, &scal->status));
         }
-        GKOMI_TRY(check_launch());
-        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&polled, scal, sizeof(cg_scalars), hipMemcpyDeviceToHost, stream)));
-        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-        if (polled.status & GKOMI_STATUS_ID_MASK) {
-            done = true;
-            iterations = polled.stop_iter;
-            converged = (polled.status & GKOMI_STATUS_CONVERGED) ? 1 : 0;
+        GKOMI_TRY(nonlocal_part(stream, ctx, A, q, p, nd > 0 ? part_d : nullptr, scal));
+        // beta = p.q: local partials (+ what the non-local rows added), all-reduce
+        hipLaunchKernelGGL(dist_sum_partials_kernel, dim3(1), dim3(fblock), 0, stream, part_c, n > 0 ? nb : 0,
+                           nd > 0 ? part_d : static_cast<const double*>(nullptr), nd,
+                           static_cast<const double*>(nullptr), 0, red_b, static_cast<const cg_scalars*>(scal));
+        GKOMI_TRY(comm->allreduce_sum_f64(comm->self, s, red_b, 1));
+        // K3: x += (rho / beta) p, r -= (rho / beta) q, partials of r.r
+        hipLaunchKernelGGL(cg_fused_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r, p, q, red_b, 1,
+                           scal, it, precond == nullptr ? part_a : part_b);
+        if (precond != nullptr) {
+            GKOMI_TRY(precond(precond_ctx, s, r, z));
+            hipLaunchKernelGGL(cg_dot2_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, z,
+                               static_cast<const cg_scalars*>(scal), part_a, static_cast<double*>(nullptr));
         }
-    }
-    if (host_info != nullptr) {
-        host_info[0] = static_cast<double>(iterations);
-        host_info[1] = static_cast<double>(converged);
-        host_info[2] = polled.tau;
-        host_info[3] = polled.orig_tau;
-    }
+        GKOMI_TRY(reduce_rho_tau(scal));
+        return check_launch();
+    };
+    auto look = [&]() -> int {
+        const int err = read_scalars(stream, &polled, scal);
+        return err ? -err : (polled.status & GKOMI_STATUS_ID_MASK) != 0;
+    };
+    bool looked = false;
+    GKOMI_TRY(pace_fused_solve(stream, nullptr, max_iters, check_every, 0, issue, look, &looked));
+    if (!looked) GKOMI_TRY(read_scalars(stream, &polled, scal));
+    fill_host_info(host_info, polled.stop_iter, polled.status, polled.tau, polled.orig_tau);
     return precond_status(precond, precond_ctx, s);
 }

@@ -365,7 +365,7 @@ extern "C" int gkomi_residual_norm_f32(gkomi_stream_t s, int64_t nrhs, const flo
 extern "C" size_t gkomi_cg_workspace_bytes_f32(int64_t n)
 {
     if (n < 0) return 0;
-    const size_t vec = (sizeof(float) * static_cast<size_t>(n > 0 ? n : 1) + 255) / 256 * 256;
+    const size_t vec = align256(sizeof(float) * static_cast<size_t>(n > 0 ? n : 1));
     return 4 * vec + 256 + gkomi_dense_reduction_workspace_bytes_f32(n, 1) + 256;
 }
 
@@ -377,7 +377,7 @@ extern "C" int gkomi_cg_solve_f32(gkomi_stream_t s, int64_t n, int64_t nnz, cons
     if (workspace == nullptr || workspace_bytes < gkomi_cg_workspace_bytes_f32(n)) return GKOMI_EWORKSPACE;
     hipStream_t stream = to_stream(s);
     char* ws = static_cast<char*>(workspace);
-    const size_t vec = (sizeof(float) * static_cast<size_t>(n > 0 ? n : 1) + 255) / 256 * 256;
+    const size_t vec = align256(sizeof(float) * static_cast<size_t>(n > 0 ? n : 1));
     float* r = reinterpret_cast<float*>(ws);
     float* z = reinterpret_cast<float*>(ws + vec);
     float* p = reinterpret_cast<float*>(ws + 2 * vec);
@@ -389,11 +389,6 @@ extern "C" int gkomi_cg_solve_f32(gkomi_stream_t s, int64_t n, int64_t nnz, cons
     const size_t red_bytes = gkomi_dense_reduction_workspace_bytes_f32(n, 1);
     float *prev_rho = small, *rho = small + 1, *beta = small + 2, *tau = small + 3, *orig_tau = small + 4, *one = small + 5,
           *neg = small + 6;
-#define GKOMI_TRY(expr)        \
-    do {                       \
-        const int e_ = (expr); \
-        if (e_) return e_;     \
-    } while (0)
     GKOMI_TRY(gkomi_cg_initialize_f32(s, n, 1, b, 1, r, 1, z, 1, p, 1, q, 1, prev_rho, rho, status));
     GKOMI_TRY(gkomi_dense_fill_f32(s, 1, 1, one, 1, 1.0f));
     GKOMI_TRY(gkomi_dense_fill_f32(s, 1, 1, neg, 1, -1.0f));
@@ -433,6 +428,5 @@ extern "C" int gkomi_cg_solve_f32(gkomi_stream_t s, int64_t n, int64_t nnz, cons
         host_info[2] = h[0];
         host_info[3] = h[1];
     }
-#undef GKOMI_TRY
     return GKOMI_SUCCESS;
 }

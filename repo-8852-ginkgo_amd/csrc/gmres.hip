@@ -731,12 +731,6 @@ gmres_layout make_layout(int64_t n, int64_t nrhs, int64_t d)
     return l;
 }
 
-#define GKOMI_TRY(expr)        \
-    do {                       \
-        int err_ = (expr);     \
-        if (err_) return err_; \
-    } while (0)
-
 }  // namespace
 }  // namespace gkomi
 

@@ -93,6 +93,66 @@ __device__ __forceinline__ void host_watch_publish(host_watch_line* w, long long
 // criterion fired (they return at once, but a preconditioner's do not) stay cheap
 constexpr long long host_watch_lag = 3;
 
+// The host loop of a fused single-rhs driver.  The host does not look at device memory while the solve runs: the first
+// kernel of every iteration reports the iteration it has evaluated (and the one at which the criterion fired) into the
+// host_watch line, and the host keeps at most `lag` iterations ahead of what it has seen there -- the queue never drains
+// for a look.  Launches issued after the criterion fired return at once.  Without the line (watch == nullptr, or
+// GKOMI_HOST_WATCH=0), or once its stores fail to show up, the old way: a blocking look every `check_every` iterations.
+// Either way the launch with it == max_iters stops for sure and is the last one.
+//   issue(it, last) -> int : enqueue iteration `it`, last == (it >= max_iters); what is enqueued for the last one is
+//                            the driver's choice.  Non-zero: an error, handed up.
+//   look() -> int          : blocking read of the driver's device scalars; > 0 stopped, 0 running, < 0 -(error).
+// Returns 0 once the host knows that the solve has stopped; *looked says whether it knows from look(), i.e. whether
+// the driver's host copy of the scalars is the final one (otherwise the driver still has to read them).
+// (Not for gmres.hip: its loop interleaves restarts and the persistent Arnoldi meetings -- a different protocol.)
+template <class Issue, class Look>
+int pace_fused_solve(hipStream_t stream, host_watch* watch, long long max_iters, long long check_every, long long lag,
+                     Issue&& issue, Look&& look, bool* looked)
+{
+    *looked = false;
+    for (long long it = 0;;) {
+        // one iteration while the line is followed, a batch of check_every between two looks otherwise
+        const bool watched = watch != nullptr && watch->dev != nullptr;
+        for (const long long end = it + (watched ? 1 : check_every); it < end; ++it) {
+            const bool last = it >= max_iters;
+            GKOMI_TRY(issue(it, last));
+            if (last) return 0;
+        }
+        if (watched) {
+            if (it - 1 < lag) continue;
+            if (watch->wait(stream, it - 1 - lag)) {
+                if (watch->stop_iter() >= 0) return 0;
+                continue;  // still running: no look at device memory
+            }
+            watch->dev = nullptr;  // its stores do not reach this host: the blocking look from here on
+        }
+        const int stopped = look();
+        if (stopped < 0) return -stopped;
+        if (stopped > 0) {
+            *looked = true;
+            return 0;
+        }
+    }
+}
+
+// blocking copy of a driver's device scalars, the look of pace_fused_solve and the read-out after it
+template <class Scalars>
+int read_scalars(hipStream_t stream, Scalars* host, const Scalars* dev)
+{
+    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(host, dev, sizeof(Scalars), hipMemcpyDeviceToHost, stream)));
+    return static_cast<int>(hipStreamSynchronize(stream));
+}
+
+// host_info = {iterations, converged, ||r||, baseline norm} of a single-rhs solve
+inline void fill_host_info(double* host_info, long long stop_iter, unsigned status, double tau, double orig_tau)
+{
+    if (host_info == nullptr) return;
+    host_info[0] = static_cast<double>(stop_iter);
+    host_info[1] = (status & GKOMI_STATUS_CONVERGED) ? 1.0 : 0.0;
+    host_info[2] = tau;
+    host_info[3] = orig_tau;
+}
+
 constexpr int fused_vec_block = 1024, fused_vec_max_parts = 1024;
 // Workgroups of the fused vector kernels (1024 lanes, 16 B per lane and sweep): one per 2048 rows, at most fused_vec_max_parts.
 // Two are resident per CU; a grid between one and two rounds of resident workgroups would run a second, mostly empty

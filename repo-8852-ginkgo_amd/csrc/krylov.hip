@@ -353,12 +353,6 @@ __global__ void record_stop_kernel(const uint8_t* __restrict__ flags, long long 
 bool bad_dims(int64_t n, int64_t nrhs) { return n < 0 || nrhs < 0; }
 dim3 grid_of(int64_t n, int64_t nrhs) { return dim3(static_cast<unsigned>(ceildiv(std::max<int64_t>(n * nrhs, nrhs), block))); }
 
-#define GKOMI_TRY(expr)        \
-    do {                       \
-        const int e_ = (expr); \
-        if (e_) return e_;     \
-    } while (0)
-
 // ---- drivers ------------------------------------------------------------------
 struct solver_layout {
     size_t vec[8], small, red, parts, total;
@@ -1149,54 +1143,33 @@ int bicgstab_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_app
         return check_launch();
     };
     bicgstab_scalars h{};
-    long long it = 0;
-    bool done = false;
-    // the host's view of the solve (host_watch, internal.hpp): the first kernel of every iteration reports the
-    // iteration it evaluated; the host stays a few iterations ahead and looks at device memory only once the
-    // criterion has fired -- no blocking look every check_every iterations
+    // paced by pace_fused_solve (internal.hpp); of the last iteration only step 1 is enqueued
     host_watch watch;
     const long long lag = std::min<long long>(c.check_every, precond == nullptr ? 4 * host_watch_lag : host_watch_lag);
-    while (!done) {
-        bool last = false;
-        for (int64_t k = 0; k < (watch.dev != nullptr ? 1 : c.check_every) && !done; ++k, ++it) {
-            hipLaunchKernelGGL(bicgstab_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, r, p, v,
-                               part_rho, part_tau, g, scal, it, static_cast<long long>(max_iters),
-                               reduction_factor, watch.dev);
-            if (it >= max_iters) {  // this launch stops for sure
-                ++it;
-                last = true;
-                break;
-            }
-            if (precond != nullptr) GKOMI_TRY(precond(precond_ctx, s, p, y));
-            GKOMI_TRY(spmv_dots(y, v, rr, part_beta, nullptr));
-            hipLaunchKernelGGL(bicgstab_fused_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, r, sv,
-                               v, part_beta, nb, scal, it, part_ss);
-            if (precond != nullptr) GKOMI_TRY(precond(precond_ctx, s, sv, z));
-            GKOMI_TRY(spmv_dots(z, t, sv, part_gamma, part_tt));
-            hipLaunchKernelGGL(bicgstab_fused_step3_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r,
-                               sv, t, y, z, rr, part_gamma, part_tt, nb, scal, part_rho, part_tau, part_ss, g, it,
-                               reduction_factor);
-        }
-        GKOMI_TRY(check_launch());
-        if (watch.dev != nullptr && !last) {
-            if (it - 1 < lag) continue;
-            if (watch.wait(stream, it - 1 - lag)) {
-                if (watch.stop_iter() < 0) continue;  // still running: no look at device memory
-            } else {
-                watch.dev = nullptr;  // its stores do not reach this host: the blocking look from here on
-            }
-        }
-        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&h, scal, sizeof(h), hipMemcpyDeviceToHost, stream)));
-        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-        done = h.stop_iter >= 0;
-    }
-    const unsigned char st = h.status | h.status2;
-    if (host_info != nullptr) {
-        host_info[0] = static_cast<double>(h.stop_iter);
-        host_info[1] = (st & GKOMI_STATUS_CONVERGED) ? 1.0 : 0.0;
-        host_info[2] = h.tau;
-        host_info[3] = h.orig_tau;
-    }
+    auto issue = [&](long long it, bool last) -> int {
+        hipLaunchKernelGGL(bicgstab_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, r, p, v,
+                           part_rho, part_tau, g, scal, it, static_cast<long long>(max_iters),
+                           reduction_factor, watch.dev);
+        if (last) return check_launch();
+        if (precond != nullptr) GKOMI_TRY(precond(precond_ctx, s, p, y));
+        GKOMI_TRY(spmv_dots(y, v, rr, part_beta, nullptr));
+        hipLaunchKernelGGL(bicgstab_fused_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, r, sv,
+                           v, part_beta, nb, scal, it, part_ss);
+        if (precond != nullptr) GKOMI_TRY(precond(precond_ctx, s, sv, z));
+        GKOMI_TRY(spmv_dots(z, t, sv, part_gamma, part_tt));
+        hipLaunchKernelGGL(bicgstab_fused_step3_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r,
+                           sv, t, y, z, rr, part_gamma, part_tt, nb, scal, part_rho, part_tau, part_ss, g, it,
+                           reduction_factor);
+        return check_launch();
+    };
+    auto look = [&]() -> int {
+        const int err = read_scalars(stream, &h, scal);
+        return err ? -err : h.stop_iter >= 0;
+    };
+    bool looked = false;
+    GKOMI_TRY(pace_fused_solve(stream, &watch, max_iters, c.check_every, lag, issue, look, &looked));
+    if (!looked) GKOMI_TRY(read_scalars(stream, &h, scal));
+    fill_host_info(host_info, h.stop_iter, h.status | h.status2, h.tau, h.orig_tau);
     return precond_status(precond, precond_ctx, s);
 }
 
@@ -1532,60 +1505,40 @@ int fcg_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
                        static_cast<const unsigned char*>(nullptr), part_rho, part_rhot, part_tau);
     GKOMI_TRY(check_launch());
     fcg_scalars h{};
-    long long it = 0;
-    bool done = false;
-    // the host's view of the solve (host_watch, internal.hpp): the first kernel of every iteration reports the
-    // iteration it evaluated; the host stays a few iterations ahead and looks at device memory only once the
-    // criterion has fired -- no blocking look every check_every iterations
+    // paced by pace_fused_solve (internal.hpp); of the last iteration only step 1 is enqueued
     host_watch watch;
     const long long lag = std::min<long long>(c.check_every, precond == nullptr ? 4 * host_watch_lag : host_watch_lag);
-    while (!done) {
-        bool last = false;
-        for (int64_t k = 0; k < (watch.dev != nullptr ? 1 : c.check_every) && !done; ++k, ++it) {
-            hipLaunchKernelGGL(fcg_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, p, z, part_rho,
-                               part_rhot, identity ? part_rho : part_tau, g, scal, it,
-                               static_cast<long long>(max_iters), reduction_factor, watch.dev);
-            if (it >= max_iters) {
-                ++it;
-                last = true;
-                break;
-            }
-            if (csr_epilogue) {
-                GKOMI_TRY(spmv.launch(stream, p, q, part_beta, &scal->status));
-            } else {
-                GKOMI_TRY(A.apply(s, 1, nullptr, p, nullptr, q));
-                // only p.q is wanted: the other two sums land in scratch
-                hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, p, q, p,
-                                   &scal->status, part_beta, part_beta + per_spmv, part_beta + 2 * per_spmv);
-            }
-            hipLaunchKernelGGL(fcg_fused_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r, t, p, q,
-                               part_beta, nb, scal, it, identity ? part_rho : static_cast<double*>(nullptr),
-                               identity ? part_rhot : static_cast<double*>(nullptr));
-            if (!identity) {
-                GKOMI_TRY(precond(precond_ctx, s, r, z));
-                hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, z, t,
-                                   &scal->status, part_rho, part_rhot, part_tau);
-            }
+    auto issue = [&](long long it, bool last) -> int {
+        hipLaunchKernelGGL(fcg_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, p, z, part_rho,
+                           part_rhot, identity ? part_rho : part_tau, g, scal, it,
+                           static_cast<long long>(max_iters), reduction_factor, watch.dev);
+        if (last) return check_launch();
+        if (csr_epilogue) {
+            GKOMI_TRY(spmv.launch(stream, p, q, part_beta, &scal->status));
+        } else {
+            GKOMI_TRY(A.apply(s, 1, nullptr, p, nullptr, q));
+            // only p.q is wanted: the other two sums land in scratch
+            hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, p, q, p,
+                               &scal->status, part_beta, part_beta + per_spmv, part_beta + 2 * per_spmv);
         }
-        GKOMI_TRY(check_launch());
-        if (watch.dev != nullptr && !last) {
-            if (it - 1 < lag) continue;
-            if (watch.wait(stream, it - 1 - lag)) {
-                if (watch.stop_iter() < 0) continue;  // still running: no look at device memory
-            } else {
-                watch.dev = nullptr;  // its stores do not reach this host: the blocking look from here on
-            }
+        hipLaunchKernelGGL(fcg_fused_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r, t, p, q,
+                           part_beta, nb, scal, it, identity ? part_rho : static_cast<double*>(nullptr),
+                           identity ? part_rhot : static_cast<double*>(nullptr));
+        if (!identity) {
+            GKOMI_TRY(precond(precond_ctx, s, r, z));
+            hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, z, t,
+                               &scal->status, part_rho, part_rhot, part_tau);
         }
-        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&h, scal, sizeof(h), hipMemcpyDeviceToHost, stream)));
-        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-        done = h.stop_iter >= 0;
-    }
-    if (host_info != nullptr) {
-        host_info[0] = static_cast<double>(h.stop_iter);
-        host_info[1] = (h.status & GKOMI_STATUS_CONVERGED) ? 1.0 : 0.0;
-        host_info[2] = h.tau;
-        host_info[3] = h.orig_tau;
-    }
+        return check_launch();
+    };
+    auto look = [&]() -> int {
+        const int err = read_scalars(stream, &h, scal);
+        return err ? -err : h.stop_iter >= 0;
+    };
+    bool looked = false;
+    GKOMI_TRY(pace_fused_solve(stream, &watch, max_iters, c.check_every, lag, issue, look, &looked));
+    if (!looked) GKOMI_TRY(read_scalars(stream, &h, scal));
+    fill_host_info(host_info, h.stop_iter, h.status, h.tau, h.orig_tau);
     return precond_status(precond, precond_ctx, s);
 }
 
@@ -1914,74 +1867,54 @@ int cgs_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
                        static_cast<const unsigned char*>(nullptr), part_rho, part_gamma + per_spmv, part_tau);
     GKOMI_TRY(check_launch());
     cgs_scalars h{};
-    long long it = 0;
-    bool done = false;
-    // the host's view of the solve (host_watch, internal.hpp): the first kernel of every iteration reports the
-    // iteration it evaluated; the host stays a few iterations ahead and looks at device memory only once the
-    // criterion has fired -- no blocking look every check_every iterations
+    // paced by pace_fused_solve (internal.hpp); of the last iteration only step 1 is enqueued
     host_watch watch;
     const long long lag = std::min<long long>(c.check_every, precond == nullptr ? 4 * host_watch_lag : host_watch_lag);
-    while (!done) {
-        bool last = false;
-        for (int64_t k = 0; k < (watch.dev != nullptr ? 1 : c.check_every) && !done; ++k, ++it) {
-            hipLaunchKernelGGL(cgs_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, r, u, p, q, part_rho,
-                               part_tau, g, scal, it, static_cast<long long>(max_iters), reduction_factor, watch.dev);
-            if (it >= max_iters) {
-                ++it;
-                last = true;
-                break;
-            }
-            // v_hat = A (M p), gamma = r_tld . v_hat
-            const double* mp = p;
-            if (!identity) {
-                GKOMI_TRY(precond(precond_ctx, s, p, t));
-                mp = t;
-            }
-            if (csr_epilogue) {
-                GKOMI_TRY(spmv.launch(stream, mp, v_hat, part_gamma, &scal->status, r_tld));
-            } else {
-                GKOMI_TRY(A.apply(s, 1, nullptr, mp, nullptr, v_hat));
-                hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r_tld, v_hat,
-                                   r_tld, &scal->status, part_gamma, part_gamma + per_spmv,
-                                   part_gamma + 2 * per_spmv);
-            }
-            hipLaunchKernelGGL(cgs_fused_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, u, v_hat, q, t,
-                               part_gamma, nb, scal, it);
-            // Identity: u_hat = t, and A t goes to the u_hat buffer; otherwise
-            // u_hat = M t and A u_hat overwrites t, as in the reference
-            const double *xdir, *rdir;
-            if (identity) {
-                GKOMI_TRY(A.apply(s, 1, nullptr, t, nullptr, u_hat));
-                xdir = t;
-                rdir = u_hat;
-            } else {
-                GKOMI_TRY(precond(precond_ctx, s, t, u_hat));
-                GKOMI_TRY(A.apply(s, 1, nullptr, u_hat, nullptr, t));
-                xdir = u_hat;
-                rdir = t;
-            }
-            hipLaunchKernelGGL(cgs_fused_step3_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r, xdir, rdir,
-                               r_tld, scal, part_rho, part_tau);
+    auto issue = [&](long long it, bool last) -> int {
+        hipLaunchKernelGGL(cgs_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, r, u, p, q, part_rho,
+                           part_tau, g, scal, it, static_cast<long long>(max_iters), reduction_factor, watch.dev);
+        if (last) return check_launch();
+        // v_hat = A (M p), gamma = r_tld . v_hat
+        const double* mp = p;
+        if (!identity) {
+            GKOMI_TRY(precond(precond_ctx, s, p, t));
+            mp = t;
         }
-        GKOMI_TRY(check_launch());
-        if (watch.dev != nullptr && !last) {
-            if (it - 1 < lag) continue;
-            if (watch.wait(stream, it - 1 - lag)) {
-                if (watch.stop_iter() < 0) continue;  // still running: no look at device memory
-            } else {
-                watch.dev = nullptr;  // its stores do not reach this host: the blocking look from here on
-            }
+        if (csr_epilogue) {
+            GKOMI_TRY(spmv.launch(stream, mp, v_hat, part_gamma, &scal->status, r_tld));
+        } else {
+            GKOMI_TRY(A.apply(s, 1, nullptr, mp, nullptr, v_hat));
+            hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r_tld, v_hat,
+                               r_tld, &scal->status, part_gamma, part_gamma + per_spmv,
+                               part_gamma + 2 * per_spmv);
         }
-        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&h, scal, sizeof(h), hipMemcpyDeviceToHost, stream)));
-        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-        done = h.stop_iter >= 0;
-    }
-    if (host_info != nullptr) {
-        host_info[0] = static_cast<double>(h.stop_iter);
-        host_info[1] = (h.status & GKOMI_STATUS_CONVERGED) ? 1.0 : 0.0;
-        host_info[2] = h.tau;
-        host_info[3] = h.orig_tau;
-    }
+        hipLaunchKernelGGL(cgs_fused_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, u, v_hat, q, t,
+                           part_gamma, nb, scal, it);
+        // Identity: u_hat = t, and A t goes to the u_hat buffer; otherwise
+        // u_hat = M t and A u_hat overwrites t, as in the reference
+        const double *xdir, *rdir;
+        if (identity) {
+            GKOMI_TRY(A.apply(s, 1, nullptr, t, nullptr, u_hat));
+            xdir = t;
+            rdir = u_hat;
+        } else {
+            GKOMI_TRY(precond(precond_ctx, s, t, u_hat));
+            GKOMI_TRY(A.apply(s, 1, nullptr, u_hat, nullptr, t));
+            xdir = u_hat;
+            rdir = t;
+        }
+        hipLaunchKernelGGL(cgs_fused_step3_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r, xdir, rdir,
+                           r_tld, scal, part_rho, part_tau);
+        return check_launch();
+    };
+    auto look = [&]() -> int {
+        const int err = read_scalars(stream, &h, scal);
+        return err ? -err : h.stop_iter >= 0;
+    };
+    bool looked = false;
+    GKOMI_TRY(pace_fused_solve(stream, &watch, max_iters, c.check_every, lag, issue, look, &looked));
+    if (!looked) GKOMI_TRY(read_scalars(stream, &h, scal));
+    fill_host_info(host_info, h.stop_iter, h.status, h.tau, h.orig_tau);
     return precond_status(precond, precond_ctx, s);
 }
 

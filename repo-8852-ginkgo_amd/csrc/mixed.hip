@@ -23,8 +23,6 @@
 namespace gkomi {
 namespace {
 
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 // ---- convert_precision --------------------------------------------------------------------------------------------
 constexpr int cblock = 256;
 
@@ -291,12 +289,6 @@ cgf_layout make_cgf_layout(int64_t n)
     return l;
 }
 
-#define GKOMI_TRY(expr)        \
-    do {                       \
-        const int e_ = (expr); \
-        if (e_) return e_;     \
-    } while (0)
-
 // The whole inner solve issued on `s`; returns once the host knows that it has stopped (the host_watch line, or a look
 // every 16 iterations when the line is not available).  The final state stays in the device scalars *scal_out: the caller
 // looks at them when it needs them.
@@ -328,7 +320,7 @@ int cgf_run(gkomi_stream_t s, int64_t n, int64_t nnz, const int32_t* row_ptrs, c
                        baseline == 2 ? 1 : 0);
     GKOMI_TRY(check_launch());
     host_watch watch;
-    auto issue = [&](long long i) -> int {
+    auto issue = [&](long long i, bool) -> int {
         hipLaunchKernelGGL(cgf_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, p, r, part_rr, g, scal, i,
                            static_cast<long long>(max_iters), reduction, watch.dev);
         hipLaunchKernelGGL(cgf_spmv_dot_kernel, dim3(gs), dim3(sblock), 0, stream, static_cast<int>(n), row_ptrs, col_idxs, vals,
@@ -336,37 +328,13 @@ int cgf_run(gkomi_stream_t s, int64_t n, int64_t nnz, const int32_t* row_ptrs, c
         hipLaunchKernelGGL(cgf_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r, p, q, part_pq, gs, scal, i, part_rr);
         return check_launch();
     };
-    const long long lag = 4 * host_watch_lag;
-    constexpr int check_every = 16;
-    long long it = 0;
-    while (true) {
-        bool look = false;
-        if (watch.dev != nullptr) {
-            GKOMI_TRY(issue(it));
-            if (it >= max_iters) return GKOMI_SUCCESS;  // the launch with it == max_iters stops for sure
-            ++it;
-            if (it - 1 >= lag) {
-                if (!watch.wait(stream, it - 1 - lag)) {
-                    watch.dev = nullptr;
-                    look = true;
-                } else if (watch.stop_iter() >= 0) {
-                    return GKOMI_SUCCESS;
-                }
-            }
-        } else {
-            for (int c = 0; c < check_every; ++c) {
-                GKOMI_TRY(issue(it));
-                if (it >= max_iters) return GKOMI_SUCCESS;
-                ++it;
-            }
-            look = true;
-        }
-        if (!look) continue;
+    auto look = [&]() -> int {  // (only without the line: the status byte alone)
         uint8_t st = 0;
-        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&st, &scal->status, 1, hipMemcpyDeviceToHost, stream)));
-        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-        if (st & GKOMI_STATUS_ID_MASK) return GKOMI_SUCCESS;
-    }
+        const int err = read_scalars(stream, &st, &scal->status);
+        return err ? -err : (st & GKOMI_STATUS_ID_MASK) != 0;
+    };
+    bool looked = false;  // (not needed: the callers read the scalars themselves)
+    return pace_fused_solve(stream, &watch, max_iters, /*check_every=*/16, /*lag=*/4 * host_watch_lag, issue, look, &looked);
 }
 
 int cgf_check_args(int64_t n, int64_t nnz, int64_t max_iters, int baseline, const float* b, const float* x)
@@ -518,14 +486,8 @@ extern "C" int gkomi_cg_solve_fused_f32_i32(gkomi_stream_t s, int64_t n, int64_t
                       &scal));
     cg_scalars h{};
     hipStream_t stream = to_stream(s);
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&h, scal, sizeof(cg_scalars), hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-    if (host_info != nullptr) {
-        host_info[0] = static_cast<double>(h.stop_iter);
-        host_info[1] = (h.status & GKOMI_STATUS_CONVERGED) ? 1.0 : 0.0;
-        host_info[2] = h.tau;
-        host_info[3] = h.orig_tau;
-    }
+    GKOMI_TRY(read_scalars(stream, &h, scal));
+    fill_host_info(host_info, h.stop_iter, h.status, h.tau, h.orig_tau);
     return GKOMI_SUCCESS;
 }
 
@@ -589,14 +551,10 @@ extern "C" int gkomi_ir_mixed_solve_f64_i32(gkomi_stream_t s, int64_t n, int64_t
         GKOMI_TRY(check_launch());
         GKOMI_TRY(residual());
     }
+    fill_host_info(host_info, h.stop_iter, h.status, h.tau, h.orig_tau);
     if (host_info != nullptr) {
-        host_info[0] = static_cast<double>(h.stop_iter);
-        host_info[1] = (h.status & GKOMI_STATUS_CONVERGED) ? 1.0 : 0.0;
-        host_info[2] = h.tau;
-        host_info[3] = h.orig_tau;
         host_info[4] = static_cast<double>(h.inner_iters);
         host_info[5] = static_cast<double>(h.inner_capped);
     }
     return GKOMI_SUCCESS;
 }
-#undef GKOMI_TRY
