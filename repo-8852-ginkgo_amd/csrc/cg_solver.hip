@@ -427,9 +427,7 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
         };
         bool looked = false;
         GKOMI_TRY(pace_fused_solve(stream, &watch, max_iters, check_every, lag, issue, look, &looked));
-        if (!looked) GKOMI_TRY(read_scalars(stream, &polled, scal));
-        fill_host_info(host_info, polled.stop_iter, polled.status, polled.tau, polled.orig_tau);
-        return precond_status(precond, precond_ctx, s);
+        return finish_fused(s, looked, &polled, scal, host_info, precond, precond_ctx);
     }
 }
 }  // namespace

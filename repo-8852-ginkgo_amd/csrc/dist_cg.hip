@@ -390,7 +390,5 @@ extern "C" int gkomi_dist_cg_solve_f64(gkomi_stream_t s, const gkomi_comm* comm,
     };
     bool looked = false;
     GKOMI_TRY(pace_fused_solve(stream, nullptr, max_iters, check_every, 0, issue, look, &looked));
-    if (!looked) GKOMI_TRY(read_scalars(stream, &polled, scal));
-    fill_host_info(host_info, polled.stop_iter, polled.status, polled.tau, polled.orig_tau);
-    return precond_status(precond, precond_ctx, s);
+    return finish_fused(s, looked, &polled, scal, host_info, precond, precond_ctx);
 }

@@ -227,10 +227,7 @@ __device__ double arnoldi_sum_partials(const double* __restrict__ partials, int 
     return total;
 }
 
-__device__ __forceinline__ double2 ld2(const double* p, int64_t i)
-{
-    return reinterpret_cast<const double2*>(p)[i];
-}
+// (ld2: fused_krylov.hpp, by way of cg_persistent.hpp)
 
 // next -= h_prev * prev (if prev), partial_out[block] = sum next * (with ? with : next).
 // 16 B per lane; the first sweep's loads are issued before the partials are

@@ -185,6 +185,17 @@ int trs_bricks_solve_chained(gkomi_stream_t s, gkomi_trs_bricks* h, void* plan, 
 // GKOMI_ETRS_OVERRUN when one of the ILU's triangular solves gave up (precond.hip)
 int precond_status(gkomi_apply_fn precond, void* ctx, gkomi_stream_t s);
 
+// what a fused driver does once pace_fused_solve has returned: the final scalars (unless its last look has them
+// already), the report, the preconditioner's health.  Scalars: fused_scalars or a struct that starts with it.
+template <class Scalars>
+int finish_fused(gkomi_stream_t s, bool looked, Scalars* host, const Scalars* dev, double* host_info,
+                 gkomi_apply_fn precond, void* precond_ctx)
+{
+    if (!looked) GKOMI_TRY(read_scalars(to_stream(s), host, dev));
+    fill_host_info(host_info, host->stop_iter, host->final_status(), host->tau, host->orig_tau);
+    return precond_status(precond, precond_ctx, s);
+}
+
 // The system matrix of a solver driver: CSR arrays (op == nullptr) or any
 // format behind a gkomi_matrix_apply_fn (Ell, Sellp, Coo, Hybrid, a user LinOp).
 struct sysmat {

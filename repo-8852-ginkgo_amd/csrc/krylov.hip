@@ -16,6 +16,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "fused_krylov.hpp"
 #include "internal.hpp"
 
 namespace gkomi {
@@ -519,6 +520,51 @@ int make_common(driver_common& c, gkomi_stream_t s, int64_t n, int64_t nrhs, con
     return 0;
 }
 
+// what the three fused single-rhs drivers share on the host: the device scalars in front of the partial arrays
+// (solver_layout::parts), the grid of the vector kernels, how A leaves its dot partials, the pacing and the report
+template <class Scalars>
+struct fused_driver {
+    static_assert(sizeof(Scalars) <= 32 * sizeof(double), "the scalars have 32 doubles in front of the partials");
+    const driver_common& c;
+    Scalars* scal;
+    int g;                // workgroups of the vector kernels = partials they leave, 16 B per lane (internal.hpp)
+    spmv_dot_plan spmv;   // the dots in the SpMV's epilogue for CSR / ELL / SELL-P (internal.hpp)
+    int nb;               // partials of an apply of A: the epilogue's, or those of the partials kernel after it
+    size_t per_spmv;
+    host_watch watch;
+    fused_driver(const driver_common& c_, char* ws, const solver_layout& l)
+        : c(c_), scal(reinterpret_cast<Scalars*>(ws + l.parts)), g(fused_vec_grid(c_.n)), spmv(c_.A),
+          nb(spmv.fused() ? spmv.num_partials : g), per_spmv(spmv_dot_partials_room(c_.n)),
+          next(reinterpret_cast<double*>(ws + l.parts) + 32)
+    {}
+    // the arrays are handed out in order; the layout has room for three of each kind
+    double* vec_partials() { return take(fused_vec_max_parts); }
+    double* spmv_partials() { return take(per_spmv); }
+    // issue(it, last): pace_fused_solve's (internal.hpp); of the last iteration the drivers enqueue only step 1
+    template <class Issue>
+    int solve(Issue&& issue, double* host_info)
+    {
+        Scalars h{};
+        const long long lag = std::min<long long>(c.check_every, c.precond == nullptr ? 4 * host_watch_lag : host_watch_lag);
+        auto look = [&]() -> int {
+            const int err = read_scalars(c.stream, &h, scal);
+            return err ? -err : h.stop_iter >= 0;
+        };
+        bool looked = false;
+        GKOMI_TRY(pace_fused_solve(c.stream, &watch, c.max_iters, c.check_every, lag, issue, look, &looked));
+        return finish_fused(c.s, looked, &h, scal, host_info, c.precond, c.precond_ctx);
+    }
+
+private:
+    double* next;
+    double* take(size_t count)
+    {
+        double* at = next;
+        next += count;
+        return at;
+    }
+};
+
 }  // namespace
 }  // namespace gkomi
 
@@ -801,35 +847,15 @@ int bicgstab_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat&
 // scalars bit for bit; workgroup 0 stores them for the kernels that follow.
 // Once a criterion fires the remaining launches return at once, so x and the
 // iteration count are those of the stopping iteration whatever `check_every`.
-constexpr int fblock = 1024;
-constexpr int fused_max_parts = 1024;
-
-struct bicgstab_scalars {
-    double rho[2];  // rho of iteration `it` lives in rho[it & 1]
-    double alpha, omega, tau, orig_tau;
-    long long stop_iter;
+// The sweep, the criterion and the partial sums are those of fused_krylov.hpp; these kernels report id 1 for both criteria.
+struct bicgstab_scalars : fused_scalars {
+    double alpha, omega;
     long long stop2_iter;   // iteration whose half step converged (written by KE only), -1 before
     int phase;
-    unsigned char status;   // written by KA only
-    unsigned char status2;  // written by KE only (the half step's criterion)
-    unsigned char pad[2];
+    unsigned char status2;  // written by KE only (the half step's criterion); `status` by KA only
+    unsigned char pad2[3];
+    unsigned final_status() const { return status | status2; }
 };
-
-__device__ __forceinline__ double sum_partials_f(const double* __restrict__ part, int nparts,
-                                                 double* smem)
-{
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += fblock) acc += part[i];
-    acc = wave_reduce_sum(acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) smem[wave] = acc;
-    __syncthreads();
-    double total = 0.0;
-#pragma unroll
-    for (int w = 0; w < fblock / wave_size; ++w) total += smem[w];
-    return total;  // identical in every thread of every workgroup
-}
 
 __device__ __forceinline__ bool fused_stopped(const bicgstab_scalars* scal)
 {
@@ -838,20 +864,16 @@ __device__ __forceinline__ bool fused_stopped(const bicgstab_scalars* scal)
 
 __global__ void bicgstab_fused_init_kernel(bicgstab_scalars* scal, const double* orig_tau)
 {
-    scal->rho[0] = 1.0;
-    scal->rho[1] = 1.0;  // prev_rho = rho = alpha = omega = 1 (bicgstab::initialize)
+    init_fused_scalars(scal, 1.0, orig_tau[0]);  // prev_rho = rho = alpha = omega = 1 (bicgstab::initialize)
     scal->alpha = 1.0;
     scal->omega = 1.0;
-    scal->tau = 0.0;
-    scal->orig_tau = orig_tau[0];
-    scal->stop_iter = -1;
     scal->stop2_iter = -1;
     scal->phase = 0;
-    scal->status = 0;
     scal->status2 = 0;
 }
 
-// pa[block] = sum a*b, pb[block] = sum c*c over the workgroup's share (pb optional)
+// pa[block] = sum a*b, pb[block] = sum c*c over the workgroup's share (pb optional).
+// (8 B per lane, one accumulator per sum: not cg_dot2_partials_kernel of cg_fused.hpp, whose sums associate differently.)
 __global__ __launch_bounds__(fblock) void fused_dot2_partials_kernel(
     int64_t n, const double* __restrict__ a, const double* __restrict__ b,
     const double* __restrict__ c, const bicgstab_scalars* scal, double* __restrict__ pa,
@@ -868,35 +890,9 @@ __global__ __launch_bounds__(fblock) void fused_dot2_partials_kernel(
             w += cv * cv;
         }
     }
-    const double tu = block_reduce_sum<fblock>(u, smem);
-    __syncthreads();
-    const double tw = block_reduce_sum<fblock>(w, smem);
-    if (threadIdx.x == 0) {
-        pa[blockIdx.x] = tu;
-        if (pb != nullptr) pb[blockIdx.x] = tw;
-    }
-}
-
-// The vector kernels move 16 B per lane and issue the loads of their first
-// sweep (which do not depend on the scalars) before re-adding the partials, so
-// the reduction's latency hides behind them (as in cg_solver.hip).
-struct pair_sweep {
-    int64_t n2, step, i0;
-    __device__ pair_sweep(int64_t n)
-        : n2(n / 2), step(static_cast<int64_t>(gridDim.x) * fblock),
-          i0(blockIdx.x * static_cast<int64_t>(fblock) + threadIdx.x)
-    {}
-    __device__ bool first() const { return i0 < n2; }
-    __device__ bool tail(int64_t n) const { return (n & 1) && blockIdx.x == 0 && threadIdx.x == 0; }
-};
-
-__device__ __forceinline__ double2 ld2(const double* p, int64_t i)
-{
-    return reinterpret_cast<const double2*>(p)[i];
-}
-__device__ __forceinline__ void st2(double* p, int64_t i, double2 v)
-{
-    reinterpret_cast<double2*>(p)[i] = v;
+    const double sum[] = {u, w};
+    double* const part[] = {pa, pb};
+    store_block_sums(false, sum, part, smem);
 }
 
 // KA
@@ -906,48 +902,25 @@ __global__ __launch_bounds__(fblock) void bicgstab_fused_step1_kernel(
     bicgstab_scalars* scal, long long it, long long max_iters, double goal, host_watch_line* watch = nullptr)
 {
     __shared__ double smem[fblock / wave_size];
-    if (fused_stopped(scal)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) host_watch_publish(watch, it, scal->stop_iter);  // internal.hpp
-        return;
-    }
+    if (fused_stopped_before(fused_stopped(scal), scal, watch, it)) return;
     const pair_sweep sw(n);
-    double2 r0 = make_double2(0.0, 0.0), p0 = r0, v0 = r0;
-    if (sw.first()) {
-        r0 = ld2(r, sw.i0);
-        p0 = ld2(p, sw.i0);
-        v0 = ld2(v, sw.i0);
-    }
-    const double rho = sum_partials_f(rho_part, nparts, smem);
-    const double tau = sqrt(sum_partials_f(tau_part, nparts, smem));
-    uint8_t st = 0;
-    if (it >= max_iters) {
-        st = 1 | GKOMI_STATUS_FINALIZED;
-    } else if (tau < goal * scal->orig_tau) {
-        st = GKOMI_STATUS_CONVERGED | 1 | GKOMI_STATUS_FINALIZED;
-    }
+    const double* const in[] = {r, p, v};
+    double* const out[] = {p};
+    const auto first = sw.prefetch(in);
+    const double rho = sum_partials(rho_part, nparts, smem);
+    const double tau = sqrt(sum_partials(tau_part, nparts, smem));
     const double prev = scal->rho[(it + 1) & 1];
     const double alpha = scal->alpha, omega = scal->omega;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        scal->rho[it & 1] = rho;
-        scal->tau = tau;  // also at the iteration limit: the norm of the residual that is returned
-        if (st) {
-            scal->stop_iter = it;
-            scal->phase = 1;
-            scal->status = st;
-        }
+    if (fused_criterion(scal, watch, it, max_iters, rho, tau, goal, 1, 1, [&](uint8_t st) {
+            if (st) scal->phase = 1;
+        })) {
+        return;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) host_watch_publish(watch, it, st ? it : -1ll);
-    if (st) return;
     // bicgstab::step_1 (reference/solver/bicgstab_kernels.cpp)
     const bool update = prev * omega != 0.0;
     const double tmp = update ? rho / prev * alpha / omega : 0.0;
-    auto step1 = [&](double rv, double pv, double vv) { return update ? rv + tmp * (pv - omega * vv) : rv; };
-    if (sw.first()) st2(p, sw.i0, make_double2(step1(r0.x, p0.x, v0.x), step1(r0.y, p0.y, v0.y)));
-    for (int64_t i = sw.i0 + sw.step; i < sw.n2; i += sw.step) {
-        const double2 rv = ld2(r, i), pv = ld2(p, i), vv = ld2(v, i);
-        st2(p, i, make_double2(step1(rv.x, pv.x, vv.x), step1(rv.y, pv.y, vv.y)));
-    }
-    if (sw.tail(n)) p[n - 1] = step1(r[n - 1], p[n - 1], v[n - 1]);
+    sw.run(first, in, out, true,
+           [&](int, const double* e, double* o) { o[0] = update ? e[0] + tmp * (e[1] - omega * e[2]) : e[0]; });
 }
 
 // KC
@@ -959,40 +932,23 @@ __global__ __launch_bounds__(fblock) void bicgstab_fused_step2_kernel(
     __shared__ double smem[fblock / wave_size];
     if (fused_stopped(scal)) return;
     const pair_sweep sw(n);
-    double2 r0 = make_double2(0.0, 0.0), v0 = r0;
-    if (sw.first()) {
-        r0 = ld2(r, sw.i0);
-        v0 = ld2(v, sw.i0);
-    }
-    const double beta = sum_partials_f(beta_part, nparts, smem);
+    const double* const in[] = {r, v};
+    double* const out[] = {sv};
+    const auto first = sw.prefetch(in);
+    const double beta = sum_partials(beta_part, nparts, smem);
     const double rho = scal->rho[it & 1];
     const bool update = beta != 0.0;
     const double alpha = update ? rho / beta : 0.0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) scal->alpha = alpha;
-    // bicgstab::step_2
-    auto step2 = [&](double rv, double vv) { return update ? rv - alpha * vv : rv; };
-    double a0 = 0.0, a1 = 0.0;
-    if (sw.first()) {
-        const double2 o = make_double2(step2(r0.x, v0.x), step2(r0.y, v0.y));
-        st2(sv, sw.i0, o);
-        a0 += o.x * o.x;
-        a1 += o.y * o.y;
-    }
-    for (int64_t i = sw.i0 + sw.step; i < sw.n2; i += sw.step) {
-        const double2 rv = ld2(r, i), vv = ld2(v, i);
-        const double2 o = make_double2(step2(rv.x, vv.x), step2(rv.y, vv.y));
-        st2(sv, i, o);
-        a0 += o.x * o.x;
-        a1 += o.y * o.y;
-    }
-    if (sw.tail(n)) {
-        const double o = step2(r[n - 1], v[n - 1]);
-        sv[n - 1] = o;
-        a0 += o * o;
-    }
-    __syncthreads();
-    const double total = block_reduce_sum<fblock>(a0 + a1, smem);
-    if (threadIdx.x == 0) ss_part[blockIdx.x] = total;
+    if (fused_leader()) scal->alpha = alpha;
+    // bicgstab::step_2; s.s of .x and of .y apart, the tail with .x
+    double acc[2] = {0.0, 0.0};
+    sw.run(first, in, out, true, [&](int half, const double* e, double* o) {
+        o[0] = update ? e[0] - alpha * e[1] : e[0];
+        acc[half] += o[0] * o[0];
+    });
+    const double sum[] = {acc[0] + acc[1]};
+    double* const part[] = {ss_part};
+    store_block_sums(true, sum, part, smem);
 }
 
 // KE
@@ -1012,80 +968,42 @@ __global__ __launch_bounds__(fblock) void bicgstab_fused_step3_kernel(
     const long long stopped_at = scal->stop2_iter;
     if (stopped_at >= 0 && stopped_at != it) return;
     const pair_sweep sw(n);
-    double2 x0 = make_double2(0.0, 0.0), y0 = x0, z0 = x0, s0 = x0, t0 = x0, q0 = x0;
-    if (sw.first()) {
-        x0 = ld2(x, sw.i0);
-        y0 = ld2(y, sw.i0);
-        z0 = ld2(z, sw.i0);
-        s0 = ld2(sv, sw.i0);
-        t0 = ld2(t, sw.i0);
-        q0 = ld2(rr, sw.i0);
-    }
-    const double tau_s = sqrt(sum_partials_f(ss_part, nss, smem));
+    const double* const in[] = {x, y, z, sv, t, rr};
+    const auto first = sw.prefetch(in);
+    const double tau_s = sqrt(sum_partials(ss_part, nss, smem));
     if (tau_s < goal * scal->orig_tau) {
         // bicgstab::finalize (core/solver/bicgstab.cpp:196-203): s has converged, x += alpha y and nothing else
         // (the preconditioner apply and the SpMV between step 2 and here ran on that s for nothing, once per solve)
         const double alpha = scal->alpha;
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (fused_leader()) {
             scal->tau = tau_s;
             scal->stop_iter = it;
             scal->stop2_iter = it;
             scal->phase = 2;
             scal->status2 = GKOMI_STATUS_CONVERGED | 1 | GKOMI_STATUS_FINALIZED;
         }
-        if (sw.first()) st2(x, sw.i0, make_double2(x0.x + alpha * y0.x, x0.y + alpha * y0.y));
-        for (int64_t i = sw.i0 + sw.step; i < sw.n2; i += sw.step) {
-            const double2 xv = ld2(x, i), yv = ld2(y, i);
-            st2(x, i, make_double2(xv.x + alpha * yv.x, xv.y + alpha * yv.y));
-        }
-        if (sw.tail(n)) x[n - 1] += alpha * y[n - 1];
+        const double* const fin[] = {x, y};
+        double* const fout[] = {x};
+        const pair_values<2> ffirst{{first.v[0], first.v[1]}};
+        sw.run(ffirst, fin, fout, true, [&](int, const double* e, double* o) { o[0] = e[0] + alpha * e[1]; });
         return;
     }
-    const double gamma = sum_partials_f(gamma_part, nparts, smem);
-    const double beta = sum_partials_f(tt_part, nparts, smem);
+    const double gamma = sum_partials(gamma_part, nparts, smem);
+    const double beta = sum_partials(tt_part, nparts, smem);
     const double omega = beta != 0.0 ? gamma / beta : 0.0;
     const double alpha = scal->alpha;
-    if (blockIdx.x == 0 && threadIdx.x == 0) scal->omega = omega;
-    // bicgstab::step_3
-    double a0 = 0.0, a1 = 0.0;
-    auto step3 = [&](double xv, double yv, double zv, double svv, double tv, double qv, double* xo,
-                     double* ro) {
-        *xo = xv + (alpha * yv + omega * zv);
-        *ro = svv - omega * tv;
-        a0 += qv * *ro;
-        a1 += *ro * *ro;
-    };
-    if (sw.first()) {
-        double2 xo, ro;
-        step3(x0.x, y0.x, z0.x, s0.x, t0.x, q0.x, &xo.x, &ro.x);
-        step3(x0.y, y0.y, z0.y, s0.y, t0.y, q0.y, &xo.y, &ro.y);
-        st2(x, sw.i0, xo);
-        st2(r, sw.i0, ro);
-    }
-    for (int64_t i = sw.i0 + sw.step; i < sw.n2; i += sw.step) {
-        const double2 xv = ld2(x, i), yv = ld2(y, i), zv = ld2(z, i), svv = ld2(sv, i), tv = ld2(t, i),
-                      qv = ld2(rr, i);
-        double2 xo, ro;
-        step3(xv.x, yv.x, zv.x, svv.x, tv.x, qv.x, &xo.x, &ro.x);
-        step3(xv.y, yv.y, zv.y, svv.y, tv.y, qv.y, &xo.y, &ro.y);
-        st2(x, i, xo);
-        st2(r, i, ro);
-    }
-    if (sw.tail(n)) {
-        const int64_t i = n - 1;
-        double xo, ro;
-        step3(x[i], y[i], z[i], sv[i], t[i], rr[i], &xo, &ro);
-        x[i] = xo;
-        r[i] = ro;
-    }
-    __syncthreads();
-    const double t0s = block_reduce_sum<fblock>(a0, smem);
-    __syncthreads();
-    const double t1s = block_reduce_sum<fblock>(a1, smem);
-    if (threadIdx.x == 0) {
-        rho_part[blockIdx.x] = t0s;
-        tau_part[blockIdx.x] = t1s;
-    }
+    if (fused_leader()) scal->omega = omega;
+    // bicgstab::step_3; rr.r and r.r, both halves and the tail into the same two accumulators
+    double acc[2] = {0.0, 0.0};
+    double* const out[] = {x, r};
+    sw.run(first, in, out, true, [&](int, const double* e, double* o) {
+        o[0] = e[0] + (alpha * e[1] + omega * e[2]);
+        o[1] = e[3] - omega * e[4];
+        acc[0] += e[5] * o[1];
+        acc[1] += o[1] * o[1];
+    });
+    double* const part[] = {rho_part, tau_part};
+    store_block_sums(true, acc, part, smem);
 }
 
 int bicgstab_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn precond,
@@ -1110,20 +1028,13 @@ int bicgstab_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_app
     GKOMI_TRY(c.start(b, x, r, baseline));
     GKOMI_TRY(gkomi_dense_copy_f64(s, n, 1, r, 1, rr, 1));
     hipStream_t stream = c.stream;
-    double* parts = reinterpret_cast<double*>(ws + l.parts);
-    bicgstab_scalars* scal = reinterpret_cast<bicgstab_scalars*>(parts);
-    double* part_rho = parts + 32;
-    double* part_tau = part_rho + fused_max_parts;
-    double* part_ss = part_tau + fused_max_parts;
-    const size_t per_spmv = spmv_dot_partials_room(n);
-    double* part_beta = part_ss + fused_max_parts;
-    double* part_gamma = part_beta + per_spmv;
-    double* part_tt = part_gamma + per_spmv;
-    const int g = fused_vec_grid(n);  // 16 B per lane (internal.hpp)
-    // the dots in the SpMV's epilogue for CSR / ELL / SELL-P (internal.hpp)
-    const spmv_dot_plan spmv(A);
+    fused_driver<bicgstab_scalars> f(c, ws, l);
+    bicgstab_scalars* scal = f.scal;
+    double *part_rho = f.vec_partials(), *part_tau = f.vec_partials(), *part_ss = f.vec_partials();
+    double *part_beta = f.spmv_partials(), *part_gamma = f.spmv_partials(), *part_tt = f.spmv_partials();
+    const int g = f.g, nb = f.nb;
+    const spmv_dot_plan& spmv = f.spmv;
     const bool csr_epilogue = spmv.fused();
-    const int nb = csr_epilogue ? spmv.num_partials : g;
     if (precond == nullptr) {  // Identity: y = p, z = s without the copies
         y = p;
         z = sv;
@@ -1142,10 +1053,7 @@ int bicgstab_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_app
                            out, static_cast<const bicgstab_scalars*>(scal), pw, pq);
         return check_launch();
     };
-    bicgstab_scalars h{};
-    // paced by pace_fused_solve (internal.hpp); of the last iteration only step 1 is enqueued
-    host_watch watch;
-    const long long lag = std::min<long long>(c.check_every, precond == nullptr ? 4 * host_watch_lag : host_watch_lag);
+    host_watch& watch = f.watch;
     auto issue = [&](long long it, bool last) -> int {
         hipLaunchKernelGGL(bicgstab_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, r, p, v,
                            part_rho, part_tau, g, scal, it, static_cast<long long>(max_iters),
@@ -1162,15 +1070,7 @@ int bicgstab_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_app
                            reduction_factor);
         return check_launch();
     };
-    auto look = [&]() -> int {
-        const int err = read_scalars(stream, &h, scal);
-        return err ? -err : h.stop_iter >= 0;
-    };
-    bool looked = false;
-    GKOMI_TRY(pace_fused_solve(stream, &watch, max_iters, c.check_every, lag, issue, look, &looked));
-    if (!looked) GKOMI_TRY(read_scalars(stream, &h, scal));
-    fill_host_info(host_info, h.stop_iter, h.status | h.status2, h.tau, h.orig_tau);
-    return precond_status(precond, precond_ctx, s);
+    return f.solve(issue, host_info);
 }
 
 }  // namespace
@@ -1270,22 +1170,11 @@ int fcg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, 
 //       the next FA; with one: z = M r, then a three-dot partials kernel
 namespace {
 
-struct fcg_scalars {
-    double rho[2];  // rho of iteration `it` lives in rho[it & 1]
-    double tau, orig_tau;
-    long long stop_iter;
-    unsigned char status;
-    unsigned char pad[7];
-};
+struct fcg_scalars : fused_scalars {};
 
 __global__ void fcg_fused_init_kernel(fcg_scalars* scal, const double* orig_tau)
 {
-    scal->rho[0] = 0.0;
-    scal->rho[1] = 1.0;  // prev_rho = 1 (fcg::initialize)
-    scal->tau = 0.0;
-    scal->orig_tau = orig_tau[0];
-    scal->stop_iter = -1;
-    scal->status = 0;
+    init_fused_scalars(scal, 0.0, orig_tau[0]);  // prev_rho = 1 (fcg::initialize)
 }
 
 // p0[b] = sum r*z, p1[b] = sum t*z, p2[b] = sum r*r
@@ -1296,48 +1185,38 @@ __global__ __launch_bounds__(fblock) void fused_dot3_partials_kernel(
 {
     __shared__ double smem[fblock / wave_size];
     if (status != nullptr && status_has_stopped(status[0])) return;
-    const int64_t step = static_cast<int64_t>(gridDim.x) * fblock;
-    double a = 0.0, b = 0.0, c = 0.0;
+    double sum[3] = {0.0, 0.0, 0.0};
     const bool vec = ((reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(z) |
                        reinterpret_cast<uintptr_t>(t)) & 15) == 0;
     if (vec) {  // 16 B per lane
-        const int64_t n2 = n / 2;
-        double a1 = 0.0, b1 = 0.0, c1 = 0.0;
-        for (int64_t i = blockIdx.x * static_cast<int64_t>(fblock) + threadIdx.x; i < n2; i += step) {
-            const double2 rv = ld2(r, i), zv = ld2(z, i), tv = ld2(t, i);
-            a += rv.x * zv.x;
-            a1 += rv.y * zv.y;
-            b += tv.x * zv.x;
-            b1 += tv.y * zv.y;
-            c += rv.x * rv.x;
-            c1 += rv.y * rv.y;
-        }
-        a += a1;
-        b += b1;
-        c += c1;
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            a += r[n - 1] * z[n - 1];
-            b += t[n - 1] * z[n - 1];
-            c += r[n - 1] * r[n - 1];
-        }
+        const pair_sweep sw(n);
+        const double* const in[] = {r, z, t};
+        double a[2] = {0.0, 0.0}, b[2] = {0.0, 0.0}, c[2] = {0.0, 0.0};
+        auto dots = [&](int half, const double* e) {
+            a[half] += e[0] * e[1];
+            b[half] += e[2] * e[1];
+            c[half] += e[0] * e[0];
+        };
+        sw.loop(sw.i0, in, dots);
+        // the halves are joined before the tail is added
+        a[0] += a[1];
+        b[0] += b[1];
+        c[0] += c[1];
+        sw.tail(in, dots);
+        sum[0] = a[0];
+        sum[1] = b[0];
+        sum[2] = c[0];
     } else {
+        const int64_t step = static_cast<int64_t>(gridDim.x) * fblock;
         for (int64_t i = blockIdx.x * static_cast<int64_t>(fblock) + threadIdx.x; i < n; i += step) {
             const double rv = r[i], zv = z[i];
-            a += rv * zv;
-            b += t[i] * zv;
-            c += rv * rv;
+            sum[0] += rv * zv;
+            sum[1] += t[i] * zv;
+            sum[2] += rv * rv;
         }
     }
-    const double ta = block_reduce_sum<fblock>(a, smem);
-    __syncthreads();
-    const double tb = block_reduce_sum<fblock>(b, smem);
-    __syncthreads();
-    const double tc = block_reduce_sum<fblock>(c, smem);
-    if (threadIdx.x == 0) {
-        p0[blockIdx.x] = ta;
-        p1[blockIdx.x] = tb;
-        p2[blockIdx.x] = tc;
-    }
+    double* const part[] = {p0, p1, p2};
+    store_block_sums(false, sum, part, smem);
 }
 
 // FA.  z may alias r (Identity).
@@ -1348,45 +1227,20 @@ __global__ __launch_bounds__(fblock) void fcg_fused_step1_kernel(
     long long max_iters, double goal, host_watch_line* watch = nullptr)
 {
     __shared__ double smem[fblock / wave_size];
-    if (status_has_stopped(scal->status)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) host_watch_publish(watch, it, scal->stop_iter);  // internal.hpp
-        return;
-    }
+    if (fused_stopped_before(status_has_stopped(scal->status), scal, watch, it)) return;
     const pair_sweep sw(n);
-    double2 z0 = make_double2(0.0, 0.0), p0 = z0;
-    if (sw.first()) {
-        z0 = ld2(z, sw.i0);
-        p0 = ld2(p, sw.i0);
-    }
-    const double rho = sum_partials_f(rho_part, nparts, smem);
-    const double rho_t = sum_partials_f(rhot_part, nparts, smem);
-    const double tau = sqrt(rho_part == tau_part ? rho : sum_partials_f(tau_part, nparts, smem));
-    uint8_t st = 0;
-    if (it >= max_iters) {
-        st = 1 | GKOMI_STATUS_FINALIZED;
-    } else if (tau < goal * scal->orig_tau) {
-        st = GKOMI_STATUS_CONVERGED | 1 | GKOMI_STATUS_FINALIZED;
-    }
+    const double* const in[] = {z, p};
+    double* const out[] = {p};
+    const auto first = sw.prefetch(in);
+    const double rho = sum_partials(rho_part, nparts, smem);
+    const double rho_t = sum_partials(rhot_part, nparts, smem);
+    const double tau = sqrt(rho_part == tau_part ? rho : sum_partials(tau_part, nparts, smem));
     const double prev = scal->rho[(it + 1) & 1];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        scal->rho[it & 1] = rho;
-        scal->tau = tau;  // also at the iteration limit: the norm of the residual that is returned
-        if (st) {
-            scal->stop_iter = it;
-            scal->status = st;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) host_watch_publish(watch, it, st ? it : -1ll);
-    if (st) return;
+    if (fused_criterion(scal, watch, it, max_iters, rho, tau, goal, 1, 1)) return;
+    // fcg::step_1
     const bool restart = prev == 0.0;
     const double tmp = restart ? 0.0 : rho_t / prev;
-    auto step1 = [&](double zv, double pv) { return restart ? zv : zv + tmp * pv; };
-    if (sw.first()) st2(p, sw.i0, make_double2(step1(z0.x, p0.x), step1(z0.y, p0.y)));
-    for (int64_t i = sw.i0 + sw.step; i < sw.n2; i += sw.step) {
-        const double2 zv = ld2(z, i), pv = ld2(p, i);
-        st2(p, i, make_double2(step1(zv.x, pv.x), step1(zv.y, pv.y)));
-    }
-    if (sw.tail(n)) p[n - 1] = step1(z[n - 1], p[n - 1]);
+    sw.run(first, in, out, true, [&](int, const double* e, double* o) { o[0] = restart ? e[0] : e[0] + tmp * e[1]; });
 }
 
 // FC.  With partials != nullptr (Identity): leaves r.r and t.r of the new r, t.
@@ -1399,69 +1253,32 @@ __global__ __launch_bounds__(fblock) void fcg_fused_step2_kernel(
     __shared__ double smem[fblock / wave_size];
     if (status_has_stopped(scal->status)) return;
     const pair_sweep sw(n);
-    double2 x0 = make_double2(0.0, 0.0), r0 = x0, p0 = x0, q0 = x0, t0 = x0;
-    if (sw.first()) {
-        x0 = ld2(x, sw.i0);
-        r0 = ld2(r, sw.i0);
-        p0 = ld2(p, sw.i0);
-        q0 = ld2(q, sw.i0);
-        t0 = ld2(t, sw.i0);
-    }
-    const double beta = sum_partials_f(beta_part, nparts, smem);
+    const double* const in[] = {x, r, t, p, q};
+    double* const out[] = {x, r, t};
+    const auto first = sw.prefetch(in);
+    const double beta = sum_partials(beta_part, nparts, smem);
     const double rho = scal->rho[it & 1];
     const bool update = beta != 0.0;
     const double tmp = update ? rho / beta : 0.0;
-    double a0 = 0.0, a1 = 0.0;
-    // fcg::step_2; returns through the references, accumulates r.r and t.r
-    auto step2 = [&](double& xv, double& rv, double& tv, double pv, double qv) {
+    // fcg::step_2; r.r and t.r, both halves and the tail into the same two accumulators (beta == 0: nothing is written)
+    double acc[2] = {0.0, 0.0};
+    sw.run(first, in, out, update, [&](int, const double* e, double* o) {
+        double xv = e[0], rv = e[1], tv = e[2];
         if (update) {
             const double prev_r = rv;
-            xv += tmp * pv;
-            rv = prev_r - tmp * qv;
+            xv += tmp * e[3];
+            rv = prev_r - tmp * e[4];
             tv = rv - prev_r;
         }
-        a0 += rv * rv;
-        a1 += tv * rv;
-    };
-    if (sw.first()) {
-        step2(x0.x, r0.x, t0.x, p0.x, q0.x);
-        step2(x0.y, r0.y, t0.y, p0.y, q0.y);
-        if (update) {
-            st2(x, sw.i0, x0);
-            st2(r, sw.i0, r0);
-            st2(t, sw.i0, t0);
-        }
-    }
-    for (int64_t i = sw.i0 + sw.step; i < sw.n2; i += sw.step) {
-        double2 xv = ld2(x, i), rv = ld2(r, i), tv = ld2(t, i);
-        const double2 pv = ld2(p, i), qv = ld2(q, i);
-        step2(xv.x, rv.x, tv.x, pv.x, qv.x);
-        step2(xv.y, rv.y, tv.y, pv.y, qv.y);
-        if (update) {
-            st2(x, i, xv);
-            st2(r, i, rv);
-            st2(t, i, tv);
-        }
-    }
-    if (sw.tail(n)) {
-        const int64_t i = n - 1;
-        double xv = x[i], rv = r[i], tv = t[i];
-        step2(xv, rv, tv, p[i], q[i]);
-        if (update) {
-            x[i] = xv;
-            r[i] = rv;
-            t[i] = tv;
-        }
-    }
+        o[0] = xv;
+        o[1] = rv;
+        o[2] = tv;
+        acc[0] += rv * rv;
+        acc[1] += tv * rv;
+    });
     if (rr_part == nullptr) return;
-    __syncthreads();
-    const double s0 = block_reduce_sum<fblock>(a0, smem);
-    __syncthreads();
-    const double s1 = block_reduce_sum<fblock>(a1, smem);
-    if (threadIdx.x == 0) {
-        rr_part[blockIdx.x] = s0;
-        tr_part[blockIdx.x] = s1;
-    }
+    double* const part[] = {rr_part, tr_part};
+    store_block_sums(true, acc, part, smem);
 }
 
 int fcg_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn precond,
@@ -1485,18 +1302,14 @@ int fcg_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
     GKOMI_TRY(c.start(b, x, r, baseline));
     // t = b from initialize, exactly like the reference (fcg.cpp:137 does not refresh it after r = b - A x)
     hipStream_t stream = c.stream;
-    double* parts = reinterpret_cast<double*>(ws + l.parts);
-    fcg_scalars* scal = reinterpret_cast<fcg_scalars*>(parts);
-    double* part_rho = parts + 32;
-    double* part_rhot = part_rho + fused_max_parts;
-    double* part_tau = part_rhot + fused_max_parts;
-    double* part_beta = part_tau + fused_max_parts;
-    const size_t per_spmv = spmv_dot_partials_room(n);  // >= g: room for three arrays (layout)
-    const int g = fused_vec_grid(n);
-    // the dots in the SpMV's epilogue for CSR / ELL / SELL-P (internal.hpp)
-    const spmv_dot_plan spmv(A);
+    fused_driver<fcg_scalars> f(c, ws, l);
+    fcg_scalars* scal = f.scal;
+    double *part_rho = f.vec_partials(), *part_rhot = f.vec_partials(), *part_tau = f.vec_partials();
+    double* part_beta = f.spmv_partials();  // (and, without the epilogue, two more of that size as scratch)
+    const size_t per_spmv = f.per_spmv;
+    const int g = f.g, nb = f.nb;
+    const spmv_dot_plan& spmv = f.spmv;
     const bool csr_epilogue = spmv.fused();
-    const int nb = csr_epilogue ? spmv.num_partials : g;
     const bool identity = precond == nullptr;
     if (identity) z = r;
     hipLaunchKernelGGL(fcg_fused_init_kernel, dim3(1), dim3(1), 0, stream, scal, c.orig_tau);
@@ -1504,10 +1317,7 @@ int fcg_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
     hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, z, t,
                        static_cast<const unsigned char*>(nullptr), part_rho, part_rhot, part_tau);
     GKOMI_TRY(check_launch());
-    fcg_scalars h{};
-    // paced by pace_fused_solve (internal.hpp); of the last iteration only step 1 is enqueued
-    host_watch watch;
-    const long long lag = std::min<long long>(c.check_every, precond == nullptr ? 4 * host_watch_lag : host_watch_lag);
+    host_watch& watch = f.watch;
     auto issue = [&](long long it, bool last) -> int {
         hipLaunchKernelGGL(fcg_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, p, z, part_rho,
                            part_rhot, identity ? part_rho : part_tau, g, scal, it,
@@ -1531,15 +1341,7 @@ int fcg_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
         }
         return check_launch();
     };
-    auto look = [&]() -> int {
-        const int err = read_scalars(stream, &h, scal);
-        return err ? -err : h.stop_iter >= 0;
-    };
-    bool looked = false;
-    GKOMI_TRY(pace_fused_solve(stream, &watch, max_iters, c.check_every, lag, issue, look, &looked));
-    if (!looked) GKOMI_TRY(read_scalars(stream, &h, scal));
-    fill_host_info(host_info, h.stop_iter, h.status, h.tau, h.orig_tau);
-    return precond_status(precond, precond_ctx, s);
+    return f.solve(issue, host_info);
 }
 
 }  // namespace
@@ -1645,24 +1447,15 @@ int cgs_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, 
 //   GE  x += alpha u_hat, r -= alpha t (cgs::step_3), partials for the next GA
 namespace {
 
-struct cgs_scalars {
-    double rho[2];
-    double alpha, beta, tau, orig_tau;
-    long long stop_iter;
-    unsigned char status;
-    unsigned char pad[7];
+struct cgs_scalars : fused_scalars {
+    double alpha, beta;
 };
 
 __global__ void cgs_fused_init_kernel(cgs_scalars* scal, const double* orig_tau)
 {
-    scal->rho[0] = 0.0;
-    scal->rho[1] = 1.0;  // prev_rho = alpha = beta = gamma = 1 (cgs::initialize)
+    init_fused_scalars(scal, 0.0, orig_tau[0]);  // prev_rho = alpha = beta = gamma = 1 (cgs::initialize)
     scal->alpha = 1.0;
     scal->beta = 1.0;
-    scal->tau = 0.0;
-    scal->orig_tau = orig_tau[0];
-    scal->stop_iter = -1;
-    scal->status = 0;
 }
 
 // GA
@@ -1673,68 +1466,30 @@ __global__ __launch_bounds__(fblock) void cgs_fused_step1_kernel(
     long long max_iters, double goal, host_watch_line* watch = nullptr)
 {
     __shared__ double smem[fblock / wave_size];
-    if (status_has_stopped(scal->status)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) host_watch_publish(watch, it, scal->stop_iter);  // internal.hpp
-        return;
-    }
+    if (fused_stopped_before(status_has_stopped(scal->status), scal, watch, it)) return;
     const pair_sweep sw(n);
-    double2 r0 = make_double2(0.0, 0.0), q0 = r0, p0 = r0;
-    if (sw.first()) {
-        r0 = ld2(r, sw.i0);
-        q0 = ld2(q, sw.i0);
-        p0 = ld2(p, sw.i0);
-    }
-    const double rho = sum_partials_f(rho_part, nparts, smem);
-    const double tau = sqrt(sum_partials_f(tau_part, nparts, smem));
-    uint8_t st = 0;
-    if (it >= max_iters) {
-        st = 1 | GKOMI_STATUS_FINALIZED;
-    } else if (tau < goal * scal->orig_tau) {
-        st = GKOMI_STATUS_CONVERGED | 1 | GKOMI_STATUS_FINALIZED;
-    }
+    const double* const in[] = {r, q, p};
+    double* const out[] = {u, p};
+    const auto first = sw.prefetch(in);
+    const double rho = sum_partials(rho_part, nparts, smem);
+    const double tau = sqrt(sum_partials(tau_part, nparts, smem));
     const double prev = scal->rho[(it + 1) & 1];
     const bool update = prev != 0.0;
-    // beta is rewritten only when prev_rho != 0, and then nobody reads the old value
-    const double bt = update ? rho / prev : scal->beta;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        scal->rho[it & 1] = rho;
-        scal->tau = tau;  // also at the iteration limit: the norm of the residual that is returned
-        if (st) {
-            scal->stop_iter = it;
-            scal->status = st;
-        } else if (update) {
-            scal->beta = bt;
-        }
+    // beta is rewritten only when prev_rho != 0, and then nobody reads the old value.  (Read before the select, not
+    // inside it: with the store in fused_criterion's lambda the other form costs 14 VGPRs and a wave per SIMD.)
+    const double old_beta = scal->beta;
+    const double bt = update ? rho / prev : old_beta;
+    if (fused_criterion(scal, watch, it, max_iters, rho, tau, goal, 1, 1, [&](uint8_t st) {
+            if (!st && update) scal->beta = bt;
+        })) {
+        return;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) host_watch_publish(watch, it, st ? it : -1ll);
-    if (st) return;
-    auto step1 = [&](double rv, double qv, double pv, double* uo, double* po) {
-        const double uu = rv + bt * qv;
-        *uo = uu;
-        *po = uu + bt * (qv + bt * pv);
-    };
-    if (sw.first()) {
-        double2 uo, po;
-        step1(r0.x, q0.x, p0.x, &uo.x, &po.x);
-        step1(r0.y, q0.y, p0.y, &uo.y, &po.y);
-        st2(u, sw.i0, uo);
-        st2(p, sw.i0, po);
-    }
-    for (int64_t i = sw.i0 + sw.step; i < sw.n2; i += sw.step) {
-        const double2 rv = ld2(r, i), qv = ld2(q, i), pv = ld2(p, i);
-        double2 uo, po;
-        step1(rv.x, qv.x, pv.x, &uo.x, &po.x);
-        step1(rv.y, qv.y, pv.y, &uo.y, &po.y);
-        st2(u, i, uo);
-        st2(p, i, po);
-    }
-    if (sw.tail(n)) {
-        const int64_t i = n - 1;
-        double uo, po;
-        step1(r[i], q[i], p[i], &uo, &po);
-        u[i] = uo;
-        p[i] = po;
-    }
+    // cgs::step_1
+    sw.run(first, in, out, true, [&](int, const double* e, double* o) {
+        const double uu = e[0] + bt * e[1];
+        o[0] = uu;
+        o[1] = uu + bt * (e[1] + bt * e[2]);
+    });
 }
 
 // GC
@@ -1746,45 +1501,21 @@ __global__ __launch_bounds__(fblock) void cgs_fused_step2_kernel(
     __shared__ double smem[fblock / wave_size];
     if (status_has_stopped(scal->status)) return;
     const pair_sweep sw(n);
-    double2 u0 = make_double2(0.0, 0.0), v0 = u0;
-    if (sw.first()) {
-        u0 = ld2(u, sw.i0);
-        v0 = ld2(v_hat, sw.i0);
-    }
-    const double gamma = sum_partials_f(gamma_part, nparts, smem);
+    const double* const in[] = {u, v_hat};
+    double* const out[] = {q, t};
+    const auto first = sw.prefetch(in);
+    const double gamma = sum_partials(gamma_part, nparts, smem);
     const bool update = gamma != 0.0;
     const double a = update ? scal->rho[it & 1] / gamma : scal->alpha;
-    if (update && blockIdx.x == 0 && threadIdx.x == 0) scal->alpha = a;
-    auto step2 = [&](double uv, double vv, double* qo, double* to) {
-        const double qq = uv - a * vv;
-        *qo = qq;
-        *to = uv + qq;
-    };
-    if (sw.first()) {
-        double2 qo, to;
-        step2(u0.x, v0.x, &qo.x, &to.x);
-        step2(u0.y, v0.y, &qo.y, &to.y);
-        st2(q, sw.i0, qo);
-        st2(t, sw.i0, to);
-    }
-    for (int64_t i = sw.i0 + sw.step; i < sw.n2; i += sw.step) {
-        const double2 uv = ld2(u, i), vv = ld2(v_hat, i);
-        double2 qo, to;
-        step2(uv.x, vv.x, &qo.x, &to.x);
-        step2(uv.y, vv.y, &qo.y, &to.y);
-        st2(q, i, qo);
-        st2(t, i, to);
-    }
-    if (sw.tail(n)) {
-        const int64_t i = n - 1;
-        double qo, to;
-        step2(u[i], v_hat[i], &qo, &to);
-        q[i] = qo;
-        t[i] = to;
-    }
+    if (update && fused_leader()) scal->alpha = a;
+    // cgs::step_2
+    sw.run(first, in, out, true, [&](int, const double* e, double* o) {
+        o[0] = e[0] - a * e[1];
+        o[1] = e[0] + o[0];
+    });
 }
 
-// GE: x += alpha xdir, r -= alpha rdir; partials of r.r_tld and r.r
+// GE: x += alpha xdir, r -= alpha rdir; partials of r.r_tld and r.r.  No prefetch: nothing to re-add, alpha is there.
 __global__ __launch_bounds__(fblock) void cgs_fused_step3_kernel(
     int64_t n, double* __restrict__ x, double* __restrict__ r, const double* __restrict__ xdir,
     const double* __restrict__ rdir, const double* __restrict__ r_tld, cgs_scalars* scal,
@@ -1793,38 +1524,19 @@ __global__ __launch_bounds__(fblock) void cgs_fused_step3_kernel(
     __shared__ double smem[fblock / wave_size];
     if (status_has_stopped(scal->status)) return;
     const double alpha = scal->alpha;
-    const int64_t n2 = n / 2;
-    const int64_t step = static_cast<int64_t>(gridDim.x) * fblock;
-    double a0 = 0.0, a1 = 0.0;
-    auto step3 = [&](double& xv, double& rv, double xd, double rd, double rt) {
-        xv += alpha * xd;
-        rv -= alpha * rd;
-        a0 += rv * rt;
-        a1 += rv * rv;
-    };
-    for (int64_t i = blockIdx.x * static_cast<int64_t>(fblock) + threadIdx.x; i < n2; i += step) {
-        double2 xv = ld2(x, i), rv = ld2(r, i);
-        const double2 xd = ld2(xdir, i), rd = ld2(rdir, i), rt = ld2(r_tld, i);
-        step3(xv.x, rv.x, xd.x, rd.x, rt.x);
-        step3(xv.y, rv.y, xd.y, rd.y, rt.y);
-        st2(x, i, xv);
-        st2(r, i, rv);
-    }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const int64_t i = n - 1;
-        double xv = x[i], rv = r[i];
-        step3(xv, rv, xdir[i], rdir[i], r_tld[i]);
-        x[i] = xv;
-        r[i] = rv;
-    }
-    __syncthreads();
-    const double s0 = block_reduce_sum<fblock>(a0, smem);
-    __syncthreads();
-    const double s1 = block_reduce_sum<fblock>(a1, smem);
-    if (threadIdx.x == 0) {
-        rho_part[blockIdx.x] = s0;
-        tau_part[blockIdx.x] = s1;
-    }
+    const pair_sweep sw(n);
+    const double* const in[] = {x, r, xdir, rdir, r_tld};
+    double* const out[] = {x, r};
+    // cgs::step_3; both halves and the tail into the same two accumulators
+    double acc[2] = {0.0, 0.0};
+    sw.run(in, out, true, [&](int, const double* e, double* o) {
+        o[0] = e[0] + alpha * e[2];
+        o[1] = e[1] - alpha * e[3];
+        acc[0] += o[1] * e[4];
+        acc[1] += o[1] * o[1];
+    });
+    double* const part[] = {rho_part, tau_part};
+    store_block_sums(true, acc, part, smem);
 }
 
 int cgs_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn precond,
@@ -1849,27 +1561,21 @@ int cgs_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
     GKOMI_TRY(c.start(b, x, r, baseline));
     GKOMI_TRY(gkomi_dense_copy_f64(s, n, 1, r, 1, r_tld, 1));
     hipStream_t stream = c.stream;
-    double* parts = reinterpret_cast<double*>(ws + l.parts);
-    cgs_scalars* scal = reinterpret_cast<cgs_scalars*>(parts);
-    double* part_rho = parts + 32;
-    double* part_tau = part_rho + fused_max_parts;
-    double* part_gamma = part_tau + 2 * fused_max_parts;
-    const size_t per_spmv = spmv_dot_partials_room(n);
-    const int g = fused_vec_grid(n);
-    // the dots in the SpMV's epilogue for CSR / ELL / SELL-P (internal.hpp)
-    const spmv_dot_plan spmv(A);
+    fused_driver<cgs_scalars> f(c, ws, l);
+    cgs_scalars* scal = f.scal;
+    double *part_rho = f.vec_partials(), *part_tau = f.vec_partials();
+    double* part_gamma = f.spmv_partials();  // (and two more of that size as scratch)
+    const size_t per_spmv = f.per_spmv;
+    const int g = f.g, nb = f.nb;
+    const spmv_dot_plan& spmv = f.spmv;
     const bool csr_epilogue = spmv.fused();
-    const int nb = csr_epilogue ? spmv.num_partials : g;
     const bool identity = precond == nullptr;
     hipLaunchKernelGGL(cgs_fused_init_kernel, dim3(1), dim3(1), 0, stream, scal, c.orig_tau);
     // partials of r.r_tld and r.r (the third sum is scratch)
     hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, r_tld, r,
                        static_cast<const unsigned char*>(nullptr), part_rho, part_gamma + per_spmv, part_tau);
     GKOMI_TRY(check_launch());
-    cgs_scalars h{};
-    // paced by pace_fused_solve (internal.hpp); of the last iteration only step 1 is enqueued
-    host_watch watch;
-    const long long lag = std::min<long long>(c.check_every, precond == nullptr ? 4 * host_watch_lag : host_watch_lag);
+    host_watch& watch = f.watch;
     auto issue = [&](long long it, bool last) -> int {
         hipLaunchKernelGGL(cgs_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, r, u, p, q, part_rho,
                            part_tau, g, scal, it, static_cast<long long>(max_iters), reduction_factor, watch.dev);
@@ -1907,15 +1613,7 @@ int cgs_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
                            r_tld, scal, part_rho, part_tau);
         return check_launch();
     };
-    auto look = [&]() -> int {
-        const int err = read_scalars(stream, &h, scal);
-        return err ? -err : h.stop_iter >= 0;
-    };
-    bool looked = false;
-    GKOMI_TRY(pace_fused_solve(stream, &watch, max_iters, c.check_every, lag, issue, look, &looked));
-    if (!looked) GKOMI_TRY(read_scalars(stream, &h, scal));
-    fill_host_info(host_info, h.stop_iter, h.status, h.tau, h.orig_tau);
-    return precond_status(precond, precond_ctx, s);
+    return f.solve(issue, host_info);
 }
 
 }  // namespace

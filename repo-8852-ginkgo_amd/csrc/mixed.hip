@@ -117,13 +117,8 @@ __global__ __launch_bounds__(fblock) void cgf_init_kernel(cg_scalars* scal, cons
     __shared__ double smem[fblock / wave_size];
     const double orig = baseline_absolute ? 1.0 : sqrt(sum_partials(base_part, nparts, smem));
     if (threadIdx.x == 0) {
-        scal->rho[0] = 0.0;
-        scal->rho[1] = 1.0;
-        scal->tau = 0.0;
-        scal->orig_tau = orig;
+        init_fused_scalars(scal, 0.0, orig);
         scal->beta = 0.0;
-        scal->stop_iter = -1;
-        scal->status = 0;
     }
 }
 
@@ -134,28 +129,9 @@ __global__ __launch_bounds__(fblock) void cgf_step1_kernel(int64_t n, float* __r
                                                            host_watch_line* watch)
 {
     __shared__ double smem[fblock / wave_size];
-    if (status_has_stopped(scal->status)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) host_watch_publish(watch, it, scal->stop_iter);
-        return;
-    }
+    if (fused_stopped_before(status_has_stopped(scal->status), scal, watch, it)) return;
     const double rho = sum_partials(rr_part, nparts, smem);
-    const double tau = sqrt(rho);
-    uint8_t st = 0;
-    if (it >= max_iters) {
-        st = id_iteration | GKOMI_STATUS_FINALIZED;
-    } else if (tau < goal * scal->orig_tau) {
-        st = GKOMI_STATUS_CONVERGED | id_residual | GKOMI_STATUS_FINALIZED;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        scal->rho[it & 1] = rho;
-        scal->tau = tau;
-        if (st) {
-            scal->stop_iter = it;
-            scal->status = st;
-        }
-        host_watch_publish(watch, it, st ? it : -1ll);
-    }
-    if (st) return;
+    if (fused_criterion(scal, watch, it, max_iters, rho, sqrt(rho), goal, id_iteration, id_residual)) return;
     const double prev = scal->rho[(it + 1) & 1];
     const bool restart = prev == 0.0;
     const float tmp = restart ? 0.0f : static_cast<float>(rho / prev);

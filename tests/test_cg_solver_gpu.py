@@ -368,3 +368,23 @@ def test_fused_cg_block_jacobi_compresses_the_partials_of_a_large_system(gk, ora
     r = b.reshape(n, 1).copy()
     oracle.ref_csr_advanced_spmv(n, 1, -1.0, rp, ci, v, np.ascontiguousarray(host(fused["x"])).reshape(n, 1), 1, 1.0, r, 1)
     assert np.linalg.norm(r) / np.linalg.norm(b) <= 2e-10
+
+
+def test_fused_cg_sweeps_twice_and_takes_the_odd_tail(gk):
+    """poisson_2d_5pt(1025) without a preconditioner: more pairs than the 512 workgroups x 1024 lanes of the fused
+    vector kernels on 256 CUs (1024 lanes run their grid-stride loop once) and an odd n (the one-element tail runs).
+    Three iterations, fused against the reference kernel sequence, with the bounds of the iteration-limit check of
+    the other Krylov drivers (test_krylov_gpu.py)."""
+    n, rp, ci, v = matgen.poisson_2d_5pt(1025)
+    assert n % 2 == 1 and n // 2 > 1024 * 512
+    b = np.sin(0.001 * np.arange(n))
+    rpd, cid, vd, bd = dev(rp), dev(ci), dev(v), dev(b)
+    a = solvers.cg_solve(gk, n, rpd, cid, vd, bd, max_iters=3, reduction=1e-14, mode=1)
+    u = solvers.cg_solve(gk, n, rpd, cid, vd, bd, max_iters=3, reduction=1e-14, mode=0)
+    assert a["iterations"] == 3 and not a["converged"] and u["iterations"] == 3 and not u["converged"]
+    err = matgen.rel_err(host(a["x"]), host(u["x"]))
+    r3 = b - np.add.reduceat(v * host(a["x"])[ci], rp[:-1])
+    gap = abs(np.linalg.norm(r3) - a["residual_norm"][0]) / np.linalg.norm(b)
+    print(f"two_sweep cg identity: rel_err {err:.3e} residual gap {gap:.3e}")
+    assert err < 1e-12
+    assert gap <= 1e-9

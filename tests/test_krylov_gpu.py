@@ -397,6 +397,37 @@ def test_fused_bicgstab_stops_in_the_half_step_and_at_the_iteration_limit(gk, or
     assert z["iterations"] == 0 and not z["converged"] and not host(z["x"]).any()
 
 
+@pytest.fixture(scope="module")
+def two_sweep_system(gk):
+    """poisson_2d_5pt(1025): more pairs than the 512 workgroups x 1024 lanes of the fused vector kernels on 256 CUs
+    (1024 lanes run their grid-stride loop once) and an odd n (the one-element tail runs)."""
+    n, rp, ci, v = matgen.poisson_2d_5pt(1025)
+    assert n % 2 == 1 and n // 2 > 1024 * 512
+    b = np.sin(0.001 * np.arange(n))
+    rpd, cid, vd = dev(rp), dev(ci), dev(v)
+    return dict(n=n, rp=rp, ci=ci, v=v, b=b, rpd=rpd, cid=cid, vd=vd, bd=dev(b),
+                jacobi=solvers.jacobi_generate(gk, n, rpd, cid, vd, max_block_size=8))
+
+
+@pytest.mark.parametrize("precond", ["identity", "jacobi"])
+@pytest.mark.parametrize("solver", ["bicgstab", "fcg", "cgs"])
+def test_fused_drivers_sweep_twice_and_take_the_odd_tail(gk, two_sweep_system, solver, precond):
+    """The iteration-limit check of test_fused_bicgstab_stops_in_the_half_step_and_at_the_iteration_limit, same
+    bounds, at the smallest square grid where the loop and the tail of the fused step kernels run at all."""
+    s = two_sweep_system
+    pc = s["jacobi"] if precond == "jacobi" else None
+    kw = dict(max_iters=3, reduction=1e-14, precond=pc)
+    a = solvers.krylov_solve(gk, solver, s["n"], s["rpd"], s["cid"], s["vd"], s["bd"], fused=True, **kw)
+    u = solvers.krylov_solve(gk, solver, s["n"], s["rpd"], s["cid"], s["vd"], s["bd"], **kw)
+    assert a["iterations"] == 3 and not a["converged"] and u["iterations"] == 3 and not u["converged"]
+    err = matgen.rel_err(host(a["x"]), host(u["x"]))
+    r3 = s["b"] - np.add.reduceat(s["v"] * host(a["x"])[s["ci"]], s["rp"][:-1])
+    gap = abs(np.linalg.norm(r3) - a["residual_norm"][0]) / np.linalg.norm(s["b"])
+    print(f"two_sweep {solver} {precond}: rel_err {err:.3e} residual gap {gap:.3e}")
+    assert err < 1e-12
+    assert gap <= 1e-9
+
+
 def test_fused_bicgstab_with_preconditioners_and_formats(gk, oracle):
     from gkomi import formats
     n, rp, ci, v = _convection()
