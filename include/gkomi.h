@@ -1658,6 +1658,103 @@ int gkomi_gmres_solve_f64_i32(gkomi_stream_t s, int64_t n, int64_t nrhs,
                               int baseline, void* workspace,
                               size_t workspace_bytes, double* host_info);
 
+/* IDR(s), core/solver/idr_kernels.hpp (semantics: reference/solver/idr_kernels.cpp;
+ * initialize :134-189, step_1 :194-219, step_2 :224-244, step_3 :249-287 with
+ * update_g_and_u :83-112 and solve_lower_triangular :60-80, compute_omega :292-313).
+ * Real subspace, fp64.  Layouts are the reference's: m is s x (s nrhs), g and u are
+ * n x (s nrhs) row-major with column k nrhs + i belonging to right-hand side i,
+ * subspace_vectors is s x n, f and c are s x nrhs, scalars 1 x nrhs on the device,
+ * one status byte per column (stopped columns are left untouched).  1 <= s <= 32,
+ * 0 <= k < s, else GKOMI_EINVAL.  initialize never draws random numbers (the
+ * reference's deterministic == true): it sets m to the identity pattern, resets the
+ * statuses and orthonormalises the rows of subspace_vectors as the caller filled
+ * them (modified Gram-Schmidt in row order, s <= n).  step_1 (which first solves
+ * c = M \ f), step_2 and compute_omega are bit-identical to the reference; the dots
+ * of step_3 and initialize are summed in a two-stage order.  step_3 needs
+ * gkomi_idr_step_3_workspace_bytes(nrhs, s) bytes of device workspace. */
+int gkomi_idr_initialize_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+    int64_t subspace_dim, double* m, int64_t m_stride, double* subspace_vectors,
+    int64_t subspace_stride, uint8_t* stop_status);
+int gkomi_idr_step_1_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+    int64_t subspace_dim, int64_t k, const double* m, int64_t m_stride,
+    const double* f, int64_t f_stride, const double* residual,
+    int64_t residual_stride, const double* g, int64_t g_stride, double* c,
+    int64_t c_stride, double* v, int64_t v_stride, const uint8_t* stop_status);
+int gkomi_idr_step_2_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+    int64_t subspace_dim, int64_t k, const double* omega,
+    const double* preconditioned_vector, int64_t pv_stride, const double* c,
+    int64_t c_stride, double* u, int64_t u_stride, const uint8_t* stop_status);
+size_t gkomi_idr_step_3_workspace_bytes(int64_t nrhs, int64_t subspace_dim);
+int gkomi_idr_step_3_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+    int64_t subspace_dim, int64_t k, const double* subspace_vectors,
+    int64_t subspace_stride, double* g, int64_t g_stride, double* g_k,
+    int64_t g_k_stride, double* u, int64_t u_stride, double* m, int64_t m_stride,
+    double* f, int64_t f_stride, double* alpha, double* residual,
+    int64_t residual_stride, double* x, int64_t x_stride,
+    const uint8_t* stop_status, void* workspace, size_t workspace_bytes);
+int gkomi_idr_compute_omega_f64(gkomi_stream_t s, int64_t nrhs, double kappa,
+    const double* tht, const double* residual_norm, double* omega,
+    const uint8_t* stop_status);
+/* Idr::iterate (core/solver/idr.cpp:157-290) as the reference's kernel sequence,
+ * Combined(Iteration, ResidualNorm) evaluated on the device once per outer
+ * iteration (the host looks every check_every evaluations).  Arguments and
+ * host_info as gkomi_bicgstab_solve_f64_i32, plus subspace_dim (1..32, <= n),
+ * kappa and the device pointer `subspace`: s x n row-major, filled by the caller,
+ * orthonormalised in place.  The solution update uses the preconditioned residual,
+ * as the code at idr.cpp:289 does.  Two departures from idr.cpp, both so that what
+ * is reported is true: the criterion sees the norm of the residual it returns (the
+ * reference hands it the norm from before the omega step, :273), and a column that
+ * has stopped keeps its x and residual (Dense::add_scaled at :288-289 moves it on).
+ * precond == NULL = Identity.  Workspace: gkomi_idr_workspace_bytes(n, nrhs, s). */
+size_t gkomi_idr_workspace_bytes(int64_t n, int64_t nrhs, int64_t subspace_dim);
+int gkomi_idr_solve_f64_i32(gkomi_stream_t s, int64_t n, int64_t nrhs,
+    int64_t nnz, const int32_t* row_ptrs, const int32_t* col_idxs,
+    const double* vals, int spmv_strategy, int64_t max_row_nnz_hint,
+    gkomi_apply_fn precond, void* precond_ctx, int64_t subspace_dim, double kappa,
+    double* subspace, const double* b, double* x, int64_t max_iters,
+    double reduction_factor, int baseline, int64_t check_every, void* workspace,
+    size_t workspace_bytes, double* host_info);
+int gkomi_idr_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+    gkomi_matrix_apply_fn matrix, void* matrix_ctx, gkomi_apply_fn precond,
+    void* precond_ctx, int64_t subspace_dim, double kappa, double* subspace,
+    const double* b, double* x, int64_t max_iters, double reduction_factor,
+    int baseline, int64_t check_every, void* workspace, size_t workspace_bytes,
+    double* host_info);
+/* Fused IDR(s) for one right-hand side and s <= 8 (GKOMI_ENOTSUPPORTED for s > 8
+ * or nrhs != 1): 4 s + 2 launches per outer iteration with the Identity
+ * preconditioner.  g, u and a copy of P are column-major; the k sequential
+ * dot/update pairs of step_3 become one multi-dot sweep d = P g_k, a triangular
+ * solve with the stored m (p_j . g_i = m_ji) in every workgroup, and one update
+ * sweep -- an identity in exact arithmetic.  Iterates agree with the reference
+ * sequence to rounding and do not depend on check_every.  The sweeps move 16 B
+ * per lane: the workspace must be 16-byte aligned (GKOMI_EINVAL otherwise; every
+ * vector inside it then is), and when x is not 16-byte aligned the call runs
+ * gkomi_idr_solve_f64_i32 / _op_f64 instead, as the other fused drivers do -- the
+ * results then are that driver's, nothing else tells the caller. */
+int gkomi_idr_solve_fused_f64_i32(gkomi_stream_t s, int64_t n, int64_t nrhs,
+    int64_t nnz, const int32_t* row_ptrs, const int32_t* col_idxs,
+    const double* vals, int spmv_strategy, int64_t max_row_nnz_hint,
+    gkomi_apply_fn precond, void* precond_ctx, int64_t subspace_dim, double kappa,
+    double* subspace, const double* b, double* x, int64_t max_iters,
+    double reduction_factor, int baseline, int64_t check_every, void* workspace,
+    size_t workspace_bytes, double* host_info);
+int gkomi_idr_solve_fused_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+    gkomi_matrix_apply_fn matrix, void* matrix_ctx, gkomi_apply_fn precond,
+    void* precond_ctx, int64_t subspace_dim, double kappa, double* subspace,
+    const double* b, double* x, int64_t max_iters, double reduction_factor,
+    int baseline, int64_t check_every, void* workspace, size_t workspace_bytes,
+    double* host_info);
+/* Step 3 of the fused driver on its own (diagnostic): the multi-dot sweep and the
+ * projection / update sweep for inner step k.  subspace_vectors (s x ld), g and u
+ * (s columns of ld) are column-major with an even ld >= n and 16-byte aligned, m is
+ * s x s row-major, f_in / f_out hold s values (f_out = f after the step).
+ * Workspace: gkomi_idr_fused_step_3_workspace_bytes(s), 8-byte aligned. */
+size_t gkomi_idr_fused_step_3_workspace_bytes(int64_t subspace_dim);
+int gkomi_idr_fused_step_3_f64(gkomi_stream_t s, int64_t n, int64_t subspace_dim,
+    int64_t k, const double* subspace_vectors, double* g, double* u, int64_t ld,
+    double* m, const double* f_in, double* f_out, double* residual, double* x,
+    void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 // solve_mtx: solve A x = b for MatrixMarket files with the solvers of the hot path, through the gko:: host
 // mirror over libgkomi.so.
 //
-//   solve_mtx --dir data [--executor hip|reference|omp] [--solver cg|fcg|gmres|bicgstab|cgs]
+//   solve_mtx --dir data [--executor hip|reference|omp] [--solver cg|fcg|gmres|bicgstab|cgs|idr]
 //             [--precond none|jacobi|ilu] [--max-iters N] [--reduction R] [--restart K] [--quiet]
 //
 // reads <dir>/A.mtx, <dir>/b.mtx and, when present, <dir>/x0.mtx (else x0 = 0), prints the solution (unless
@@ -117,7 +117,17 @@ int main(int argc, char** argv)
         else if (o.solver == "fcg") solver = build<gko::solver::Fcg<double>>(o, exec, A, precond, &iterations);
         else if (o.solver == "bicgstab") solver = build<gko::solver::Bicgstab<double>>(o, exec, A, precond, &iterations);
         else if (o.solver == "cgs") solver = build<gko::solver::Cgs<double>>(o, exec, A, precond, &iterations);
-        else if (o.solver == "gmres") {
+        else if (o.solver == "idr") {
+            auto factory = gko::solver::Idr<double>::build()
+                               .with_subspace_dim(4u)
+                               .with_kappa(0.7)
+                               .with_deterministic(true)
+                               .with_criteria(gko::stop::Iteration::build().with_max_iters(o.max_iters).on(exec),
+                                              gko::stop::ResidualNorm<double>::build().with_reduction_factor(o.reduction).on(exec));
+            auto idr = precond ? factory.with_generated_preconditioner(precond).on(exec)->generate(A) : factory.on(exec)->generate(A);
+            idr->apply(gko::lend(b), gko::lend(x));
+            iterations = idr->get_last_iteration_count();
+        } else if (o.solver == "gmres") {
             auto factory = gko::solver::Gmres<double>::build()
                                .with_krylov_dim(o.restart)
                                .with_criteria(gko::stop::Iteration::build().with_max_iters(o.max_iters).on(exec),

@@ -177,11 +177,64 @@ def ir_mixed(gk, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=100, reductio
             "inner_iterations": int(info[4]), "inner_capped": int(info[5])}
 
 
+IDR_SUBSPACE_SEED = 15
+
+
+def idr_subspace(subspace_dim, n, device, seed=IDR_SUBSPACE_SEED):
+    """The s x n matrix P that idr_solve draws when it is given none: torch.randn under a fixed seed (the library
+    itself never draws random numbers; it orthonormalises the rows in place)."""
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(seed)
+    return torch.randn((subspace_dim, n), dtype=torch.float64, generator=gen).to(device)
+
+
+def idr_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, subspace_dim=2, kappa=0.7, subspace=None, max_iters=1000,
+              reduction=1e-10, baseline="rhs_norm", strategy=0, max_row_nnz=-1, precond=None, check_every=8,
+              fused=False, matrix=None):
+    """Idr::apply with Combined(Iteration(max_iters), ResidualNorm(reduction, baseline)); `iterations` counts outer
+    iterations (s + 1 applies of A each).  subspace: None or an s x n float64 device tensor, orthonormalised in place.
+    fused (one right-hand side, s <= 8): the driver with 4 s + 2 launches per outer iteration instead of the
+    reference kernel sequence.  matrix: a gkomi.formats object instead of the CSR arrays (solve_op)."""
+    b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
+    nrhs = b2.shape[1]
+    _check_precond(precond, nrhs)
+    if x is None:
+        x = torch.zeros_like(b2)
+    x2 = x.reshape(n, nrhs)
+    assert b2.is_contiguous() and x2.is_contiguous()
+    if subspace is None:
+        subspace = idr_subspace(subspace_dim, n, b.device)
+    assert subspace.dtype == torch.float64 and subspace.is_contiguous() and tuple(subspace.shape) == (subspace_dim, n)
+    nbytes = gk.idr_workspace_bytes(n, nrhs, subspace_dim)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
+    info = np.zeros(2 + 2 * nrhs, dtype=np.float64)
+    stream = torch.cuda.current_stream().cuda_stream
+    fn = precond.fn if precond is not None else None
+    ctx = precond.ctx_ptr if precond is not None else None
+    tail = (fn, ctx, subspace_dim, kappa, subspace, b2, x2, max_iters, reduction, BASELINES[baseline], check_every, ws,
+            nbytes, info)
+    name = "idr_solve_fused" if fused else "idr_solve"
+    if matrix is not None:
+        cb = matrix.callback()
+        getattr(gk, name + "_op_f64")(stream, n, nrhs, cb.fn, cb.ctx_ptr, *tail)
+    else:
+        getattr(gk, name + "_f64_i32")(stream, n, nrhs, int(vals.numel()), row_ptrs, col_idxs, vals, strategy, max_row_nnz,
+                                       *tail)
+    res, base = info[2::2].copy(), info[3::2].copy()
+    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]), "converged": bool(info[1]),
+            "residual_norm": res, "baseline_norm": base,
+            "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
+
+
 def solve_op(gk, solver, matrix, b, x=None, max_iters=1000, reduction=1e-10, baseline="rhs_norm", precond=None,
-             krylov_dim=100, check_every=8, fused=False):
-    """Any solver in {"cg", "gmres", "bicgstab", "fcg", "cgs"} on a system matrix in
+             krylov_dim=100, check_every=8, fused=False, subspace_dim=2, kappa=0.7, subspace=None):
+    """Any solver in {"cg", "gmres", "bicgstab", "fcg", "cgs", "idr"} on a system matrix in
     any format (a gkomi.formats object): the *_solve_op_f64 drivers."""
     n = matrix.nrows
+    if solver == "idr":
+        return idr_solve(gk, n, None, None, None, b, x=x, subspace_dim=subspace_dim, kappa=kappa, subspace=subspace,
+                         max_iters=max_iters, reduction=reduction, baseline=baseline, precond=precond,
+                         check_every=check_every, fused=fused, matrix=matrix)
     b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
     nrhs = b2.shape[1]
     _check_precond(precond, nrhs)

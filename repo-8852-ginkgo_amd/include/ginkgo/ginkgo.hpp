@@ -37,6 +37,7 @@
 #include <istream>
 #include <limits>
 #include <memory>
+#include <random>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -2265,6 +2266,87 @@ GKOMI_KRYLOV_SOLVER(Bicgstab, detail::bicgstab_driver, detail::bicgstab_op_drive
 GKOMI_KRYLOV_SOLVER(Fcg, detail::fcg_driver, detail::fcg_op_driver);
 GKOMI_KRYLOV_SOLVER(Cgs, detail::cgs_driver, detail::cgs_op_driver);
 #undef GKOMI_KRYLOV_SOLVER
+
+// Idr (include/ginkgo/core/solver/idr.hpp): IDR(s) with a real subspace, native drivers of csrc/idr.hip (the fused
+// one for a single right-hand side and s <= 8).  P is filled on the host: std::normal_distribution<>(0, 1) over
+// std::default_random_engine(15) when deterministic, as core/solver/idr.cpp:159-164 does, seeded from
+// std::random_device otherwise; the device orthonormalises its rows.  get_last_iteration_count() counts outer
+// iterations (s + 1 applies of the system matrix each).
+template <typename V = double>
+class Idr : public LinOp {
+public:
+    class Factory : public detail::factory_base<Idr> {
+    public:
+        Factory& with_subspace_dim(size_type s) { subspace_dim_ = s; return *this; }
+        Factory& with_kappa(V k) { kappa_ = k; return *this; }
+        Factory& with_deterministic(bool d) { deterministic_ = d; return *this; }
+        Factory& with_complex_subspace(bool c)
+        {
+            if (c) GKO_NOT_SUPPORTED("Idr: complex subspace (this backend is fp64 only)");
+            return *this;
+        }
+        size_type subspace_dim_{2};  // idr.hpp: defaults 2, 0.7, false
+        V kappa_{0.7};
+        bool deterministic_{false};
+    };
+    static Factory build() { return Factory{}; }
+    std::shared_ptr<const LinOp> get_system_matrix() const { return A_; }
+    std::shared_ptr<const LinOp> get_preconditioner() const { return precond_; }
+    size_type get_subspace_dim() const noexcept { return subspace_dim_; }
+    V get_kappa() const noexcept { return kappa_; }
+    bool get_deterministic() const noexcept { return deterministic_; }
+    bool get_complex_subspace() const noexcept { return false; }
+    int64_t get_last_iteration_count() const noexcept { return last_iters_; }
+    bool has_converged() const noexcept { return last_converged_; }
+protected:
+    friend class detail::factory_base<Idr>;
+    Idr(const Factory* f, std::shared_ptr<const LinOp> A)
+        : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings()), subspace_dim_(f->subspace_dim_), kappa_(f->kappa_),
+          deterministic_(f->deterministic_)
+    {
+        static_assert(std::is_same<V, double>::value, "Idr: fp64 only");
+        if (size_[0] != size_[1]) throw DimensionMismatch(__FILE__, __LINE__, "Idr needs a square system matrix");
+        precond_ = f->precond_ ? f->precond_ : (f->precond_factory_ ? std::shared_ptr<const LinOp>(f->precond_factory_->generate_impl(A_)) : nullptr);
+    }
+    void apply_impl(const LinOp* b, LinOp* x) const override
+    {
+        ::gko::detail::require_device(exec_, "idr::apply");
+        auto db = matrix::detail_fmt::dense(b); auto dx = matrix::detail_fmt::dense(x);
+        const int64_t n = size_[0], nrhs = db->cols(), s = static_cast<int64_t>(subspace_dim_);
+        if (db->get_stride() != static_cast<size_type>(nrhs) || dx->get_stride() != static_cast<size_type>(nrhs)) GKO_NOT_SUPPORTED("solver vectors must be contiguous (stride == #columns)");
+        std::vector<double> host_p(static_cast<size_t>(s * n));
+        std::default_random_engine engine(deterministic_ ? 15u : std::random_device{}());
+        std::normal_distribution<> dist(0.0, 1.0);
+        for (auto& v : host_p) v = dist(engine);
+        array<double> p(exec_, host_p.size());
+        exec_->copy_from(exec_->get_master().get(), host_p.size(), host_p.data(), p.get_data());
+        array<char> ws(exec_, gkomi_idr_workspace_bytes(n, nrhs, s));
+        std::vector<double> info(2 + 2 * nrhs, 0.0);
+        ::gko::detail::precond_callback cb(precond_.get(), exec_, static_cast<size_type>(n), static_cast<size_type>(nrhs));
+        ::gko::detail::system_callback mcb(A_.get(), exec_, static_cast<size_type>(n));
+        auto driver = nrhs == 1 && s <= 8 ? &gkomi_idr_solve_fused_op_f64 : &gkomi_idr_solve_op_f64;
+        GKOMI_CALL(driver(nullptr, n, nrhs, mcb.fn, mcb.ctx, cb.fn, cb.ctx, s, kappa_, p.get_data(), db->get_const_values(), dx->get_values(), settings_.max_iters,
+                          settings_.reduction_factor, detail::baseline_code(settings_.baseline), 8, ws.get_data(), ws.get_num_elems(), info.data()));
+        last_iters_ = static_cast<int64_t>(info[0]);
+        last_converged_ = info[1] != 0.0;
+    }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
+    {
+        auto dx = matrix::detail_fmt::dense(x);
+        auto x_clone = dx->clone();
+        this->apply_impl(b, x_clone.get());
+        dx->scale(matrix::detail_fmt::dense(beta));
+        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
+    }
+    std::shared_ptr<const LinOp> A_;
+    std::shared_ptr<const LinOp> precond_;
+    stop::criterion_settings settings_;
+    size_type subspace_dim_;
+    V kappa_;
+    bool deterministic_;
+    mutable int64_t last_iters_{-1};
+    mutable bool last_converged_{false};
+};
 
 // Bicg (include/ginkgo/core/solver/bicg.hpp): the transposed system matrix is
 // built once at generate (the reference rebuilds it in every apply), and so is

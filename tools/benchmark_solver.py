@@ -39,11 +39,13 @@ def make_preconditioner(gk, name, A, args):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--solvers", default="cg,bicgstab,cgs,fcg,gmres")
+    ap.add_argument("--solvers", default="cg,bicgstab,cgs,fcg,gmres", help="comma-separated: cg, bicgstab, cgs, fcg, gmres, idr")
     ap.add_argument("--preconditioners", default="none")
     ap.add_argument("--max_iters", type=int, default=1000)
     ap.add_argument("--rel_res_goal", type=float, default=1e-6)
     ap.add_argument("--gmres_restart", type=int, default=100)
+    ap.add_argument("--idr_subspace_dim", type=int, default=2)
+    ap.add_argument("--idr_kappa", type=float, default=0.7)
     ap.add_argument("--rhs_generation", default="sinus", choices=["sinus", "1"])
     ap.add_argument("--jacobi_max_block_size", type=int, default=32)
     ap.add_argument("--jacobi_storage", default="0,0", choices=["0,0", "autodetect"])
@@ -87,6 +89,10 @@ def main():
                         elif sname == "gmres":
                             r = solvers.gmres_solve(gk, n, A.row_ptrs, A.col_idxs, A.vals, b, krylov_dim=args.gmres_restart,
                                                     max_iters=args.max_iters, reduction=args.rel_res_goal, precond=pc)
+                        elif sname == "idr":  # iterations = outer iterations, s + 1 applies of A each
+                            r = solvers.idr_solve(gk, n, A.row_ptrs, A.col_idxs, A.vals, b, subspace_dim=args.idr_subspace_dim,
+                                                  kappa=args.idr_kappa, max_iters=args.max_iters, reduction=args.rel_res_goal,
+                                                  precond=pc, fused=args.idr_subspace_dim <= 8, check_every=16)
                         else:
                             r = solvers.krylov_solve(gk, sname, n, A.row_ptrs, A.col_idxs, A.vals, b, max_iters=args.max_iters,
                                                      reduction=args.rel_res_goal, precond=pc, fused=True, check_every=16)
