@@ -564,6 +564,29 @@ int gkomi_hybrid_spmv_f64_i32(gkomi_stream_t s, int64_t nrows, int64_t ncols,
                               int64_t b_stride, double* c, int64_t c_stride,
                               const double* alpha, const double* beta);
 
+/* ---- Fbcsr: fixed-block CSR (core/matrix/fbcsr_kernels.hpp; csrc/fbcsr.hip) ------
+ * row_ptrs[nbrows + 1], col_idxs[nbnz] (block columns), vals[nbnz * bs * bs]; a
+ * block is column-major: entry (ib, jb) of block z at z*bs*bs + ib + jb*bs
+ * (acc::block_col_major, reference/matrix/fbcsr_kernels.cpp:84-85).  Any bs >= 1.
+ * fbcsr::spmv / advanced_spmv (reference/matrix/fbcsr_kernels.cpp:72-151):
+ * alpha == beta == NULL: c = A b; otherwise c = alpha A b + beta c (c *= beta, then
+ * += (alpha * val) * b).  Bit-identical to the reference loops: per scalar row the
+ * terms are added one by one over the row's blocks in storage order (sorted or
+ * not) and inside a block over its columns left to right.  Empty block rows get 0
+ * (beta * c).  vals must be 8-byte aligned; col_idxs / vals may be NULL when
+ * nbnz == 0. */
+int gkomi_fbcsr_spmv_f64_i32(gkomi_stream_t s, int64_t nbrows, int64_t nbcols,
+                             int64_t bs, int64_t nbnz, const int32_t* row_ptrs,
+                             const int32_t* col_idxs, const double* vals,
+                             const double* b, int64_t b_stride, int64_t nrhs,
+                             double* c, int64_t c_stride, const double* alpha,
+                             const double* beta);
+/* How gkomi_fbcsr_spmv_f64_i32 cuts the work for this block size (host values):
+ * the block rows one workgroup owns and the blocks of one LDS tile (0: bs > 16,
+ * one thread per scalar row without tiles). */
+int gkomi_fbcsr_spmv_geometry(int64_t bs, int64_t* host_block_rows_per_workgroup,
+                              int64_t* host_blocks_per_tile);
+
 /* ---- index components and format conversions (bit-exact) ---------------- */
 /* components::prefix_sum: exclusive, in place
  * (reference/components/prefix_sum_kernels.cpp:43-53) */
@@ -641,6 +664,77 @@ int gkomi_hybrid_ell_width_i32(gkomi_stream_t s, const int32_t* row_ptrs,
                                int64_t nrows, int kind, double percent,
                                double ratio, int64_t num_columns,
                                int64_t* host_result);
+
+/* csr::convert_to_fbcsr (reference/matrix/csr_kernels.cpp:464-530; the same loop
+ * is fbcsr::fill_in_matrix_data, reference/matrix/fbcsr_kernels.cpp:158-209, for
+ * row-major sorted, duplicate-free triplets).  nrows and ncols must be multiples
+ * of bs (GKOMI_EINVAL otherwise, as Fbcsr's constructor).  Two calls with the same
+ * workspace (gkomi_csr_convert_to_fbcsr_workspace_bytes(nnz) bytes, left alone in
+ * between): out_col_idxs == out_vals == NULL counts -- out_row_ptrs[nrows/bs + 1]
+ * and *host_nbnz are written (blocking); with out_col_idxs[*host_nbnz] and
+ * out_vals[*host_nbnz * bs * bs] the blocks are filled: block columns ascending,
+ * entries not present in a touched block explicit zeros. */
+size_t gkomi_csr_convert_to_fbcsr_workspace_bytes(int64_t nnz);
+int gkomi_csr_convert_to_fbcsr_i32(gkomi_stream_t s, int64_t nrows, int64_t ncols,
+                                   int64_t bs, int64_t nnz,
+                                   const int32_t* row_ptrs,
+                                   const int32_t* col_idxs, const double* vals,
+                                   int32_t* out_row_ptrs, int32_t* out_col_idxs,
+                                   double* out_vals, int64_t* host_nbnz,
+                                   void* workspace, size_t workspace_bytes);
+/* fbcsr::convert_to_csr (reference/matrix/fbcsr_kernels.cpp:252-304): each scalar
+ * row lists its entries block by block in storage order, explicit zeros included;
+ * csr_row_ptrs[nbrows * bs + 1], csr_col_idxs / csr_vals[nbnz * bs * bs] */
+int gkomi_fbcsr_convert_to_csr_i32(gkomi_stream_t s, int64_t nbrows, int64_t bs,
+                                   int64_t nbnz, const int32_t* row_ptrs,
+                                   const int32_t* col_idxs, const double* vals,
+                                   int32_t* csr_row_ptrs, int32_t* csr_col_idxs,
+                                   double* csr_vals);
+/* fbcsr::fill_in_dense (reference/matrix/fbcsr_kernels.cpp:216-245): writes the
+ * stored entries into the row-major result (the caller zero-fills it first, as
+ * core/matrix/fbcsr.cpp does) */
+int gkomi_fbcsr_fill_in_dense_f64_i32(gkomi_stream_t s, int64_t nbrows,
+                                      int64_t nbcols, int64_t bs, int64_t nbnz,
+                                      const int32_t* row_ptrs,
+                                      const int32_t* col_idxs,
+                                      const double* vals, double* result,
+                                      int64_t result_stride);
+/* fbcsr::transpose (reference/matrix/fbcsr_kernels.cpp:310-388): block columns
+ * become block rows, within one in the order of the original block rows, every
+ * block transposed; t_row_ptrs[nbcols + 1] */
+size_t gkomi_fbcsr_transpose_workspace_bytes(int64_t nbnz);
+int gkomi_fbcsr_transpose_f64_i32(gkomi_stream_t s, int64_t nbrows,
+                                  int64_t nbcols, int64_t bs, int64_t nbnz,
+                                  const int32_t* row_ptrs,
+                                  const int32_t* col_idxs, const double* vals,
+                                  int32_t* t_row_ptrs, int32_t* t_col_idxs,
+                                  double* t_vals, void* workspace,
+                                  size_t workspace_bytes);
+/* fbcsr::is_sorted_by_column_index / sort_by_column_index
+ * (reference/matrix/fbcsr_kernels.cpp:406-425, :434-483): the sort moves whole
+ * blocks with their column index, in place (stable; workspace:
+ * gkomi_fbcsr_sort_workspace_bytes).  is_sorted needs 4 bytes and blocks. */
+int gkomi_fbcsr_is_sorted_by_column_index_i32(gkomi_stream_t s, int64_t nbrows,
+                                              const int32_t* row_ptrs,
+                                              const int32_t* col_idxs,
+                                              void* workspace,
+                                              size_t workspace_bytes,
+                                              int* host_is_sorted);
+size_t gkomi_fbcsr_sort_workspace_bytes(int64_t nbnz, int64_t bs);
+int gkomi_fbcsr_sort_by_column_index_f64_i32(gkomi_stream_t s, int64_t nbrows,
+                                             int64_t bs, int64_t nbnz,
+                                             const int32_t* row_ptrs,
+                                             int32_t* col_idxs, double* vals,
+                                             void* workspace,
+                                             size_t workspace_bytes);
+/* fbcsr::extract_diagonal (reference/matrix/fbcsr_kernels.cpp:490-522):
+ * diag[min(nbrows, nbcols) * bs]; rows without a stored diagonal block are not
+ * written */
+int gkomi_fbcsr_extract_diagonal_f64_i32(gkomi_stream_t s, int64_t nbrows,
+                                         int64_t nbcols, int64_t bs,
+                                         const int32_t* row_ptrs,
+                                         const int32_t* col_idxs,
+                                         const double* vals, double* diag);
 
 /* ---- block-Jacobi preconditioner (core/preconditioner/jacobi_kernels.hpp:50-190)
  * fp64 block storage (precision_reduction(0,0)) or adaptive precision (the
@@ -1434,6 +1528,12 @@ typedef struct gkomi_hybrid_ctx {
     const int32_t* coo_col_idxs;
     const double* coo_vals;
 } gkomi_hybrid_ctx;
+typedef struct gkomi_fbcsr_ctx {
+    int64_t nbrows, nbcols, bs, nbnz;
+    const int32_t* row_ptrs;
+    const int32_t* col_idxs;
+    const double* vals;
+} gkomi_fbcsr_ctx;
 int gkomi_csr_matrix_apply_cb(void* ctx, gkomi_stream_t s, int64_t nrhs,
                               const double* alpha, const double* b,
                               int64_t b_stride, const double* beta, double* c,
@@ -1458,6 +1558,11 @@ int gkomi_hybrid_matrix_apply_cb(void* ctx, gkomi_stream_t s, int64_t nrhs,
                                  const double* alpha, const double* b,
                                  int64_t b_stride, const double* beta,
                                  double* c, int64_t c_stride);
+/* Fbcsr (gkomi_fbcsr_spmv_f64_i32) */
+int gkomi_fbcsr_matrix_apply_cb(void* ctx, gkomi_stream_t s, int64_t nrhs,
+                                const double* alpha, const double* b,
+                                int64_t b_stride, const double* beta,
+                                double* c, int64_t c_stride);
 /* The solver drivers with the system matrix behind a callback (config 4 of
  * BASELINE.json runs GMRES on ELL / SELL-P).  Same loops, same arguments as the
  * CSR entry points; gkomi_cg_solve_op_f64 runs the reference kernel sequence,

@@ -1,4 +1,4 @@
-"""gko::matrix::{Csr, Coo, Ell, Sellp, Hybrid} over the C ABI for Python callers
+"""gko::matrix::{Csr, Coo, Ell, Sellp, Hybrid, Fbcsr} over the C ABI for Python callers
 (tests, bench, tools/benchmark_*.py): device arrays are torch tensors, every
 conversion and apply is a gkomi_* kernel -- no CPU fallback.  Conversions
 follow core/matrix/csr.cpp:257-405 (the sizes the reference reads back with
@@ -31,6 +31,8 @@ SellpCtx = _ctx_type("SellpCtx", [("nrows", _i64), ("ncols", _i64), ("slice_size
                                   ("slice_lengths", _ptr), ("col_idxs", _ptr), ("vals", _ptr)])
 CooCtx = _ctx_type("CooCtx", [("nrows", _i64), ("ncols", _i64), ("nnz", _i64), ("row_idxs", _ptr), ("col_idxs", _ptr),
                               ("vals", _ptr)])
+FbcsrCtx = _ctx_type("FbcsrCtx", [("nbrows", _i64), ("nbcols", _i64), ("bs", _i64), ("nbnz", _i64), ("row_ptrs", _ptr),
+                                  ("col_idxs", _ptr), ("vals", _ptr)])
 HybridCtx = _ctx_type("HybridCtx", [("nrows", _i64), ("ncols", _i64), ("ell_num_stored_per_row", _i64),
                                     ("ell_stride", _i64), ("ell_col_idxs", _ptr), ("ell_vals", _ptr), ("coo_nnz", _i64),
                                     ("coo_row_idxs", _ptr), ("coo_col_idxs", _ptr), ("coo_vals", _ptr)])
@@ -244,7 +246,7 @@ class Csr:
             if code == self.strategy:
                 return self
             return Csr(self.gk, self.nrows, self.ncols, self.row_ptrs, self.col_idxs, self.vals, code, self.split)
-        return {"coo": Coo, "ell": Ell, "sellp": Sellp, "hybrid": Hybrid}[fmt].from_csr(self, **kw)
+        return {"coo": Coo, "ell": Ell, "sellp": Sellp, "hybrid": Hybrid, "fbcsr": Fbcsr}[fmt].from_csr(self, **kw)
 
 
 class Csr64:
@@ -435,6 +437,106 @@ class Ell:
                                  self.col_idxs, self.vals, b, b.stride(0), x, x.stride(0), _scalar(dv, alpha),
                                  _scalar(dv, beta))
         return x
+
+
+class Fbcsr:
+    """gko::matrix::Fbcsr<double, int32>: row_ptrs[nbrows + 1], col_idxs[nbnz] (block columns),
+    vals[nbnz * bs * bs] with column-major blocks"""
+    name = "fbcsr"
+
+    def __init__(self, gk, nbrows, nbcols, bs, row_ptrs, col_idxs, vals):
+        self.gk, self.nbrows, self.nbcols, self.bs = gk, int(nbrows), int(nbcols), int(bs)
+        self.nrows, self.ncols = self.nbrows * self.bs, self.nbcols * self.bs
+        self.row_ptrs, self.col_idxs, self.vals = row_ptrs, col_idxs, vals
+        self.nbnz = int(col_idxs.numel())
+
+    @classmethod
+    def from_host(cls, gk, nbrows, nbcols, bs, row_ptrs, col_idxs, vals, device="cuda:0"):
+        d = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, dtype=t)).to(device)
+        return cls(gk, nbrows, nbcols, bs, d(row_ptrs, np.int32), d(col_idxs, np.int32), d(vals, np.float64))
+
+    @classmethod
+    def from_csr(cls, csr, block_size):
+        """Csr::convert_to(Fbcsr*) (core/matrix/csr.cpp): count the blocks, read their number back, fill"""
+        gk, dv, bs = csr.gk, csr.vals.device, int(block_size)
+        s = _stream(csr.vals)
+        # (a block size that does not divide the matrix is the count call's GKOMI_EINVAL)
+        nbrows, nbcols = csr.nrows // max(bs, 1), csr.ncols // max(bs, 1)
+        nb = gk.csr_convert_to_fbcsr_workspace_bytes(csr.nnz)
+        ws = torch.empty(max(nb, 8), dtype=U8, device=dv)
+        ptrs = torch.empty(nbrows + 1, dtype=I32, device=dv)
+        nbnz = ctypes.c_int64(0)
+        gk.csr_convert_to_fbcsr_i32(s, csr.nrows, csr.ncols, bs, csr.nnz, csr.row_ptrs, csr.col_idxs, csr.vals, ptrs,
+                                    None, None, ctypes.addressof(nbnz), ws, nb)
+        cols = torch.empty(nbnz.value, dtype=I32, device=dv)
+        vals = torch.empty(nbnz.value * bs * bs, dtype=F64, device=dv)
+        if nbnz.value:
+            gk.csr_convert_to_fbcsr_i32(s, csr.nrows, csr.ncols, bs, csr.nnz, csr.row_ptrs, csr.col_idxs, csr.vals, ptrs,
+                                        cols, vals, ctypes.addressof(nbnz), ws, nb)
+        return cls(gk, nbrows, nbcols, bs, ptrs, cols, vals)
+
+    def storage_bytes(self):
+        return 4 * (self.nbrows + 1) + (8 * self.bs * self.bs + 4) * self.nbnz
+
+    def callback(self):
+        ctx = FbcsrCtx(self.nbrows, self.nbcols, self.bs, self.nbnz, self.row_ptrs.data_ptr(), self.col_idxs.data_ptr(),
+                       self.vals.data_ptr())
+        return MatrixCallback(self.gk, "gkomi_fbcsr_matrix_apply_cb", ctx, self)
+
+    def apply(self, b, x, alpha=None, beta=None):
+        dv = self.vals.device
+        self.gk.fbcsr_spmv_f64_i32(_stream(self.vals), self.nbrows, self.nbcols, self.bs, self.nbnz, self.row_ptrs,
+                                   self.col_idxs, self.vals, b, b.stride(0), b.shape[1], x, x.stride(0),
+                                   _scalar(dv, alpha), _scalar(dv, beta))
+        return x
+
+    def to_csr(self):
+        dv, n = self.vals.device, self.nbnz * self.bs * self.bs
+        ptrs = torch.empty(self.nrows + 1, dtype=I32, device=dv)
+        cols, vals = torch.empty(n, dtype=I32, device=dv), torch.empty(n, dtype=F64, device=dv)
+        self.gk.fbcsr_convert_to_csr_i32(_stream(self.vals), self.nbrows, self.bs, self.nbnz, self.row_ptrs, self.col_idxs,
+                                         self.vals, ptrs, cols, vals)
+        return Csr(self.gk, self.nrows, self.ncols, ptrs, cols, vals)
+
+    def to_dense(self):
+        out = torch.zeros((self.nrows, max(self.ncols, 1)), dtype=F64, device=self.vals.device)
+        self.gk.fbcsr_fill_in_dense_f64_i32(_stream(self.vals), self.nbrows, self.nbcols, self.bs, self.nbnz, self.row_ptrs,
+                                            self.col_idxs, self.vals, out, out.stride(0))
+        return out[:, :self.ncols]
+
+    def transpose(self):
+        dv = self.vals.device
+        nb = self.gk.fbcsr_transpose_workspace_bytes(self.nbnz)
+        ws = torch.empty(max(nb, 8), dtype=U8, device=dv)
+        ptrs = torch.empty(self.nbcols + 1, dtype=I32, device=dv)
+        cols, vals = torch.empty_like(self.col_idxs), torch.empty_like(self.vals)
+        self.gk.fbcsr_transpose_f64_i32(_stream(self.vals), self.nbrows, self.nbcols, self.bs, self.nbnz, self.row_ptrs,
+                                        self.col_idxs, self.vals, ptrs, cols, vals, ws, nb)
+        return Fbcsr(self.gk, self.nbcols, self.nbrows, self.bs, ptrs, cols, vals)
+
+    def is_sorted_by_column_index(self):
+        ws = torch.empty(8, dtype=U8, device=self.vals.device)
+        flag = ctypes.c_int(0)
+        self.gk.fbcsr_is_sorted_by_column_index_i32(_stream(self.vals), self.nbrows, self.row_ptrs, self.col_idxs, ws, 8,
+                                                    ctypes.addressof(flag))
+        return bool(flag.value)
+
+    def sort_by_column_index(self):
+        """in place, like the reference"""
+        nb = self.gk.fbcsr_sort_workspace_bytes(self.nbnz, self.bs)
+        ws = torch.empty(max(nb, 8), dtype=U8, device=self.vals.device)
+        self.gk.fbcsr_sort_by_column_index_f64_i32(_stream(self.vals), self.nbrows, self.bs, self.nbnz, self.row_ptrs,
+                                                   self.col_idxs, self.vals, ws, nb)
+        return self
+
+    def extract_diagonal(self, out=None):
+        """the reference writes only where a diagonal block is stored; `out` (else zeros) keeps the rest"""
+        n = min(self.nbrows, self.nbcols) * self.bs
+        if out is None:
+            out = torch.zeros(n, dtype=F64, device=self.vals.device)
+        self.gk.fbcsr_extract_diagonal_f64_i32(_stream(self.vals), self.nbrows, self.nbcols, self.bs, self.row_ptrs,
+                                               self.col_idxs, self.vals, out)
+        return out
 
 
 class Sellp:

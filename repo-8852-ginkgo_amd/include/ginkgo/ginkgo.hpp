@@ -854,6 +854,8 @@ class Coo;
 template <typename V, typename I>
 class Ell;
 template <typename V, typename I>
+class Fbcsr;
+template <typename V, typename I>
 class Sellp;
 template <typename V, typename I>
 class Hybrid;
@@ -1063,6 +1065,7 @@ public:
     void convert_to(Ell<V, I>* result) const;
     void convert_to(Sellp<V, I>* result) const;
     void convert_to(Hybrid<V, I>* result) const;
+    void convert_to(Fbcsr<V, I>* result) const;   // the block size is the target's (core/matrix/csr.cpp)
     std::unique_ptr<Csr> transpose() const
     {
         detail::require_device(exec_, "csr::transpose");
@@ -1402,6 +1405,131 @@ protected:
     std::shared_ptr<strategy_type> strategy_;
 };
 
+// include/ginkgo/core/matrix/fbcsr.hpp: fixed-block CSR, blocks column-major (csrc/fbcsr.hip)
+template <typename V = double, typename I = int32>
+class Fbcsr : public LinOp {
+    static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "Fbcsr: <double, int32> only");
+public:
+    using mat_data = matrix_data<V, I>;
+    // fbcsr.hpp: create(exec, block_size), create(exec, size, num_nonzeros, block_size)
+    static std::unique_ptr<Fbcsr> create(std::shared_ptr<const Executor> exec, int block_size = 1)
+    {
+        return std::unique_ptr<Fbcsr>(new Fbcsr(std::move(exec), dim<2>{}, 0, block_size));
+    }
+    static std::unique_ptr<Fbcsr> create(std::shared_ptr<const Executor> exec, const dim<2>& size, size_type num_nonzeros, int block_size)
+    {
+        return std::unique_ptr<Fbcsr>(new Fbcsr(std::move(exec), size, num_nonzeros, block_size));
+    }
+    int get_block_size() const noexcept { return bs_; }
+    void set_block_size(int block_size) { check_block_size(block_size, size_); bs_ = block_size; }
+    I get_num_block_rows() const noexcept { return static_cast<I>(size_[0] / bs_); }
+    I get_num_block_cols() const noexcept { return static_cast<I>(size_[1] / bs_); }
+    size_type get_num_stored_blocks() const noexcept { return col_idxs_.get_num_elems(); }
+    size_type get_num_stored_elements() const noexcept { return values_.get_num_elems(); }
+    V* get_values() noexcept { return values_.get_data(); }
+    const V* get_const_values() const noexcept { return values_.get_const_data(); }
+    I* get_col_idxs() noexcept { return col_idxs_.get_data(); }
+    const I* get_const_col_idxs() const noexcept { return col_idxs_.get_const_data(); }
+    I* get_row_ptrs() noexcept { return row_ptrs_.get_data(); }
+    const I* get_const_row_ptrs() const noexcept { return row_ptrs_.get_const_data(); }
+    // Fbcsr::read(matrix_data) (core/matrix/fbcsr.cpp; fbcsr::fill_in_matrix_data is the loop of csr::convert_to_fbcsr):
+    // row-major sorted, duplicate-free entries, dimensions divisible by the block size
+    void read(const mat_data& data)
+    {
+        auto csr = Csr<V, I>::create(exec_);
+        csr->read(data);
+        csr->convert_to(this);
+    }
+    void convert_to(Csr<V, I>* result) const
+    {
+        detail::require_device(exec_, "fbcsr::convert_to_csr");
+        const size_type nnz = get_num_stored_elements();
+        array<I> rp(exec_, size_[0] + 1), ci(exec_, nnz);
+        array<V> v(exec_, nnz);
+        GKOMI_CALL(gkomi_fbcsr_convert_to_csr_i32(nullptr, get_num_block_rows(), bs_, get_num_stored_blocks(), get_const_row_ptrs(), get_const_col_idxs(), get_const_values(),
+                                                  rp.get_data(), ci.get_data(), v.get_data()));
+        result->adopt(size_, std::move(rp), std::move(ci), std::move(v));
+    }
+    void convert_to(Dense<V>* result) const
+    {
+        detail::require_device(exec_, "fbcsr::fill_in_dense");
+        auto tmp = Dense<V>::create(exec_, size_);
+        tmp->fill(V{});
+        GKOMI_CALL(gkomi_fbcsr_fill_in_dense_f64_i32(nullptr, get_num_block_rows(), get_num_block_cols(), bs_, get_num_stored_blocks(), get_const_row_ptrs(), get_const_col_idxs(),
+                                                     get_const_values(), tmp->get_values(), tmp->get_stride()));
+        result->copy_from(tmp.get());
+    }
+    std::unique_ptr<Fbcsr> transpose() const
+    {
+        detail::require_device(exec_, "fbcsr::transpose");
+        auto t = Fbcsr::create(exec_, gko::transpose(size_), get_num_stored_elements(), bs_);
+        array<char> ws(exec_, gkomi_fbcsr_transpose_workspace_bytes(get_num_stored_blocks()) + 8);
+        GKOMI_CALL(gkomi_fbcsr_transpose_f64_i32(nullptr, get_num_block_rows(), get_num_block_cols(), bs_, get_num_stored_blocks(), get_const_row_ptrs(), get_const_col_idxs(),
+                                                 get_const_values(), t->get_row_ptrs(), t->get_col_idxs(), t->get_values(), ws.get_data(), ws.get_num_elems()));
+        return t;
+    }
+    std::unique_ptr<Fbcsr> conj_transpose() const { return transpose(); }
+    void sort_by_column_index()
+    {
+        detail::require_device(exec_, "fbcsr::sort_by_column_index");
+        array<char> ws(exec_, gkomi_fbcsr_sort_workspace_bytes(get_num_stored_blocks(), bs_) + 8);
+        GKOMI_CALL(gkomi_fbcsr_sort_by_column_index_f64_i32(nullptr, get_num_block_rows(), bs_, get_num_stored_blocks(), get_const_row_ptrs(), get_col_idxs(), get_values(),
+                                                            ws.get_data(), ws.get_num_elems()));
+    }
+    bool is_sorted_by_column_index() const
+    {
+        detail::require_device(exec_, "fbcsr::is_sorted_by_column_index");
+        array<char> ws(exec_, 8);
+        int sorted = 1;
+        GKOMI_CALL(gkomi_fbcsr_is_sorted_by_column_index_i32(nullptr, get_num_block_rows(), get_const_row_ptrs(), get_const_col_idxs(), ws.get_data(), ws.get_num_elems(), &sorted));
+        return sorted != 0;
+    }
+    // the diagonal as an array of min(rows, cols) values, zero where no diagonal block is stored (the mirror has no
+    // matrix::Diagonal; Csr's diagonal is read the same way, by the ABI call, where Jacobi needs it)
+    array<V> extract_diagonal() const
+    {
+        detail::require_device(exec_, "fbcsr::extract_diagonal");
+        array<V> diag(exec_, std::min(size_[0], size_[1]));
+        diag.fill(V{});
+        GKOMI_CALL(gkomi_fbcsr_extract_diagonal_f64_i32(nullptr, get_num_block_rows(), get_num_block_cols(), bs_, get_const_row_ptrs(), get_const_col_idxs(), get_const_values(),
+                                                        diag.get_data()));
+        return diag;
+    }
+    // arrays handed over by kernels that size their own outputs
+    void adopt(const dim<2>& size, int block_size, array<I> rp, array<I> ci, array<V> v)
+    {
+        check_block_size(block_size, size);
+        bs_ = block_size; row_ptrs_ = std::move(rp); col_idxs_ = std::move(ci); values_ = std::move(v); set_size(size);
+    }
+protected:
+    static void check_block_size(int block_size, const dim<2>& size)
+    {
+        if (block_size < 1 || size[0] % block_size != 0 || size[1] % block_size != 0)
+            throw BadDimension(__FILE__, __LINE__, "Fbcsr: the block size does not divide the size");
+    }
+    Fbcsr(std::shared_ptr<const Executor> exec, const dim<2>& size, size_type num_nonzeros, int block_size)
+        : LinOp(exec, size), values_(exec, num_nonzeros), col_idxs_(exec, block_size > 0 ? num_nonzeros / (static_cast<size_type>(block_size) * block_size) : 0),
+          row_ptrs_(exec, block_size > 0 ? size[0] / block_size + 1 : 1), bs_(block_size)
+    {
+        check_block_size(block_size, size);
+        row_ptrs_.fill(I{});
+    }
+    void run(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const
+    {
+        detail::require_device(exec_, "fbcsr::spmv");
+        auto db = detail_fmt::dense(b); auto dx = detail_fmt::dense(x);
+        GKOMI_CALL(gkomi_fbcsr_spmv_f64_i32(nullptr, get_num_block_rows(), get_num_block_cols(), bs_, get_num_stored_blocks(), get_const_row_ptrs(), get_const_col_idxs(),
+                                            get_const_values(), db->get_const_values(), db->get_stride(), db->cols(), dx->get_values(), dx->get_stride(),
+                                            alpha ? detail_fmt::dense(alpha)->get_const_values() : nullptr, beta ? detail_fmt::dense(beta)->get_const_values() : nullptr));
+    }
+    void apply_impl(const LinOp* b, LinOp* x) const override { run(nullptr, b, nullptr, x); }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override { run(alpha, b, beta, x); }
+    array<V> values_;
+    array<I> col_idxs_;
+    array<I> row_ptrs_;
+    int bs_;
+};
+
 // conversions (core/matrix/csr.cpp:257-405)
 template <typename V, typename I>
 void Csr<V, I>::convert_to(Coo<V, I>* result) const
@@ -1458,6 +1586,27 @@ void Csr<V, I>::convert_to(Hybrid<V, I>* result) const
     result->set_size(size_);
     GKOMI_CALL(gkomi_csr_convert_to_hybrid_f64_i32(nullptr, size_[0], get_const_row_ptrs(), get_const_col_idxs(), get_const_values(), crp.get_const_data(), ell_lim, size_[0],
                                                    result->ell_->get_col_idxs(), result->ell_->get_values(), result->coo_->get_row_idxs(), result->coo_->get_col_idxs(), result->coo_->get_values()));
+}
+
+template <typename V, typename I>
+void Csr<V, I>::convert_to(Fbcsr<V, I>* result) const
+{
+    detail::require_device(exec_, "csr::convert_to_fbcsr");
+    const int bs = result->get_block_size();
+    const size_type nnz = get_num_stored_elements();
+    auto rexec = result->get_executor();
+    array<char> ws(exec_, gkomi_csr_convert_to_fbcsr_workspace_bytes(nnz) + 8);
+    array<I> rp(rexec, bs > 0 ? size_[0] / bs + 1 : 1);
+    int64_t nbnz = 0;
+    GKOMI_CALL(gkomi_csr_convert_to_fbcsr_i32(nullptr, size_[0], size_[1], bs, nnz, get_const_row_ptrs(), get_const_col_idxs(), get_const_values(), rp.get_data(), nullptr, nullptr,
+                                              &nbnz, ws.get_data(), ws.get_num_elems()));
+    array<I> ci(rexec, static_cast<size_type>(nbnz));
+    array<V> v(rexec, static_cast<size_type>(nbnz) * bs * bs);
+    if (nbnz > 0) {
+        GKOMI_CALL(gkomi_csr_convert_to_fbcsr_i32(nullptr, size_[0], size_[1], bs, nnz, get_const_row_ptrs(), get_const_col_idxs(), get_const_values(), rp.get_data(), ci.get_data(),
+                                                  v.get_data(), &nbnz, ws.get_data(), ws.get_num_elems()));
+    }
+    result->adopt(size_, bs, std::move(rp), std::move(ci), std::move(v));
 }
 
 }  // namespace matrix
@@ -1747,13 +1896,15 @@ struct matrix_callback {
 };
 // The system matrix of a solver as (gkomi_matrix_apply_fn, context): Ell and
 // Sellp go by the library's own callbacks + records, which the fused drivers
-// recognise (SpMV with the dot-product epilogue, csrc/formats.hip); every other
-// LinOp goes through matrix_callback.
+// recognise (SpMV with the dot-product epilogue, csrc/formats.hip), Fbcsr by its
+// own callback + record (no epilogue: the drivers follow it with their partials
+// kernel); every other LinOp goes through matrix_callback.
 struct system_callback {
     matrix_callback generic;
     gkomi_csr_ctx csr{};
     gkomi_ell_ctx ell{};
     gkomi_sellp_ctx sellp{};
+    gkomi_fbcsr_ctx fbcsr{};
     gkomi_matrix_apply_fn fn;
     void* ctx;
     system_callback(const LinOp* A, std::shared_ptr<const Executor> exec, size_type n)
@@ -1794,6 +1945,16 @@ struct system_callback {
             sellp.vals = sp->get_const_values();
             fn = &gkomi_sellp_matrix_apply_cb;
             ctx = &sellp;
+        } else if (auto fb = dynamic_cast<const matrix::Fbcsr<double, int32>*>(A)) {
+            fbcsr.nbrows = fb->get_num_block_rows();
+            fbcsr.nbcols = fb->get_num_block_cols();
+            fbcsr.bs = fb->get_block_size();
+            fbcsr.nbnz = static_cast<int64_t>(fb->get_num_stored_blocks());
+            fbcsr.row_ptrs = fb->get_const_row_ptrs();
+            fbcsr.col_idxs = fb->get_const_col_idxs();
+            fbcsr.vals = fb->get_const_values();
+            fn = &gkomi_fbcsr_matrix_apply_cb;
+            ctx = &fbcsr;
         }
     }
     system_callback(const system_callback&) = delete;

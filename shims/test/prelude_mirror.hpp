@@ -11,6 +11,21 @@ class stopping_status {
 public:
     uint8 data_{0};
 };
+namespace matrix {
+// include/ginkgo/core/matrix/diagonal.hpp, as far as the extract_diagonal kernels use it: n values
+template <typename V = double>
+class Diagonal {
+public:
+    static std::unique_ptr<Diagonal> create(std::shared_ptr<const Executor> exec, size_type n) { return std::unique_ptr<Diagonal>(new Diagonal(std::move(exec), n)); }
+    dim<2> get_size() const noexcept { return dim<2>(values_.get_num_elems(), values_.get_num_elems()); }
+    V* get_values() noexcept { return values_.get_data(); }
+    const V* get_const_values() const noexcept { return values_.get_const_data(); }
+    std::shared_ptr<const Executor> get_executor() const noexcept { return values_.get_executor(); }
+private:
+    Diagonal(std::shared_ptr<const Executor> exec, size_type n) : values_(std::move(exec), n) {}
+    array<V> values_;
+};
+}  // namespace matrix
 namespace kernels {
 namespace hip {
 // the mirror's Csr keeps the statistic itself (gkomi_bindings.hpp has the reference-tree version)
