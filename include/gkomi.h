@@ -1077,6 +1077,63 @@ int gkomi_csr_transpose_f64_i32(gkomi_stream_t s, int64_t nrows, int64_t ncols,
                                 double* t_vals, void* workspace,
                                 size_t workspace_bytes);
 
+/* ---- CSR times CSR, CSR plus CSR (core/matrix/csr.cpp:184-233) ---------- */
+/* csr::spgemm (reference/matrix/csr_kernels.cpp:209-252), C = A B, and with
+ * device scalars alpha, beta and a matrix D csr::advanced_spgemm (:257-307),
+ * C = alpha A B + beta D.  alpha == beta == d_row_ptrs == NULL selects the
+ * simple form (the d_* sizes are then ignored); only some of the three is
+ * GKOMI_EINVAL, as are a_ncols != b_nrows and a D that is not a_nrows x b_ncols.
+ *
+ * Two calls with the same workspace (gkomi_csr_spgemm_workspace_bytes(a_nrows,
+ * b_ncols) bytes, left alone in between), nothing allocates:
+ *  - c_col_idxs == c_vals == NULL counts: c_row_ptrs[a_nrows + 1] and
+ *    *host_c_nnz are written (blocking).  Row lengths are summed in 64 bits; if
+ *    nnz(C) exceeds INT32_MAX, *host_c_nnz holds the true count and the call
+ *    returns GKOMI_ENOTSUPPORTED.
+ *  - with c_col_idxs / c_vals[*host_c_nnz] and the c_row_ptrs of the first call
+ *    the entries are filled (not blocking).
+ * The result is bit for bit the reference's: row i holds one entry per distinct
+ * column reached through row i of A (and row i of D), columns ascending whether
+ * or not A, B, D are sorted, entries that cancel to zero stay stored; a value
+ * starts at +0.0 and receives beta * d for D's row in storage order, then, for
+ * each nonzero a of A's row in storage order and each nonzero b of that row of
+ * B in storage order, (alpha * a) * b (a * b in the simple form), every product
+ * and every sum rounded once.  Repeated columns are legal everywhere.
+ * Speed: rows are spread over groups of lanes as long as every row of B and D
+ * is strictly ascending; otherwise (unsorted rows or repeated columns in B or
+ * D) one lane per row walks the reference loop -- exact, but slow: sort B first
+ * where only the order is at fault. */
+size_t gkomi_csr_spgemm_workspace_bytes(int64_t a_nrows, int64_t b_ncols);
+int gkomi_csr_spgemm_f64_i32(
+    gkomi_stream_t s, int64_t a_nrows, int64_t a_ncols, int64_t a_nnz,
+    const int32_t* a_row_ptrs, const int32_t* a_col_idxs, const double* a_vals,
+    int64_t b_nrows, int64_t b_ncols, int64_t b_nnz, const int32_t* b_row_ptrs,
+    const int32_t* b_col_idxs, const double* b_vals, const double* alpha,
+    const double* beta, int64_t d_nrows, int64_t d_ncols, int64_t d_nnz,
+    const int32_t* d_row_ptrs, const int32_t* d_col_idxs, const double* d_vals,
+    int32_t* c_row_ptrs, int32_t* c_col_idxs, double* c_vals,
+    int64_t* host_c_nnz, void* workspace, size_t workspace_bytes);
+/* The row bins of the kernel above by u = the number of products of a row
+ * (+ the length of D's row): u <= out[0] eight lanes and a 64-entry LDS table
+ * per row, <= out[1] a wave and 1024 entries, <= out[2] a workgroup and 4096
+ * entries, beyond a dense marker array of b_ncols entries in the workspace. */
+int gkomi_csr_spgemm_bins(int64_t out[3]);
+/* csr::spgeam (reference/matrix/csr_kernels.cpp:313-357), C = alpha A + beta B
+ * by the two-pointer merge of reference/components/csr_spgeam.hpp:58-104, one
+ * lane per row: each value is alpha * a + beta * b with a literal 0.0 for the
+ * missing side (still multiplied); unsorted rows give what that merge gives.
+ * A and B must have the same shape (GKOMI_EINVAL).  The same two calls as
+ * above; workspace gkomi_csr_spgeam_workspace_bytes(nrows). */
+size_t gkomi_csr_spgeam_workspace_bytes(int64_t nrows);
+int gkomi_csr_spgeam_f64_i32(
+    gkomi_stream_t s, int64_t nrows, int64_t ncols, const double* alpha,
+    int64_t a_nnz, const int32_t* a_row_ptrs, const int32_t* a_col_idxs,
+    const double* a_vals, const double* beta, int64_t b_nrows, int64_t b_ncols,
+    int64_t b_nnz, const int32_t* b_row_ptrs, const int32_t* b_col_idxs,
+    const double* b_vals, int32_t* c_row_ptrs, int32_t* c_col_idxs,
+    double* c_vals, int64_t* host_c_nnz, void* workspace,
+    size_t workspace_bytes);
+
 /* ---- CG solver driver (core/solver/cg.cpp:107-193) ----------------------- */
 /* Cg::apply_dense_impl for a CSR system matrix, an optional preconditioner
  * and the criteria Combined(Iteration(max_iters) [id 1], ResidualNorm(

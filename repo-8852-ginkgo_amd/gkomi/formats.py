@@ -56,6 +56,13 @@ def _scalar(dev, x):
     return None if x is None else torch.tensor([float(x)], dtype=F64, device=dev)
 
 
+def _device_scalar(dev, x):
+    """a float, or a one-element tensor that is already on the device"""
+    if torch.is_tensor(x):
+        return x.to(device=dev, dtype=F64).reshape(1)
+    return _scalar(dev, x)
+
+
 class Csr:
     name = "csr"
 
@@ -232,6 +239,40 @@ class Csr:
         rows = torch.zeros(max(self.nnz, 1), dtype=I32, device=self.vals.device)
         self.gk.convert_ptrs_to_idxs_i32(_stream(self.vals), self.row_ptrs, self.nrows, rows)
         return rows
+
+    def _two_calls(self, nrows, ncols, nbytes, call):
+        """count, read nnz back, allocate, fill: call(row_ptrs, col_idxs, vals, host_nnz, ws, nbytes) runs either"""
+        dv = self.vals.device
+        ws = torch.empty(max(nbytes, 8), dtype=U8, device=dv)
+        ptrs = torch.empty(nrows + 1, dtype=I32, device=dv)
+        nnz = ctypes.c_int64(0)
+        call(ptrs, None, None, ctypes.addressof(nnz), ws, nbytes)
+        cols = torch.empty(nnz.value, dtype=I32, device=dv)
+        vals = torch.empty(nnz.value, dtype=F64, device=dv)
+        if nnz.value:
+            call(ptrs, cols, vals, ctypes.addressof(nnz), ws, nbytes)
+        return Csr(self.gk, nrows, ncols, ptrs, cols, vals, self.strategy, self.split)
+
+    def spgemm(self, b, alpha=None, beta=None, d=None):
+        """Csr::apply to a Csr (core/matrix/csr.cpp:184-233): self * b, or alpha * self * b + beta * d when all of
+        alpha, beta (floats or one-element device tensors) and d are given.  Bit for bit the reference's result."""
+        dv = self.vals.device
+        al, be = _device_scalar(dv, alpha), _device_scalar(dv, beta)
+        dn = (d.nrows, d.ncols, d.nnz, d.row_ptrs, d.col_idxs, d.vals) if d is not None else (0, 0, 0, None, None, None)
+        nbytes = self.gk.csr_spgemm_workspace_bytes(self.nrows, b.ncols)
+        return self._two_calls(self.nrows, b.ncols, nbytes, lambda *out: self.gk.csr_spgemm_f64_i32(
+            _stream(self.vals), self.nrows, self.ncols, self.nnz, self.row_ptrs, self.col_idxs, self.vals, b.nrows, b.ncols,
+            b.nnz, b.row_ptrs, b.col_idxs, b.vals, al, be, *dn, *out))
+
+    def spgeam(self, alpha, beta, b):
+        """Csr::apply(alpha, Identity, beta, x) (core/matrix/csr.cpp:217-226): alpha * self + beta * b by the
+        reference's merge of two sorted rows"""
+        dv = self.vals.device
+        al, be = _device_scalar(dv, alpha), _device_scalar(dv, beta)
+        nbytes = self.gk.csr_spgeam_workspace_bytes(self.nrows)
+        return self._two_calls(self.nrows, self.ncols, nbytes, lambda *out: self.gk.csr_spgeam_f64_i32(
+            _stream(self.vals), self.nrows, self.ncols, al, self.nnz, self.row_ptrs, self.col_idxs, self.vals, be, b.nrows,
+            b.ncols, b.nnz, b.row_ptrs, b.col_idxs, b.vals, *out))
 
     # benchmark/utils/formats.hpp:272-290: "csr" = automatical, "csri" = load_balance,
     # "csrm" = merge_path, "csrc" = classical, "csrs" = sparselib (served by the automatic

@@ -849,6 +849,27 @@ inline const Dense<double>* dense(const LinOp* op) { return as<const Dense<doubl
 inline Dense<double>* dense(LinOp* op) { return as<Dense<double>>(op); }
 }  // namespace detail_fmt
 
+// gko::matrix::Identity (include/ginkgo/core/matrix/identity.hpp, core/matrix/identity.cpp:46-60): x = b, and as the
+// operand of Csr::apply(alpha, I, beta, x) the mark of a sparse matrix sum
+template <typename V = double>
+class Identity : public LinOp {
+public:
+    using value_type = V;
+    static std::unique_ptr<Identity> create(std::shared_ptr<const Executor> exec, size_type n = 0)
+    {
+        return std::unique_ptr<Identity>(new Identity(std::move(exec), n));
+    }
+protected:
+    Identity(std::shared_ptr<const Executor> exec, size_type n) : LinOp(std::move(exec), dim<2>(n, n)) {}
+    void apply_impl(const LinOp* b, LinOp* x) const override { as<Dense<V>>(x)->copy_from(as<const Dense<V>>(b)); }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
+    {
+        auto dx = as<Dense<V>>(x);
+        dx->scale(as<const Dense<V>>(beta));
+        dx->add_scaled(as<const Dense<V>>(alpha), as<const Dense<V>>(b));
+    }
+};
+
 template <typename V, typename I>
 class Coo;
 template <typename V, typename I>
@@ -1099,8 +1120,77 @@ public:
 protected:
     Csr(std::shared_ptr<const Executor> exec, const dim<2>& size, size_type nnz, std::shared_ptr<strategy_type> strategy)
         : LinOp(exec, size), values_(exec, nnz), col_idxs_(exec, nnz), row_ptrs_(exec, size[0] + 1), strategy_(std::move(strategy)) {}
-    void apply_impl(const LinOp* b, LinOp* x) const override { spmv(nullptr, b, nullptr, x); }
-    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override { spmv(alpha, b, beta, x); }
+    // the operand decides (core/matrix/csr.cpp:184-233): a Csr -> spgemm, alpha/Csr/beta -> advanced_spgemm with the old x
+    // as D, alpha/Identity/beta -> spgeam with the old x as B, anything else -> spmv
+    using sparse_kernels = std::integral_constant<bool, std::is_same<V, double>::value && std::is_same<I, int32>::value>;
+    void apply_impl(const LinOp* b, LinOp* x) const override
+    {
+        if (auto b_csr = dynamic_cast<const Csr*>(b)) {
+            spgemm_as(sparse_kernels{}, nullptr, b_csr, nullptr, as<Csr>(x));
+        } else {
+            spmv(nullptr, b, nullptr, x);
+        }
+    }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
+    {
+        if (auto b_csr = dynamic_cast<const Csr*>(b)) {
+            spgemm_as(sparse_kernels{}, alpha, b_csr, beta, as<Csr>(x));
+        } else if (dynamic_cast<const Identity<V>*>(b)) {
+            spgeam_as(sparse_kernels{}, alpha, beta, as<Csr>(x));
+        } else {
+            spmv(alpha, b, beta, x);
+        }
+    }
+    void spgemm_as(std::false_type, const LinOp*, const Csr*, const LinOp*, Csr*) const { GKO_NOT_SUPPORTED("csr::spgemm: <double, int32> only"); }
+    void spgeam_as(std::false_type, const LinOp*, const LinOp*, Csr*) const { GKO_NOT_SUPPORTED("csr::spgeam: <double, int32> only"); }
+    // csr::spgemm / advanced_spgemm: count, read nnz(C) back, fill.  The reference clones x because its kernel writes
+    // into x; here the result goes into fresh arrays that x adopts afterwards, so x's own arrays serve as D and no copy
+    // is made (this == x and b == x are fine for the same reason).  adopt() drops srow, the row statistic and the
+    // column-partitioned copy of x.
+    void spgemm_as(std::true_type, const LinOp* alpha, const Csr* b, const LinOp* beta, Csr* x) const
+    {
+        detail::require_device(exec_, "csr::spgemm");
+        const dim<2> size(size_[0], b->get_size()[1]);
+        const double* al = alpha ? detail_fmt::dense(alpha)->get_const_values() : nullptr;
+        const double* be = beta ? detail_fmt::dense(beta)->get_const_values() : nullptr;
+        array<char> ws(exec_, gkomi_csr_spgemm_workspace_bytes(size[0], size[1]) + 8);
+        array<I> rp(exec_, size[0] + 1);
+        int64_t nnz = 0;
+        auto call = [&](I* ci, V* v) {
+            return gkomi_csr_spgemm_f64_i32(nullptr, size_[0], size_[1], get_num_stored_elements(), get_const_row_ptrs(), get_const_col_idxs(), get_const_values(),
+                                            b->get_size()[0], b->get_size()[1], b->get_num_stored_elements(), b->get_const_row_ptrs(), b->get_const_col_idxs(),
+                                            b->get_const_values(), al, be, x->get_size()[0], x->get_size()[1], alpha ? x->get_num_stored_elements() : 0,
+                                            alpha ? x->get_const_row_ptrs() : nullptr, alpha ? x->get_const_col_idxs() : nullptr,
+                                            alpha ? x->get_const_values() : nullptr, rp.get_data(), ci, v, &nnz, ws.get_data(), ws.get_num_elems());
+        };
+        GKOMI_CALL(call(nullptr, nullptr));
+        array<I> ci(exec_, static_cast<size_type>(nnz));
+        array<V> v(exec_, static_cast<size_type>(nnz));
+        if (nnz > 0) GKOMI_CALL(call(ci.get_data(), v.get_data()));
+        GKOMI_CALL(gkomi_synchronize(nullptr));  // the workspace goes away with this scope
+        x->adopt(size, std::move(rp), std::move(ci), std::move(v));
+    }
+    // csr::spgeam: alpha * this + beta * x
+    void spgeam_as(std::true_type, const LinOp* alpha, const LinOp* beta, Csr* x) const
+    {
+        detail::require_device(exec_, "csr::spgeam");
+        const double* al = detail_fmt::dense(alpha)->get_const_values();
+        const double* be = detail_fmt::dense(beta)->get_const_values();
+        array<char> ws(exec_, gkomi_csr_spgeam_workspace_bytes(size_[0]) + 8);
+        array<I> rp(exec_, size_[0] + 1);
+        int64_t nnz = 0;
+        auto call = [&](I* ci, V* v) {
+            return gkomi_csr_spgeam_f64_i32(nullptr, size_[0], size_[1], al, get_num_stored_elements(), get_const_row_ptrs(), get_const_col_idxs(),
+                                            get_const_values(), be, x->get_size()[0], x->get_size()[1], x->get_num_stored_elements(), x->get_const_row_ptrs(),
+                                            x->get_const_col_idxs(), x->get_const_values(), rp.get_data(), ci, v, &nnz, ws.get_data(), ws.get_num_elems());
+        };
+        GKOMI_CALL(call(nullptr, nullptr));
+        array<I> ci(exec_, static_cast<size_type>(nnz));
+        array<V> v(exec_, static_cast<size_type>(nnz));
+        if (nnz > 0) GKOMI_CALL(call(ci.get_data(), v.get_data()));
+        GKOMI_CALL(gkomi_synchronize(nullptr));
+        x->adopt(size_, std::move(rp), std::move(ci), std::move(v));
+    }
     void spmv(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const { spmv_as(V{}, alpha, b, beta, x); }
     // <float, int32>: csr::spmv / advanced_spmv of the single-precision instantiation (gkomi_csr_spmv_f32_i32); no srow
     void spmv_as(float, const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const

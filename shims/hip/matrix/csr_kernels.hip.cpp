@@ -1,5 +1,5 @@
 // hip/matrix/csr_kernels.hip.cpp of a reference tree that binds libgkomi.so:
-// csr::spmv / csr::advanced_spmv (core/matrix/csr_kernels.hpp:58-75).
+// csr::spmv / csr::advanced_spmv (core/matrix/csr_kernels.hpp:58-75), csr::spgemm / advanced_spgemm / spgeam.
 #include "../gkomi_bindings.hpp"
 
 #ifndef GKOMI_SROW_IS_OURS
@@ -52,6 +52,73 @@ void advanced_spmv(std::shared_ptr<const HipExecutor> exec, const matrix::Dense<
         a->get_const_row_ptrs(), a->get_const_col_idxs(), a->get_const_values(), b->get_const_values(),
         b->get_stride(), c->get_values(), c->get_stride(), alpha->get_const_values(), beta->get_const_values(),
         strategy_code(a), gkomi_row_hint(a), split_srow(a), gkomi_csr_srow_tile_for(static_cast<int64_t>(a->get_num_stored_elements()))));
+}
+
+// csr::spgemm / advanced_spgemm / spgeam (core/matrix/csr_kernels.hpp; the reference's HIP backend calls the vendor
+// library here).  The library counts into c's row pointers and reports nnz(C); c's other two arrays are swapped in
+// through matrix::CsrBuilder like reference/matrix/csr_kernels.cpp:232-236 does, then filled.
+inline void spgemm_calls(std::shared_ptr<const HipExecutor> exec, const matrix::Dense<double>* alpha,
+                         const matrix::Csr<double, int32>* a, const matrix::Csr<double, int32>* b,
+                         const matrix::Dense<double>* beta, const matrix::Csr<double, int32>* d,
+                         matrix::Csr<double, int32>* c)
+{
+    const auto m = a->get_size()[0], n = b->get_size()[1];
+    array<char> tmp(exec, gkomi_csr_spgemm_workspace_bytes(m, n) + 8);
+    int64_t nnz = 0;
+    auto call = [&](int32* cols, double* vals) {
+        return gkomi_csr_spgemm_f64_i32(
+            GKOMI_NULL_STREAM, m, a->get_size()[1], a->get_num_stored_elements(), a->get_const_row_ptrs(),
+            a->get_const_col_idxs(), a->get_const_values(), b->get_size()[0], n, b->get_num_stored_elements(),
+            b->get_const_row_ptrs(), b->get_const_col_idxs(), b->get_const_values(),
+            alpha ? alpha->get_const_values() : nullptr, beta ? beta->get_const_values() : nullptr,
+            d ? d->get_size()[0] : 0, d ? d->get_size()[1] : 0, d ? d->get_num_stored_elements() : 0,
+            d ? d->get_const_row_ptrs() : nullptr, d ? d->get_const_col_idxs() : nullptr,
+            d ? d->get_const_values() : nullptr, c->get_row_ptrs(), cols, vals, &nnz, tmp.get_data(),
+            tmp.get_num_elems());
+    };
+    GKOMI_CALL(call(nullptr, nullptr));
+    matrix::CsrBuilder<double, int32> builder{c};
+    builder.get_col_idx_array().resize_and_reset(static_cast<size_type>(nnz));
+    builder.get_value_array().resize_and_reset(static_cast<size_type>(nnz));
+    if (nnz > 0) GKOMI_CALL(call(builder.get_col_idx_array().get_data(), builder.get_value_array().get_data()));
+    GKOMI_CALL(gkomi_synchronize(GKOMI_NULL_STREAM));  // tmp is freed on return
+}
+
+void spgemm(std::shared_ptr<const HipExecutor> exec, const matrix::Csr<double, int32>* a,
+            const matrix::Csr<double, int32>* b, matrix::Csr<double, int32>* c)
+{
+    spgemm_calls(exec, nullptr, a, b, nullptr, nullptr, c);
+}
+
+void advanced_spgemm(std::shared_ptr<const HipExecutor> exec, const matrix::Dense<double>* alpha,
+                     const matrix::Csr<double, int32>* a, const matrix::Csr<double, int32>* b,
+                     const matrix::Dense<double>* beta, const matrix::Csr<double, int32>* d,
+                     matrix::Csr<double, int32>* c)
+{
+    spgemm_calls(exec, alpha, a, b, beta, d, c);
+}
+
+void spgeam(std::shared_ptr<const HipExecutor> exec, const matrix::Dense<double>* alpha,
+            const matrix::Csr<double, int32>* a, const matrix::Dense<double>* beta,
+            const matrix::Csr<double, int32>* b, matrix::Csr<double, int32>* c)
+{
+    const auto m = a->get_size()[0];
+    array<char> tmp(exec, gkomi_csr_spgeam_workspace_bytes(m) + 8);
+    int64_t nnz = 0;
+    auto call = [&](int32* cols, double* vals) {
+        return gkomi_csr_spgeam_f64_i32(
+            GKOMI_NULL_STREAM, m, a->get_size()[1], alpha->get_const_values(), a->get_num_stored_elements(),
+            a->get_const_row_ptrs(), a->get_const_col_idxs(), a->get_const_values(), beta->get_const_values(),
+            b->get_size()[0], b->get_size()[1], b->get_num_stored_elements(), b->get_const_row_ptrs(),
+            b->get_const_col_idxs(), b->get_const_values(), c->get_row_ptrs(), cols, vals, &nnz, tmp.get_data(),
+            tmp.get_num_elems());
+    };
+    GKOMI_CALL(call(nullptr, nullptr));
+    matrix::CsrBuilder<double, int32> builder{c};
+    builder.get_col_idx_array().resize_and_reset(static_cast<size_type>(nnz));
+    builder.get_value_array().resize_and_reset(static_cast<size_type>(nnz));
+    if (nnz > 0) GKOMI_CALL(call(builder.get_col_idx_array().get_data(), builder.get_value_array().get_data()));
+    GKOMI_CALL(gkomi_synchronize(GKOMI_NULL_STREAM));
 }
 
 // ---- <double, int64> (GKO_INSTANTIATE_FOR_EACH_VALUE_AND_INDEX_TYPE, include/ginkgo/core/base/types.hpp:544-560):

@@ -5,6 +5,7 @@
 // (The distributed bindings read the Partition's arrays as DEVICE pointers -- they live on the partition's executor in
 // a reference tree, partition.hpp:300-340, and in the mirror since round 4.)
 #include "prelude_mirror.hpp"
+#include "spgemm_cases.hpp"
 #include <cmath>
 #include <cstdio>
 #include <vector>
@@ -914,6 +915,8 @@ int main()
         const auto sth = st.to_host();
         ran("residual_norm::residual_norm<float>", !all && one && (sth[0].data_ & GKOMI_STATUS_CONVERGED) != 0 && (sth[1].data_ & GKOMI_STATUS_ID_MASK) == 0);
     }
+    // csr::spgemm / advanced_spgemm / spgeam on the reference tests' fixtures (shared with shim_smoke5.cpp)
+    spgemm_cases::run(hip, ran);
     std::printf("wrong: %d\n", wrong);
     return wrong;
 }
