@@ -2,9 +2,9 @@
 // with the criteria Combined(Iteration, ResidualNorm)
 // (core/stop/combined.cpp:40, core/stop/residual_norm.cpp:119-228).
 //
-// mode 0 replays the reference's kernel sequence one launch per kernel and
-// checks the criterion on the host every iteration (a blocking 2-byte D2H copy
-// per iteration, as hip/stop/residual_norm_kernels.hip.cpp:119-120 does).
+// mode 0 replays the reference's kernel sequence one launch per kernel on the
+// shared driver (krylov_driver.hpp) and looks at the criterion's outcome on the
+// host every iteration, as hip/stop/residual_norm_kernels.hip.cpp:119-120 does.
 //
 // mode 1 is the MI355X design: three launches per iteration, every scalar on
 // the device, no per-iteration host round trip.
@@ -23,6 +23,7 @@
 // for p in the epilogue, L2-resident), K3 6n values -- vs 18n + matrix in the
 // reference's accounting (core/solver/cg.cpp:148-156).
 #include "cg_persistent.hpp"
+#include "krylov_driver.hpp"
 
 #include <atomic>
 #include <cstdio>
@@ -31,34 +32,21 @@
 namespace gkomi {
 namespace {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct workspace_layout {
-    size_t r, z, p, q, scalars, part_a, part_b, part_c, red, small, pcg_ctl, pcg_slots, total;
+// the shared layout with four vectors (r, z, p, q), then the persistent single-launch solve's areas: its control word
+// and two banks of one slot per workgroup
+struct cg_layout {
+    solver_layout base;
+    size_t pcg_ctl, pcg_slots, total;
 };
 
-workspace_layout make_layout(int64_t n, int64_t nrhs)
+cg_layout make_cg_layout(int64_t n, int64_t nrhs)
 {
-    workspace_layout l{};
-    const size_t vec = align_up(sizeof(double) * static_cast<size_t>(n) * nrhs, 256);
-    size_t off = 0;
-    l.r = off; off += vec;
-    l.z = off; off += vec;
-    l.p = off; off += vec;
-    l.q = off; off += vec;
-    l.scalars = off; off += 256;
-    // (room for one partial per workgroup of a block-Jacobi apply that carries the dots, see the fused loop)
-    l.part_a = off; off += align_up(sizeof(double) * spmv_dot_partials_room(n), 256);   // r.z / r.r
-    l.part_b = off; off += align_up(sizeof(double) * spmv_dot_partials_room(n), 256);   // r.r with a preconditioner
-    l.part_c = off; off += align_up(sizeof(double) * spmv_dot_partials_room(n), 256);    // p.q (internal.hpp)
-    l.red = off; off += align_up(gkomi_dense_reduction_workspace_bytes(n, nrhs) + 8, 256);
-    // mode 0 scalars: alpha-free set {prev_rho, rho, beta, tau, orig_tau, one, neg_one} x nrhs,
-    // then stop_status[nrhs] and 2 flag bytes
-    l.small = off; off += align_up(sizeof(double) * 8 * static_cast<size_t>(nrhs) + nrhs + 16, 256);
-    // the persistent single-launch solve: its control word and two banks of one slot per workgroup
-    l.pcg_ctl = off; off += align_up(sizeof(pcg_control), 256);
-    l.pcg_slots = off; off += align_up(sizeof(pcg_slot) * 2 * (max_parts + pcg_copies) * pcg_max_stride, 256);
-    l.total = off;
+    cg_layout l{};
+    l.base = make_solver_layout(n, nrhs, 4);
+    auto align256 = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+    l.pcg_ctl = l.base.total;
+    l.pcg_slots = l.pcg_ctl + align256(sizeof(pcg_control));
+    l.total = l.pcg_slots + align256(sizeof(pcg_slot) * 2 * (max_parts + pcg_copies) * pcg_max_stride);
     return l;
 }
 
@@ -68,16 +56,6 @@ std::atomic<int> pcg_mode{[] {
     const char* e = std::getenv("GKOMI_CG_PERSISTENT");
     return e == nullptr ? 1 : std::atoi(e);
 }()};
-
-int identity_or_precond(gkomi_apply_fn precond, void* ctx, gkomi_stream_t s,
-                        int64_t n, int64_t nrhs, const double* r, double* z)
-{
-    if (precond == nullptr) {
-        // matrix::Identity::apply copies (core/matrix/identity.cpp)
-        return gkomi_dense_copy_f64(s, n, nrhs, r, nrhs, z, nrhs);
-    }
-    return precond(ctx, s, r, z);
-}
 
 }  // namespace
 }  // namespace gkomi
@@ -95,7 +73,7 @@ extern "C" int gkomi_cg_persistent_enable(int mode)
 extern "C" size_t gkomi_cg_workspace_bytes(int64_t n, int64_t nrhs)
 {
     if (n < 0 || nrhs <= 0) return 0;
-    return make_layout(n, nrhs).total;
+    return make_cg_layout(n, nrhs).total;
 }
 
 namespace {
@@ -108,12 +86,14 @@ namespace {
         const int err_ = (expr);             \
         if (err_) return -(1000 + err_);     \
     } while (0)
-int persistent_cg(gkomi_stream_t s, int64_t n, const sysmat& A, const spmv_dot_plan& spmv, gkomi_apply_fn precond,
-                  const double* b, double* x, double* r, double* p, double* q, const double* one,
-                  const double* neg_one, const double* orig_tau, int baseline, int64_t max_iters,
-                  double reduction_factor, cg_scalars* scal, void* ctl_mem, void* slot_mem, cg_scalars* result)
+int persistent_cg(const driver_common& c, const solve_request& req, const spmv_dot_plan& spmv, double* r, double* p,
+                  double* q, cg_scalars* scal, void* ctl_mem, void* slot_mem, cg_scalars* result)
 {
-    hipStream_t stream = to_stream(s);
+    const gkomi_stream_t s = c.s;
+    hipStream_t stream = c.stream;
+    const int64_t n = c.n;
+    const sysmat& A = c.A;
+    double* x = req.x;
     cg_scalars polled{};
     // The whole solve in one launch (cg_persistent.hpp) when the vectors AND the matrix fit the
     // register files: Identity preconditioner, aligned CSR, rows of at most 7 nonzeros (the
@@ -133,7 +113,7 @@ int persistent_cg(gkomi_stream_t s, int64_t n, const sysmat& A, const spmv_dot_p
     const bool pcg_fits_matrix =
         pcg_hint >= 1 && pcg_hint <= 7 && ceildiv(pcg_chunk, 512) <= 8;
     const bool pcg_fits_vectors = ceildiv(pcg_chunk, pcg_block) <= pcg_max_rows_per_thread;
-    if (persistent_mode >= 1 && precond == nullptr && (spmv.csr || ell != nullptr) && cus >= 8 &&
+    if (persistent_mode >= 1 && c.precond == nullptr && (spmv.csr || ell != nullptr) && cus >= 8 &&
         cus <= max_parts &&
         n >= 64 * static_cast<int64_t>(cus) &&
         (pcg_fits_matrix || (persistent_mode >= 2 && pcg_fits_vectors && ell == nullptr)) &&
@@ -173,7 +153,7 @@ int persistent_cg(gkomi_stream_t s, int64_t n, const sysmat& A, const spmv_dot_p
 #define GKOMI_PCG(R, KR, BLOCK)                                                                        \
 hipLaunchKernelGGL((cg_persistent_kernel<R, KR, BLOCK, (KR == 7 && R == 8)>), dim3(cus), dim3(BLOCK), 0, stream, \
                    static_cast<int>(n), chunk, m_row_ptrs, m_col_idxs, m_vals, x, r, p, q, slots,  \
-                   stride, nap, ctl, scal, static_cast<long long>(max_iters), reduction_factor,    \
+                   stride, nap, ctl, scal, static_cast<long long>(c.max_iters), c.reduction,       \
                    max_polls, ell_stored, ell_stride)
         // rows of at most 5 nonzeros, up to 8 rows per thread of a 512-thread workgroup (256
         // registers each): the matrix stays in registers
@@ -229,140 +209,85 @@ hipLaunchKernelGGL((cg_persistent_kernel<R, KR, BLOCK, (KR == 7 && R == 8)>), di
         } else {
             // a meeting timed out (workgroups not resident together?): x is a valid guess, start over
             // from r = b - A x with the three-launch iteration
-            PCG_TRY(gkomi_dense_copy_f64(s, n, 1, b, 1, r, 1));
-            PCG_TRY(A.apply(s, 1, neg_one, x, one, r));
+            PCG_TRY(gkomi_dense_copy_f64(s, n, 1, req.b, 1, r, 1));
+            PCG_TRY(A.apply(s, 1, c.neg_one, x, c.one, r));
             PCG_TRY(gkomi_dense_fill_f64(s, n, 1, p, 1, 0.0));
-            hipLaunchKernelGGL(cg_init_scalars_kernel, dim3(1), dim3(1), 0, stream, scal, orig_tau,
-                               baseline == 2 ? 1 : 0);
+            hipLaunchKernelGGL(cg_init_scalars_kernel, dim3(1), dim3(1), 0, stream, scal, c.orig_tau,
+                               req.baseline == 2 ? 1 : 0);
         }
     }
     return 0;
 }
 #undef PCG_TRY
 
-int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, gkomi_apply_fn precond,
-                  void* precond_ctx, const double* b, double* x, int64_t max_iters,
-                  double reduction_factor, int baseline, int mode, int check_every, void* workspace,
-                  size_t workspace_bytes, double* host_info)
+int cg_solve_impl(const solve_request& req, int mode)
 {
-    // what this solve moves between two applies of A decides how A is read (internal.hpp)
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * nrhs * 6);
+    const gkomi_stream_t s = req.s;
+    const int64_t n = req.n, nrhs = req.nrhs;
     if (mode == 1 && n == 0) mode = 0;  // the fused path needs rows
     // the fused kernels move 16 B per lane through x and the workspace vectors: anything else
     // (a view at an odd offset) takes the reference sequence, like the other fused drivers
-    if (mode == 1 && nrhs == 1 &&
-        (reinterpret_cast<uintptr_t>(x) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 16 != 0)) {
-        mode = 0;
-    }
-    if (n < 0 || nrhs <= 0 || max_iters < 0) return GKOMI_EINVAL;
-    if (baseline < 0 || baseline > 2 || (mode != 0 && mode != 1)) return GKOMI_EINVAL;
+    bool reference = false;
+    const int too_many_rows = fused_preflight(req, &reference);  // (answered below, after the argument checks)
+    if (mode == 1 && nrhs == 1 && (reference || reinterpret_cast<uintptr_t>(req.workspace) % 16 != 0)) mode = 0;
+    if (n < 0 || nrhs <= 0 || req.max_iters < 0) return GKOMI_EINVAL;
+    if (req.baseline < 0 || req.baseline > 2 || (mode != 0 && mode != 1)) return GKOMI_EINVAL;
     if (mode == 1 && nrhs != 1) return GKOMI_ENOTSUPPORTED;
-    if (n > INT32_MAX - 1024) return GKOMI_ENOTSUPPORTED;
-    const workspace_layout l = make_layout(n, nrhs);
-    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
-    hipStream_t stream = to_stream(s);
-    char* ws = static_cast<char*>(workspace);
-    double* r = reinterpret_cast<double*>(ws + l.r);
-    double* z = reinterpret_cast<double*>(ws + l.z);
-    double* p = reinterpret_cast<double*>(ws + l.p);
-    double* q = reinterpret_cast<double*>(ws + l.q);
-    void* red = ws + l.red;
-    const size_t red_bytes = gkomi_dense_reduction_workspace_bytes(n, nrhs) + 8;
-    double* small = reinterpret_cast<double*>(ws + l.small);
-    double* prev_rho = small;
-    double* rho = small + nrhs;
-    double* beta = small + 2 * nrhs;
-    double* tau = small + 3 * nrhs;
-    double* orig_tau = small + 4 * nrhs;
-    double* one = small + 5 * nrhs;
-    double* neg_one = small + 6 * nrhs;
-    uint8_t* stop_status = reinterpret_cast<uint8_t*>(small + 8 * nrhs);
-    uint8_t* dev_flags = stop_status + nrhs + (8 - nrhs % 8) % 8;
-
-    // cg::initialize, then r = b - A x (advanced apply), cg.cpp:137-142
-    GKOMI_TRY(gkomi_cg_initialize_f64(s, n, nrhs, b, nrhs, r, nrhs, z, nrhs, p,
-                                      nrhs, q, nrhs, prev_rho, rho, stop_status));
-    GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, one, nrhs, 1.0));
-    GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, neg_one, nrhs, -1.0));
-    GKOMI_TRY(A.apply(s, nrhs, neg_one, x, one, r));
-    // criterion generate: baseline norm (residual_norm.cpp:119-189)
-    if (baseline == 0) {
-        GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, b, nrhs, orig_tau, red, red_bytes));
-    } else if (baseline == 1) {
-        GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, r, nrhs, orig_tau, red, red_bytes));
-    } else {
-        GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, orig_tau, nrhs, 1.0));
-    }
+    GKOMI_TRY(too_many_rows);
+    const cg_layout l = make_cg_layout(n, nrhs);
+    driver_common c;
+    GKOMI_TRY(c.init(req, 6, l.base, l.total));
+    c.iteration_id = id_iteration;
+    c.residual_id = id_residual;
+    hipStream_t stream = c.stream;
+    const sysmat& A = c.A;
+    double *x = req.x, *r = c.vec(0), *z = c.vec(1), *p = c.vec(2), *q = c.vec(3);
+    double *prev_rho = c.scalars, *rho = prev_rho + nrhs, *beta = rho + nrhs;
+    // cg::initialize, then r = b - A x (advanced apply) and the criterion's baseline norm, cg.cpp:137-142
+    GKOMI_TRY(gkomi_cg_initialize_f64(s, n, nrhs, req.b, nrhs, r, nrhs, z, nrhs, p,
+                                      nrhs, q, nrhs, prev_rho, rho, c.stop_status));
+    GKOMI_TRY(c.start(req, r));
 
     if (mode == 0) {
-        uint8_t host_flags[2] = {0, 0};
-        long long iter = -1;
-        int converged = 0;
+        c.check_every = 1;  // the reference asks the host every iteration, whatever the caller's check_every
+        int64_t iter = -1;
         while (true) {
-            GKOMI_TRY(identity_or_precond(precond, precond_ctx, s, n, nrhs, r, z));
-            GKOMI_TRY(gkomi_dense_compute_dot_f64(s, n, nrhs, r, nrhs, z, nrhs, rho, red, red_bytes));
+            GKOMI_TRY(c.apply_precond(r, z));  // (matrix::Identity::apply copies, core/matrix/identity.cpp)
+            GKOMI_TRY(c.dot(r, z, rho));
             ++iter;
             bool stop = false;
-            if (iter >= max_iters) {
-                GKOMI_TRY(gkomi_set_all_statuses(s, nrhs, id_iteration, 1, stop_status));
-                stop = true;
-            } else {
-                GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, r, nrhs, tau, red, red_bytes));
-                GKOMI_TRY(gkomi_residual_norm_f64(s, nrhs, tau, orig_tau, reduction_factor,
-                                                  id_residual, 1, stop_status, dev_flags,
-                                                  host_flags));
-                stop = host_flags[0] != 0;
-                converged = stop ? 1 : 0;
-            }
+            GKOMI_TRY(c.check(iter, r, true, 1, &stop));
             if (stop) break;
-            GKOMI_TRY(gkomi_cg_step_1_f64(s, n, nrhs, p, nrhs, z, nrhs, rho, prev_rho, stop_status));
-            GKOMI_TRY(A.apply(s, nrhs, nullptr, p, nullptr, q));
-            GKOMI_TRY(gkomi_dense_compute_dot_f64(s, n, nrhs, p, nrhs, q, nrhs, beta, red, red_bytes));
+            GKOMI_TRY(gkomi_cg_step_1_f64(s, n, nrhs, p, nrhs, z, nrhs, rho, prev_rho, c.stop_status));
+            GKOMI_TRY(c.spmv(p, q));
+            GKOMI_TRY(c.dot(p, q, beta));
             GKOMI_TRY(gkomi_cg_step_2_f64(s, n, nrhs, x, nrhs, r, nrhs, p, nrhs, q, nrhs, beta, rho,
-                                          stop_status));
+                                          c.stop_status));
             std::swap(prev_rho, rho);
         }
-        if (host_info != nullptr) {
-            host_info[0] = static_cast<double>(iter);
-            host_info[1] = static_cast<double>(converged);
-            // final recurrence residual norms for the report
-            GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, r, nrhs, tau, red, red_bytes));
-            for (int64_t j = 0; j < nrhs; ++j) {
-                GKOMI_TRY(static_cast<int>(hipMemcpyAsync(host_info + 2 + 2 * j, tau + j, sizeof(double),
-                                                          hipMemcpyDeviceToHost, stream)));
-                GKOMI_TRY(static_cast<int>(hipMemcpyAsync(host_info + 3 + 2 * j, orig_tau + j,
-                                                          sizeof(double), hipMemcpyDeviceToHost, stream)));
-            }
-        }
-        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-        return precond_status(precond, precond_ctx, s);
+        return c.finish(c.stop_iter(), r, req.host_info);
     } else {
-        cg_scalars* scal = reinterpret_cast<cg_scalars*>(ws + l.scalars);
-        double* part_a = reinterpret_cast<double*>(ws + l.part_a);
-        double* part_b = reinterpret_cast<double*>(ws + l.part_b);
-        double* part_c = reinterpret_cast<double*>(ws + l.part_c);
-        const int g = vec_grid(n);
-        // q = A p with the p.q partials in the same launch for CSR / ELL /
-        // SELL-P; any other operator: its apply, then a partials kernel
-        const spmv_dot_plan spmv(A);
-        const int nb = spmv.fused() ? spmv.num_partials : g;
-        // (misaligned CSR arrays: spmv.fused() is false, apply + partials kernel like any operator)
-        cg_scalars polled{};  // per call: concurrent solves on other streams / threads do not share it
-        if (check_every < 1) check_every = 1;
-        hipLaunchKernelGGL(cg_init_scalars_kernel, dim3(1), dim3(1), 0, stream, scal, orig_tau,
-                           baseline == 2 ? 1 : 0);
+        // scal, the vector grid g, how A leaves its p.q partials (q = A p with them in the same launch for CSR / ELL /
+        // SELL-P; any other operator, or misaligned CSR arrays: its apply, then a partials kernel) and their number nb.
+        // Each partial array has room for one partial per workgroup of a block-Jacobi apply that carries the dots.
+        fused_driver<cg_scalars> f(c);
+        cg_scalars* scal = f.scal;
+        double *part_a = f.spmv_partials(), *part_b = f.spmv_partials(), *part_c = f.spmv_partials();  // r.z | r.r | p.q
+        const int g = f.g, nb = f.nb;
+        const spmv_dot_plan& spmv = f.spmv;
+        const gkomi_apply_fn precond = c.precond;
+        hipLaunchKernelGGL(cg_init_scalars_kernel, dim3(1), dim3(1), 0, stream, scal, c.orig_tau,
+                           req.baseline == 2 ? 1 : 0);
         GKOMI_TRY(check_launch());
         // The whole solve in one launch when vectors and matrix fit the register files (persistent_cg
         // above); otherwise, or when it gave up, the three-launch iteration below.
         {
-            const int done = persistent_cg(s, n, A, spmv, precond, b, x, r, p, q, one, neg_one, orig_tau, baseline,
-                                           max_iters, reduction_factor, scal, ws + l.pcg_ctl, ws + l.pcg_slots,
-                                           &polled);
+            cg_scalars polled{};
+            const int done = persistent_cg(c, req, spmv, r, p, q, scal, c.ws + l.pcg_ctl, c.ws + l.pcg_slots, &polled);
             if (done < 0) return -done - 1000;
             if (done == 1) {
-                fill_host_info(host_info, polled.stop_iter, polled.status, polled.tau, polled.orig_tau);
-                return precond_status(precond, precond_ctx, s);
+                fill_host_info(req.host_info, polled.stop_iter, polled.status, polled.tau, polled.orig_tau);
+                return precond_status(precond, c.precond_ctx, s);
             }
         }
         // partials of r.z (and r.r) for the first check
@@ -372,7 +297,7 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
         // r and z less per iteration (profiles/r03_p3_cg_kernels.md).  `ng` = how many partials K1 re-adds: the
         // apply's workgroups then, the vector grid otherwise.
         const gkomi_jacobi_ctx* jac =
-            precond == &gkomi_jacobi_apply_cb ? static_cast<const gkomi_jacobi_ctx*>(precond_ctx) : nullptr;
+            precond == &gkomi_jacobi_apply_cb ? static_cast<const gkomi_jacobi_ctx*>(c.precond_ctx) : nullptr;
         int ng = g;
         auto precondition = [&](bool first) -> int {  // z = M^-1 r and the partials of r.z (and, first / fused, r.r)
             if (jac != nullptr) {
@@ -385,7 +310,7 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
                 }
                 jac = nullptr;  // not for this one (scalar Jacobi): the general way from here on
             }
-            GKOMI_TRY(precond(precond_ctx, s, r, z));
+            GKOMI_TRY(c.apply_precond(r, z));
             hipLaunchKernelGGL(cg_dot2_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, z,
                                first ? static_cast<const cg_scalars*>(nullptr) : static_cast<const cg_scalars*>(scal),
                                part_a, first ? part_b : static_cast<double*>(nullptr));
@@ -399,15 +324,13 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
             GKOMI_TRY(check_launch());
         }
         const double* tau_part = precond == nullptr ? part_a : part_b;
-        // paced by pace_fused_solve (internal.hpp); launches issued after the criterion fired return at once -- unless
-        // a preconditioner's are among them
-        host_watch watch;
-        const long long lag = std::min<long long>(check_every, precond == nullptr ? 4 * host_watch_lag : host_watch_lag);
+        // launches issued after the criterion fired return at once -- unless a preconditioner's are among them
+        host_watch& watch = f.watch;
         auto issue = [&](long long i, bool) -> int {  // (the last iteration is enqueued whole as well)
             // (with the Jacobi apply's partials both sums have ng terms; K3's r.r partials, g of them, otherwise)
             hipLaunchKernelGGL(cg_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, p, zz,
                                part_a, ng, tau_part, jac != nullptr ? ng : g, scal, i,
-                               static_cast<long long>(max_iters), reduction_factor, watch.dev);
+                               static_cast<long long>(c.max_iters), c.reduction, watch.dev);
             if (spmv.fused()) {
                 GKOMI_TRY(spmv.launch(stream, p, q, part_c, &scal->status));
             } else {
@@ -421,13 +344,7 @@ int cg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, g
             if (precond != nullptr) GKOMI_TRY(precondition(false));
             return check_launch();
         };
-        auto look = [&]() -> int {
-            const int err = read_scalars(stream, &polled, scal);
-            return err ? -err : (polled.status & GKOMI_STATUS_ID_MASK) != 0;
-        };
-        bool looked = false;
-        GKOMI_TRY(pace_fused_solve(stream, &watch, max_iters, check_every, lag, issue, look, &looked));
-        return finish_fused(s, looked, &polled, scal, host_info, precond, precond_ctx);
+        return f.solve(issue, req.host_info);
     }
 }
 }  // namespace
@@ -440,10 +357,9 @@ extern "C" int gkomi_cg_solve_f64_i32(
     double reduction_factor, int baseline, int mode, int check_every,
     void* workspace, size_t workspace_bytes, double* host_info)
 {
-    return cg_solve_impl(s, n, nrhs,
-                         make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
-                         precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, mode,
-                         check_every, workspace, workspace_bytes, host_info);
+    return cg_solve_impl({s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info}, mode);
 }
 
 // the system matrix behind a callback, fused (single rhs): three launches per
@@ -456,10 +372,9 @@ extern "C" int gkomi_cg_solve_fused_op_f64(gkomi_stream_t s, int64_t n, gkomi_ma
                                            void* workspace, size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return cg_solve_impl(s, n, 1, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x,
-                         max_iters, reduction_factor, baseline, 1,
-                         static_cast<int>(check_every < 1 ? 1 : (check_every > 1 << 20 ? 1 << 20 : check_every)),
-                         workspace, workspace_bytes, host_info);
+    return cg_solve_impl({s, n, 1, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, std::min<int64_t>(check_every, 1 << 20),
+        workspace, workspace_bytes, host_info}, 1);
 }
 
 // the system matrix behind a callback: the reference kernel sequence (mode 0)
@@ -471,7 +386,6 @@ extern "C" int gkomi_cg_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
                                      double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return cg_solve_impl(s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x,
-                         max_iters, reduction_factor, baseline, 0, 1, workspace, workspace_bytes,
-                         host_info);
+    return cg_solve_impl({s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, 1, workspace, workspace_bytes, host_info}, 0);
 }

@@ -296,24 +296,18 @@ struct idr_params {
 };
 
 // ---- the reference's kernel sequence (core/solver/idr.cpp:157-290) -------------------------------------------------
-int idr_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, gkomi_apply_fn precond, void* precond_ctx,
-                   const idr_params& prm, const double* b, double* x, int64_t max_iters, double reduction_factor,
-                   int baseline, int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
+int idr_solve_impl(const solve_request& req, const idr_params& prm)
 {
-    const int64_t sdim = prm.sdim;
+    const gkomi_stream_t s = req.s;
+    const int64_t n = req.n, nrhs = req.nrhs, sdim = prm.sdim;
     if (n < 0 || nrhs <= 0 || sdim < 1 || sdim > max_subspace || sdim > n || prm.subspace == nullptr) return GKOMI_EINVAL;
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * nrhs * (2 * sdim + 6));
     const idr_layout l = make_idr_layout(n, nrhs, sdim);
-    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
-    char* ws = static_cast<char*>(workspace);
     driver_common c;
-    double* sc = nullptr;
-    GKOMI_TRY(make_common(c, s, n, nrhs, A, precond, precond_ctx, max_iters, reduction_factor, baseline, check_every, ws,
-                          l.base, &sc));
+    GKOMI_TRY(c.init(req, static_cast<int>(2 * sdim + 6), l.base, l.total));
+    char* ws = c.ws;
+    double *x = req.x, *sc = c.scalars;
     auto D = [&](size_t at) { return reinterpret_cast<double*>(ws + at); };
-    double *r = D(l.base.vec[0]), *v = D(l.base.vec[1]), *t = D(l.base.vec[2]), *helper = D(l.base.vec[3]),
-           *u_k = D(l.base.vec[4]);
+    double *r = c.vec(0), *v = c.vec(1), *t = c.vec(2), *helper = c.vec(3), *u_k = c.vec(4);
     double *g = D(l.g), *u = D(l.u), *m = D(l.m), *f = D(l.f), *cc = D(l.c), *dots = D(l.dots);
     double *omega = sc, *tht = sc + nrhs, *alpha = sc + 2 * nrhs, *residual_norm = sc + 3 * nrhs;
     double* p = prm.subspace;
@@ -321,11 +315,11 @@ int idr_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, 
     hipStream_t stream = c.stream;
     GKOMI_TRY(gkomi_idr_initialize_f64(s, n, nrhs, sdim, m, wide, p, n, c.stop_status));
     GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, omega, nrhs, 1.0));
-    GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, b, nrhs, r, nrhs));
-    GKOMI_TRY(c.start(b, x, r, baseline));
+    GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, req.b, nrhs, r, nrhs));
+    GKOMI_TRY(c.start(req, r));
     GKOMI_TRY(static_cast<int>(hipMemsetAsync(g, 0, sizeof(double) * n * wide, stream)));
     GKOMI_TRY(static_cast<int>(hipMemsetAsync(u, 0, sizeof(double) * n * wide, stream)));
-    const bool ident = precond == nullptr;  // Identity: helper is v, then the residual, without the copies
+    const bool ident = c.precond == nullptr;  // Identity: helper is v, then the residual, without the copies
     int64_t iter = -1;
     while (true) {
         ++iter;
@@ -338,7 +332,7 @@ int idr_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, 
         for (int64_t k = 0; k < sdim; ++k) {
             GKOMI_TRY(gkomi_idr_step_1_f64(s, n, nrhs, sdim, k, m, wide, f, nrhs, r, nrhs, g, wide, cc, nrhs, v, nrhs,
                                            c.stop_status));
-            if (!ident) GKOMI_TRY(precond(precond_ctx, s, v, helper));
+            if (!ident) GKOMI_TRY(c.apply_precond(v, helper));
             GKOMI_TRY(gkomi_idr_step_2_f64(s, n, nrhs, sdim, k, omega, ident ? v : helper, nrhs, cc, nrhs, u, wide,
                                            c.stop_status));
             // g_k = A u_k: the operators take contiguous vectors, u_k is a column block of u
@@ -348,7 +342,7 @@ int idr_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, 
                                            alpha, r, nrhs, x, nrhs, c.stop_status, dots,
                                            sizeof(double) * dot_blocks * sdim * nrhs));
         }
-        if (!ident) GKOMI_TRY(precond(precond_ctx, s, r, helper));
+        if (!ident) GKOMI_TRY(c.apply_precond(r, helper));
         GKOMI_TRY(c.spmv(ident ? r : helper, t));
         GKOMI_TRY(c.dot(t, r, omega));
         GKOMI_TRY(c.dot(t, t, tht));
@@ -359,7 +353,7 @@ int idr_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, 
                            c.stop_status);
         GKOMI_TRY(check_launch());
     }
-    return c.finish(c.stop_iter(), r, host_info);
+    return c.finish(c.stop_iter(), r, req.host_info);
 }
 
 // ---- fused IDR(s), one right-hand side, s <= 8 -----------------------------------------------------------------------
@@ -726,31 +720,26 @@ int fused_step_3(hipStream_t stream, int grid, int64_t n, int s, int k, const do
     });
 }
 
-int idr_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn precond, void* precond_ctx,
-                   const idr_params& prm, const double* b, double* x, int64_t max_iters, double reduction_factor,
-                   int baseline, int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
+int idr_fused_impl(const solve_request& req, const idr_params& prm)
 {
-    const int64_t nrhs = 1;
+    const gkomi_stream_t s = req.s;
+    const int64_t n = req.n;
     if (prm.sdim > fused_max_subspace) return GKOMI_ENOTSUPPORTED;
     if (n < 0 || prm.sdim < 1 || prm.sdim > n || prm.subspace == nullptr) return GKOMI_EINVAL;
-    if (n > INT32_MAX - 1024) return GKOMI_ENOTSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(x) % 16 != 0) {  // the vector kernels move 16 B per lane
-        return idr_solve_impl(s, n, 1, A_, precond, precond_ctx, prm, b, x, max_iters, reduction_factor, baseline,
-                              check_every, workspace, workspace_bytes, host_info);
-    }
+    bool reference;
+    GKOMI_TRY(fused_preflight(req, &reference));
+    if (reference) return idr_solve_impl(req, prm);
     const int sdim = static_cast<int>(prm.sdim);
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * (2 * sdim + 6));
     const idr_layout l = make_idr_layout(n, 1, sdim);
-    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return GKOMI_EINVAL;  // every vector in it is read 16 B per lane
-    char* ws = static_cast<char*>(workspace);
     driver_common c;
-    double* sc = nullptr;
-    GKOMI_TRY(make_common(c, s, n, nrhs, A, precond, precond_ctx, max_iters, reduction_factor, baseline, check_every, ws,
-                          l.base, &sc));
+    GKOMI_TRY(c.init(req, 2 * sdim + 6, l.base, l.total));
+    // every vector in the workspace is read 16 B per lane
+    if (reinterpret_cast<uintptr_t>(req.workspace) % 16 != 0) return GKOMI_EINVAL;
+    char* ws = c.ws;
+    const sysmat& A = c.A;
+    double* x = req.x;
     auto D = [&](size_t at) { return reinterpret_cast<double*>(ws + at); };
-    double *r = D(l.base.vec[0]), *v = D(l.base.vec[1]), *t = D(l.base.vec[2]), *helper = D(l.base.vec[3]);
+    double *r = c.vec(0), *v = c.vec(1), *t = c.vec(2), *helper = c.vec(3);
     double *g = D(l.g), *u = D(l.u), *m = D(l.m), *f = D(l.f), *p = D(l.pcopy);
     double *part_f = D(l.parts), *part_d = part_f + (sdim + 1) * max_parts, *part_rr = part_d + sdim * max_parts;
     const int64_t ld = l.ld;
@@ -759,34 +748,34 @@ int idr_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
     // m = I (row stride ms), P orthonormalised in place as the caller will find it, then copied to the even stride
     GKOMI_TRY(gkomi_idr_initialize_f64(s, n, 1, sdim, m, ms, prm.subspace, n, c.stop_status));
     GKOMI_TRY(gkomi_dense_copy_f64(s, sdim, n, prm.subspace, n, p, ld));
-    GKOMI_TRY(gkomi_dense_copy_f64(s, n, 1, b, 1, r, 1));
-    GKOMI_TRY(c.start(b, x, r, baseline));
+    GKOMI_TRY(gkomi_dense_copy_f64(s, n, 1, req.b, 1, r, 1));
+    GKOMI_TRY(c.start(req, r));
     GKOMI_TRY(static_cast<int>(hipMemsetAsync(g, 0, sizeof(double) * ld * sdim, stream)));
     GKOMI_TRY(static_cast<int>(hipMemsetAsync(u, 0, sizeof(double) * ld * sdim, stream)));
-    fused_driver<idr_scalars> fd(c, ws, l.base);
+    fused_driver<idr_scalars> fd(c);
     idr_scalars* scal = fd.scal;
     double *part_tr = fd.spmv_partials(), *part_tt = fd.spmv_partials();
     const int grid = fd.g, nb = fd.nb;
     const spmv_dot_plan& spmv = fd.spmv;
-    const bool ident = precond == nullptr;
+    const bool ident = c.precond == nullptr;
     GKOMI_TRY(dispatch_1_to_8(sdim, [&](auto S) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(idr_fused_start_kernel<decltype(S)::value>), dim3(grid), dim3(fblock), 0, stream,
                            n, r, p, ld, scal, c.orig_tau, part_f);
         return check_launch();
     }));
     host_watch& watch = fd.watch;
-    const long long limit = static_cast<long long>(max_iters);
+    const long long limit = static_cast<long long>(c.max_iters);
     auto step_1 = [&](int k, long long it) {
         return dispatch_1_to_8(sdim - k, [&](auto NJ) {
             constexpr int nj = decltype(NJ)::value;
             if (ident) {
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(idr_fused_step_1_kernel<nj, true>), dim3(grid), dim3(fblock), 0, stream,
                                    n, sdim, k, r, g, u, ld, v, m, ms, f + (k & 1) * ms, part_f, grid, scal, it, limit,
-                                   reduction_factor, watch.dev);
+                                   c.reduction, watch.dev);
             } else {
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(idr_fused_step_1_kernel<nj, false>), dim3(grid), dim3(fblock), 0, stream,
                                    n, sdim, k, r, g, u, ld, v, m, ms, f + (k & 1) * ms, part_f, grid, scal, it, limit,
-                                   reduction_factor, watch.dev);
+                                   c.reduction, watch.dev);
             }
             return check_launch();
         });
@@ -797,7 +786,7 @@ int idr_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
         for (int k = 0; k < sdim; ++k) {
             if (k > 0) GKOMI_TRY(step_1(k, it));
             if (!ident) {
-                GKOMI_TRY(precond(precond_ctx, s, v, helper));
+                GKOMI_TRY(c.apply_precond(v, helper));
                 GKOMI_TRY(dispatch_1_to_8(sdim - k, [&](auto NJ) {
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(idr_fused_step_2_kernel<decltype(NJ)::value>), dim3(grid),
                                        dim3(fblock), 0, stream, n, sdim, k, helper, u, ld, m, ms, f + (k & 1) * ms, scal);
@@ -810,7 +799,7 @@ int idr_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
         }
         const double* pr = r;
         if (!ident) {
-            GKOMI_TRY(precond(precond_ctx, s, r, helper));
+            GKOMI_TRY(c.apply_precond(r, helper));
             pr = helper;
         }
         if (spmv.fused()) {
@@ -832,7 +821,7 @@ int idr_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
             return check_launch();
         });
     };
-    return fd.solve(issue, host_info);
+    return fd.solve(issue, req.host_info);
 }
 
 }  // namespace
@@ -982,9 +971,9 @@ extern "C" int gkomi_idr_solve_f64_i32(gkomi_stream_t s, int64_t n, int64_t nrhs
                                        int64_t max_iters, double reduction_factor, int baseline, int64_t check_every,
                                        void* workspace, size_t workspace_bytes, double* host_info)
 {
-    return idr_solve_impl(s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
-                          precond, precond_ctx, idr_params{subspace_dim, kappa, subspace}, b, x, max_iters,
-                          reduction_factor, baseline, check_every, workspace, workspace_bytes, host_info);
+    return idr_solve_impl({s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info}, {subspace_dim, kappa, subspace});
 }
 
 extern "C" int gkomi_idr_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs, gkomi_matrix_apply_fn matrix,
@@ -994,9 +983,9 @@ extern "C" int gkomi_idr_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
                                       size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return idr_solve_impl(s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx,
-                          idr_params{subspace_dim, kappa, subspace}, b, x, max_iters, reduction_factor, baseline,
-                          check_every, workspace, workspace_bytes, host_info);
+    return idr_solve_impl({s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info}, {subspace_dim, kappa, subspace});
 }
 
 extern "C" int gkomi_idr_solve_fused_f64_i32(gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t nnz,
@@ -1008,9 +997,9 @@ extern "C" int gkomi_idr_solve_fused_f64_i32(gkomi_stream_t s, int64_t n, int64_
                                              double* host_info)
 {
     if (nrhs != 1) return GKOMI_ENOTSUPPORTED;
-    return idr_fused_impl(s, n, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint), precond,
-                          precond_ctx, idr_params{subspace_dim, kappa, subspace}, b, x, max_iters, reduction_factor,
-                          baseline, check_every, workspace, workspace_bytes, host_info);
+    return idr_fused_impl({s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info}, {subspace_dim, kappa, subspace});
 }
 
 extern "C" int gkomi_idr_solve_fused_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs, gkomi_matrix_apply_fn matrix,
@@ -1021,7 +1010,7 @@ extern "C" int gkomi_idr_solve_fused_op_f64(gkomi_stream_t s, int64_t n, int64_t
 {
     if (nrhs != 1) return GKOMI_ENOTSUPPORTED;
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return idr_fused_impl(s, n, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx,
-                          idr_params{subspace_dim, kappa, subspace}, b, x, max_iters, reduction_factor, baseline,
-                          check_every, workspace, workspace_bytes, host_info);
+    return idr_fused_impl({s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info}, {subspace_dim, kappa, subspace});
 }

@@ -337,7 +337,7 @@ __global__ void bicgstab_omega_kernel(int64_t nrhs, double* omega, const double*
 bool bad_dims(int64_t n, int64_t nrhs) { return n < 0 || nrhs < 0; }
 dim3 grid_of(int64_t n, int64_t nrhs) { return dim3(static_cast<unsigned>(ceildiv(std::max<int64_t>(n * nrhs, nrhs), block))); }
 
-// the drivers' workspace layout, shared start and criterion, and the fused drivers' host side: krylov_driver.hpp
+// the request record, the workspace layout, the shared start and criterion, the fused drivers' host side: krylov_driver.hpp
 
 }  // namespace
 }  // namespace gkomi
@@ -543,33 +543,22 @@ extern "C" size_t gkomi_krylov_workspace_bytes(int64_t n, int64_t nrhs)
     return make_solver_layout(n, nrhs, 8).total;
 }
 
-#define GKOMI_DRIVER_PROLOGUE(NVEC)                                                              \
-    if (n < 0 || nrhs <= 0) return GKOMI_EINVAL;                                                 \
-    const solver_layout l = make_solver_layout(n, nrhs, 8);                                      \
-    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;              \
-    char* ws = static_cast<char*>(workspace);                                                    \
-    driver_common c;                                                                             \
-    double* sc = nullptr;                                                                        \
-    GKOMI_TRY(make_common(c, s, n, nrhs, A, precond, precond_ctx, max_iters, reduction_factor,   \
-                          baseline, check_every, ws, l, &sc));                                   \
-    auto V = [&](int k) { return reinterpret_cast<double*>(ws + l.vec[k]); }
-
 namespace {
-int bicgstab_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, gkomi_apply_fn precond,
-    void* precond_ctx, const double* b, double* x, int64_t max_iters, double reduction_factor,
-    int baseline, int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
+int bicgstab_solve_impl(const solve_request& req)
 {
-    // what this solve moves between two applies of A decides how A is read (internal.hpp)
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * nrhs * 10);
-    GKOMI_DRIVER_PROLOGUE(8);
-    double *r = V(0), *z = V(1), *y = V(2), *v = V(3), *sv = V(4), *t = V(5), *p = V(6), *rr = V(7);
+    driver_common c;
+    GKOMI_TRY(c.init(req, 10));
+    const gkomi_stream_t s = c.s;
+    const int64_t n = c.n, nrhs = c.nrhs;
+    double *x = req.x, *sc = c.scalars;
+    double *r = c.vec(0), *z = c.vec(1), *y = c.vec(2), *v = c.vec(3), *sv = c.vec(4), *t = c.vec(5), *p = c.vec(6),
+           *rr = c.vec(7);
     double *alpha = sc, *beta = sc + nrhs, *gamma = sc + 2 * nrhs, *prev_rho = sc + 3 * nrhs,
            *rho = sc + 4 * nrhs, *omega = sc + 5 * nrhs;
-    GKOMI_TRY(gkomi_bicgstab_initialize_f64(s, n, nrhs, b, nrhs, r, nrhs, rr, nrhs, y, nrhs, sv, nrhs,
+    GKOMI_TRY(gkomi_bicgstab_initialize_f64(s, n, nrhs, req.b, nrhs, r, nrhs, rr, nrhs, y, nrhs, sv, nrhs,
                                             t, nrhs, z, nrhs, v, nrhs, p, nrhs, prev_rho, rho, alpha,
                                             beta, gamma, omega, c.stop_status));
-    GKOMI_TRY(c.start(b, x, r, baseline));
+    GKOMI_TRY(c.start(req, r));
     GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, r, nrhs, rr, nrhs));
     int64_t iter = -1;
     while (true) {
@@ -599,7 +588,7 @@ int bicgstab_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat&
                                             z, nrhs, alpha, beta, gamma, omega, c.stop_status));
         std::swap(prev_rho, rho);
     }
-    return c.finish(c.stop_iter(), c.host_record.phase == 2 ? sv : r, host_info);
+    return c.finish(c.stop_iter(), c.host_record.phase == 2 ? sv : r, req.host_info);
 }
 
 
@@ -780,36 +769,33 @@ __global__ __launch_bounds__(fblock) void bicgstab_fused_step3_kernel(
     store_block_sums(true, acc, part, smem);
 }
 
-int bicgstab_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn precond,
-                        void* precond_ctx, const double* b, double* x, int64_t max_iters,
-                        double reduction_factor, int baseline, int64_t check_every, void* workspace,
-                        size_t workspace_bytes, double* host_info)
+int bicgstab_fused_impl(const solve_request& req)
 {
-    // what this solve moves between two applies of A decides how A is read (internal.hpp)
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * 1 * 10);
-    const int64_t nrhs = 1;
-    if (n > INT32_MAX - 1024) return GKOMI_ENOTSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(x) % 16 != 0) {  // the vector kernels move 16 B per lane
-        return bicgstab_solve_impl(s, n, 1, A, precond, precond_ctx, b, x, max_iters, reduction_factor,
-                                   baseline, check_every, workspace, workspace_bytes, host_info);
-    }
-    GKOMI_DRIVER_PROLOGUE(8);
-    double *r = V(0), *z = V(1), *y = V(2), *v = V(3), *sv = V(4), *t = V(5), *p = V(6), *rr = V(7);
-    GKOMI_TRY(gkomi_bicgstab_initialize_f64(s, n, 1, b, 1, r, 1, rr, 1, y, 1, sv, 1, t, 1, z, 1, v, 1, p,
+    bool reference;
+    GKOMI_TRY(fused_preflight(req, &reference));
+    if (reference) return bicgstab_solve_impl(req);
+    driver_common c;
+    GKOMI_TRY(c.init(req, 10));
+    const gkomi_stream_t s = c.s;
+    const int64_t n = c.n;
+    const sysmat& A = c.A;
+    double *x = req.x, *sc = c.scalars;
+    double *r = c.vec(0), *z = c.vec(1), *y = c.vec(2), *v = c.vec(3), *sv = c.vec(4), *t = c.vec(5), *p = c.vec(6),
+           *rr = c.vec(7);
+    GKOMI_TRY(gkomi_bicgstab_initialize_f64(s, n, 1, req.b, 1, r, 1, rr, 1, y, 1, sv, 1, t, 1, z, 1, v, 1, p,
                                             1, sc, sc + 1, sc + 2, sc + 3, sc + 4, sc + 5,
                                             c.stop_status));
-    GKOMI_TRY(c.start(b, x, r, baseline));
+    GKOMI_TRY(c.start(req, r));
     GKOMI_TRY(gkomi_dense_copy_f64(s, n, 1, r, 1, rr, 1));
     hipStream_t stream = c.stream;
-    fused_driver<bicgstab_scalars> f(c, ws, l);
+    fused_driver<bicgstab_scalars> f(c);
     bicgstab_scalars* scal = f.scal;
     double *part_rho = f.vec_partials(), *part_tau = f.vec_partials(), *part_ss = f.vec_partials();
     double *part_beta = f.spmv_partials(), *part_gamma = f.spmv_partials(), *part_tt = f.spmv_partials();
     const int g = f.g, nb = f.nb;
     const spmv_dot_plan& spmv = f.spmv;
     const bool csr_epilogue = spmv.fused();
-    if (precond == nullptr) {  // Identity: y = p, z = s without the copies
+    if (c.precond == nullptr) {  // Identity: y = p, z = s without the copies
         y = p;
         z = sv;
     }
@@ -830,21 +816,21 @@ int bicgstab_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_app
     host_watch& watch = f.watch;
     auto issue = [&](long long it, bool last) -> int {
         hipLaunchKernelGGL(bicgstab_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, r, p, v,
-                           part_rho, part_tau, g, scal, it, static_cast<long long>(max_iters),
-                           reduction_factor, watch.dev);
+                           part_rho, part_tau, g, scal, it, static_cast<long long>(c.max_iters),
+                           c.reduction, watch.dev);
         if (last) return check_launch();
-        if (precond != nullptr) GKOMI_TRY(precond(precond_ctx, s, p, y));
+        if (c.precond != nullptr) GKOMI_TRY(c.apply_precond(p, y));
         GKOMI_TRY(spmv_dots(y, v, rr, part_beta, nullptr));
         hipLaunchKernelGGL(bicgstab_fused_step2_kernel, dim3(g), dim3(fblock), 0, stream, n, r, sv,
                            v, part_beta, nb, scal, it, part_ss);
-        if (precond != nullptr) GKOMI_TRY(precond(precond_ctx, s, sv, z));
+        if (c.precond != nullptr) GKOMI_TRY(c.apply_precond(sv, z));
         GKOMI_TRY(spmv_dots(z, t, sv, part_gamma, part_tt));
         hipLaunchKernelGGL(bicgstab_fused_step3_kernel, dim3(g), dim3(fblock), 0, stream, n, x, r,
                            sv, t, y, z, rr, part_gamma, part_tt, nb, scal, part_rho, part_tau, part_ss, g, it,
-                           reduction_factor);
+                           c.reduction);
         return check_launch();
     };
-    return f.solve(issue, host_info);
+    return f.solve(issue, req.host_info);
 }
 
 }  // namespace
@@ -855,10 +841,9 @@ extern "C" int gkomi_bicgstab_solve_fused_f64_i32(
     void* precond_ctx, const double* b, double* x, int64_t max_iters, double reduction_factor,
     int baseline, int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
 {
-    return bicgstab_fused_impl(s, n, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy,
-                                                     max_row_nnz_hint),
-                               precond, precond_ctx, b, x, max_iters, reduction_factor, baseline,
-                               check_every, workspace, workspace_bytes, host_info);
+    return bicgstab_fused_impl({s, n, 1, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 extern "C" int gkomi_bicgstab_solve_fused_op_f64(
@@ -868,9 +853,9 @@ extern "C" int gkomi_bicgstab_solve_fused_op_f64(
     size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return bicgstab_fused_impl(s, n, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x,
-                               max_iters, reduction_factor, baseline, check_every, workspace,
-                               workspace_bytes, host_info);
+    return bicgstab_fused_impl({s, n, 1, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 extern "C" int gkomi_bicgstab_solve_f64_i32(
@@ -880,10 +865,10 @@ extern "C" int gkomi_bicgstab_solve_f64_i32(
     double reduction_factor, int baseline, int64_t check_every, void* workspace,
     size_t workspace_bytes, double* host_info)
 {
-    return bicgstab_solve_impl(s, n, nrhs,
-                            make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
-                            precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every,
-                            workspace, workspace_bytes, host_info);
+    return bicgstab_solve_impl({s, n, nrhs,
+        make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 extern "C" int gkomi_bicgstab_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
@@ -894,25 +879,24 @@ extern "C" int gkomi_bicgstab_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t 
                                         size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return bicgstab_solve_impl(s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x,
-                            max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
-                            host_info);
+    return bicgstab_solve_impl({s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 namespace {
-int fcg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, gkomi_apply_fn precond,
-    void* precond_ctx, const double* b, double* x, int64_t max_iters, double reduction_factor,
-    int baseline, int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
+int fcg_solve_impl(const solve_request& req)
 {
-    // what this solve moves between two applies of A decides how A is read (internal.hpp)
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * nrhs * 7);
-    GKOMI_DRIVER_PROLOGUE(5);
-    double *r = V(0), *z = V(1), *p = V(2), *q = V(3), *t = V(4);
+    driver_common c;
+    GKOMI_TRY(c.init(req, 7));
+    const gkomi_stream_t s = c.s;
+    const int64_t n = c.n, nrhs = c.nrhs;
+    double *x = req.x, *sc = c.scalars;
+    double *r = c.vec(0), *z = c.vec(1), *p = c.vec(2), *q = c.vec(3), *t = c.vec(4);
     double *beta = sc, *prev_rho = sc + nrhs, *rho = sc + 2 * nrhs, *rho_t = sc + 3 * nrhs;
-    GKOMI_TRY(gkomi_fcg_initialize_f64(s, n, nrhs, b, nrhs, r, nrhs, z, nrhs, p, nrhs, q, nrhs, t,
+    GKOMI_TRY(gkomi_fcg_initialize_f64(s, n, nrhs, req.b, nrhs, r, nrhs, z, nrhs, p, nrhs, q, nrhs, t,
                                        nrhs, prev_rho, rho, rho_t, c.stop_status));
-    GKOMI_TRY(c.start(b, x, r, baseline));
+    GKOMI_TRY(c.start(req, r));
     int64_t iter = -1;
     while (true) {
         GKOMI_TRY(c.apply_precond(r, z));
@@ -929,7 +913,7 @@ int fcg_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, 
                                        rho, c.stop_status));
         std::swap(prev_rho, rho);
     }
-    return c.finish(c.stop_iter(), r, host_info);
+    return c.finish(c.stop_iter(), r, req.host_info);
 }
 
 }  // namespace
@@ -1055,28 +1039,24 @@ __global__ __launch_bounds__(fblock) void fcg_fused_step2_kernel(
     store_block_sums(true, acc, part, smem);
 }
 
-int fcg_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn precond,
-                   void* precond_ctx, const double* b, double* x, int64_t max_iters,
-                   double reduction_factor, int baseline, int64_t check_every, void* workspace,
-                   size_t workspace_bytes, double* host_info)
+int fcg_fused_impl(const solve_request& req)
 {
-    // what this solve moves between two applies of A decides how A is read (internal.hpp)
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * 1 * 7);
-    const int64_t nrhs = 1;
-    if (n > INT32_MAX - 1024) return GKOMI_ENOTSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(x) % 16 != 0) {
-        return fcg_solve_impl(s, n, 1, A, precond, precond_ctx, b, x, max_iters, reduction_factor, baseline,
-                              check_every, workspace, workspace_bytes, host_info);
-    }
-    GKOMI_DRIVER_PROLOGUE(5);
-    double *r = V(0), *z = V(1), *p = V(2), *q = V(3), *t = V(4);
-    GKOMI_TRY(gkomi_fcg_initialize_f64(s, n, 1, b, 1, r, 1, z, 1, p, 1, q, 1, t, 1, sc + 1, sc + 2, sc + 3,
+    bool reference;
+    GKOMI_TRY(fused_preflight(req, &reference));
+    if (reference) return fcg_solve_impl(req);
+    driver_common c;
+    GKOMI_TRY(c.init(req, 7));
+    const gkomi_stream_t s = c.s;
+    const int64_t n = c.n;
+    const sysmat& A = c.A;
+    double *x = req.x, *sc = c.scalars;
+    double *r = c.vec(0), *z = c.vec(1), *p = c.vec(2), *q = c.vec(3), *t = c.vec(4);
+    GKOMI_TRY(gkomi_fcg_initialize_f64(s, n, 1, req.b, 1, r, 1, z, 1, p, 1, q, 1, t, 1, sc + 1, sc + 2, sc + 3,
                                        c.stop_status));
-    GKOMI_TRY(c.start(b, x, r, baseline));
+    GKOMI_TRY(c.start(req, r));
     // t = b from initialize, exactly like the reference (fcg.cpp:137 does not refresh it after r = b - A x)
     hipStream_t stream = c.stream;
-    fused_driver<fcg_scalars> f(c, ws, l);
+    fused_driver<fcg_scalars> f(c);
     fcg_scalars* scal = f.scal;
     double *part_rho = f.vec_partials(), *part_rhot = f.vec_partials(), *part_tau = f.vec_partials();
     double* part_beta = f.spmv_partials();  // (and, without the epilogue, two more of that size as scratch)
@@ -1084,10 +1064,10 @@ int fcg_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
     const int g = f.g, nb = f.nb;
     const spmv_dot_plan& spmv = f.spmv;
     const bool csr_epilogue = spmv.fused();
-    const bool identity = precond == nullptr;
+    const bool identity = c.precond == nullptr;
     if (identity) z = r;
     hipLaunchKernelGGL(fcg_fused_init_kernel, dim3(1), dim3(1), 0, stream, scal, c.orig_tau);
-    if (!identity) GKOMI_TRY(precond(precond_ctx, s, r, z));
+    if (!identity) GKOMI_TRY(c.apply_precond(r, z));
     hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, z, t,
                        static_cast<const unsigned char*>(nullptr), part_rho, part_rhot, part_tau);
     GKOMI_TRY(check_launch());
@@ -1095,7 +1075,7 @@ int fcg_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
     auto issue = [&](long long it, bool last) -> int {
         hipLaunchKernelGGL(fcg_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, p, z, part_rho,
                            part_rhot, identity ? part_rho : part_tau, g, scal, it,
-                           static_cast<long long>(max_iters), reduction_factor, watch.dev);
+                           static_cast<long long>(c.max_iters), c.reduction, watch.dev);
         if (last) return check_launch();
         if (csr_epilogue) {
             GKOMI_TRY(spmv.launch(stream, p, q, part_beta, &scal->status));
@@ -1109,13 +1089,13 @@ int fcg_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
                            part_beta, nb, scal, it, identity ? part_rho : static_cast<double*>(nullptr),
                            identity ? part_rhot : static_cast<double*>(nullptr));
         if (!identity) {
-            GKOMI_TRY(precond(precond_ctx, s, r, z));
+            GKOMI_TRY(c.apply_precond(r, z));
             hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, z, t,
                                &scal->status, part_rho, part_rhot, part_tau);
         }
         return check_launch();
     };
-    return f.solve(issue, host_info);
+    return f.solve(issue, req.host_info);
 }
 
 }  // namespace
@@ -1126,10 +1106,9 @@ extern "C" int gkomi_fcg_solve_fused_f64_i32(
     void* precond_ctx, const double* b, double* x, int64_t max_iters, double reduction_factor,
     int baseline, int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
 {
-    return fcg_fused_impl(s, n, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy,
-                                                max_row_nnz_hint),
-                          precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every,
-                          workspace, workspace_bytes, host_info);
+    return fcg_fused_impl({s, n, 1, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 extern "C" int gkomi_fcg_solve_fused_op_f64(
@@ -1139,8 +1118,9 @@ extern "C" int gkomi_fcg_solve_fused_op_f64(
     size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return fcg_fused_impl(s, n, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x, max_iters,
-                          reduction_factor, baseline, check_every, workspace, workspace_bytes, host_info);
+    return fcg_fused_impl({s, n, 1, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 extern "C" int gkomi_fcg_solve_f64_i32(
@@ -1150,10 +1130,9 @@ extern "C" int gkomi_fcg_solve_f64_i32(
     double reduction_factor, int baseline, int64_t check_every, void* workspace,
     size_t workspace_bytes, double* host_info)
 {
-    return fcg_solve_impl(s, n, nrhs,
-                            make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
-                            precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every,
-                            workspace, workspace_bytes, host_info);
+    return fcg_solve_impl({s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 extern "C" int gkomi_fcg_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
@@ -1164,28 +1143,27 @@ extern "C" int gkomi_fcg_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
                                         size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return fcg_solve_impl(s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x,
-                            max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
-                            host_info);
+    return fcg_solve_impl({s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 namespace {
-int cgs_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, gkomi_apply_fn precond,
-    void* precond_ctx, const double* b, double* x, int64_t max_iters, double reduction_factor,
-    int baseline, int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
+int cgs_solve_impl(const solve_request& req)
 {
-    // what this solve moves between two applies of A decides how A is read (internal.hpp)
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * nrhs * 11);
-    GKOMI_DRIVER_PROLOGUE(8);
-    double *r = V(0), *r_tld = V(1), *p = V(2), *q = V(3), *u = V(4), *u_hat = V(5), *v_hat = V(6),
-           *t = V(7);
+    driver_common c;
+    GKOMI_TRY(c.init(req, 11));
+    const gkomi_stream_t s = c.s;
+    const int64_t n = c.n, nrhs = c.nrhs;
+    double *x = req.x, *sc = c.scalars;
+    double *r = c.vec(0), *r_tld = c.vec(1), *p = c.vec(2), *q = c.vec(3), *u = c.vec(4), *u_hat = c.vec(5),
+           *v_hat = c.vec(6), *t = c.vec(7);
     double *alpha = sc, *beta = sc + nrhs, *gamma = sc + 2 * nrhs, *prev_rho = sc + 3 * nrhs,
            *rho = sc + 4 * nrhs;
-    GKOMI_TRY(gkomi_cgs_initialize_f64(s, n, nrhs, b, nrhs, r, nrhs, r_tld, nrhs, p, nrhs, q, nrhs, u,
+    GKOMI_TRY(gkomi_cgs_initialize_f64(s, n, nrhs, req.b, nrhs, r, nrhs, r_tld, nrhs, p, nrhs, q, nrhs, u,
                                        nrhs, u_hat, nrhs, v_hat, nrhs, t, nrhs, alpha, beta, gamma,
                                        prev_rho, rho, c.stop_status));
-    GKOMI_TRY(c.start(b, x, r, baseline));
+    GKOMI_TRY(c.start(req, r));
     GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, r, nrhs, r_tld, nrhs));
     int64_t iter = -1;
     while (true) {
@@ -1207,7 +1185,7 @@ int cgs_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, 
                                        c.stop_status));
         std::swap(prev_rho, rho);
     }
-    return c.finish(c.stop_iter(), r, host_info);
+    return c.finish(c.stop_iter(), r, req.host_info);
 }
 
 }  // namespace
@@ -1313,29 +1291,25 @@ __global__ __launch_bounds__(fblock) void cgs_fused_step3_kernel(
     store_block_sums(true, acc, part, smem);
 }
 
-int cgs_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn precond,
-                   void* precond_ctx, const double* b, double* x, int64_t max_iters,
-                   double reduction_factor, int baseline, int64_t check_every, void* workspace,
-                   size_t workspace_bytes, double* host_info)
+int cgs_fused_impl(const solve_request& req)
 {
-    // what this solve moves between two applies of A decides how A is read (internal.hpp)
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * 1 * 11);
-    const int64_t nrhs = 1;
-    if (n > INT32_MAX - 1024) return GKOMI_ENOTSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(x) % 16 != 0) {
-        return cgs_solve_impl(s, n, 1, A, precond, precond_ctx, b, x, max_iters, reduction_factor, baseline,
-                              check_every, workspace, workspace_bytes, host_info);
-    }
-    GKOMI_DRIVER_PROLOGUE(8);
-    double *r = V(0), *r_tld = V(1), *p = V(2), *q = V(3), *u = V(4), *u_hat = V(5), *v_hat = V(6),
-           *t = V(7);
-    GKOMI_TRY(gkomi_cgs_initialize_f64(s, n, 1, b, 1, r, 1, r_tld, 1, p, 1, q, 1, u, 1, u_hat, 1, v_hat, 1, t, 1,
+    bool reference;
+    GKOMI_TRY(fused_preflight(req, &reference));
+    if (reference) return cgs_solve_impl(req);
+    driver_common c;
+    GKOMI_TRY(c.init(req, 11));
+    const gkomi_stream_t s = c.s;
+    const int64_t n = c.n;
+    const sysmat& A = c.A;
+    double *x = req.x, *sc = c.scalars;
+    double *r = c.vec(0), *r_tld = c.vec(1), *p = c.vec(2), *q = c.vec(3), *u = c.vec(4), *u_hat = c.vec(5),
+           *v_hat = c.vec(6), *t = c.vec(7);
+    GKOMI_TRY(gkomi_cgs_initialize_f64(s, n, 1, req.b, 1, r, 1, r_tld, 1, p, 1, q, 1, u, 1, u_hat, 1, v_hat, 1, t, 1,
                                        sc, sc + 1, sc + 2, sc + 3, sc + 4, c.stop_status));
-    GKOMI_TRY(c.start(b, x, r, baseline));
+    GKOMI_TRY(c.start(req, r));
     GKOMI_TRY(gkomi_dense_copy_f64(s, n, 1, r, 1, r_tld, 1));
     hipStream_t stream = c.stream;
-    fused_driver<cgs_scalars> f(c, ws, l);
+    fused_driver<cgs_scalars> f(c);
     cgs_scalars* scal = f.scal;
     double *part_rho = f.vec_partials(), *part_tau = f.vec_partials();
     double* part_gamma = f.spmv_partials();  // (and two more of that size as scratch)
@@ -1343,7 +1317,7 @@ int cgs_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
     const int g = f.g, nb = f.nb;
     const spmv_dot_plan& spmv = f.spmv;
     const bool csr_epilogue = spmv.fused();
-    const bool identity = precond == nullptr;
+    const bool identity = c.precond == nullptr;
     hipLaunchKernelGGL(cgs_fused_init_kernel, dim3(1), dim3(1), 0, stream, scal, c.orig_tau);
     // partials of r.r_tld and r.r (the third sum is scratch)
     hipLaunchKernelGGL(fused_dot3_partials_kernel, dim3(g), dim3(fblock), 0, stream, n, r, r_tld, r,
@@ -1352,12 +1326,12 @@ int cgs_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
     host_watch& watch = f.watch;
     auto issue = [&](long long it, bool last) -> int {
         hipLaunchKernelGGL(cgs_fused_step1_kernel, dim3(g), dim3(fblock), 0, stream, n, r, u, p, q, part_rho,
-                           part_tau, g, scal, it, static_cast<long long>(max_iters), reduction_factor, watch.dev);
+                           part_tau, g, scal, it, static_cast<long long>(c.max_iters), c.reduction, watch.dev);
         if (last) return check_launch();
         // v_hat = A (M p), gamma = r_tld . v_hat
         const double* mp = p;
         if (!identity) {
-            GKOMI_TRY(precond(precond_ctx, s, p, t));
+            GKOMI_TRY(c.apply_precond(p, t));
             mp = t;
         }
         if (csr_epilogue) {
@@ -1378,7 +1352,7 @@ int cgs_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
             xdir = t;
             rdir = u_hat;
         } else {
-            GKOMI_TRY(precond(precond_ctx, s, t, u_hat));
+            GKOMI_TRY(c.apply_precond(t, u_hat));
             GKOMI_TRY(A.apply(s, 1, nullptr, u_hat, nullptr, t));
             xdir = u_hat;
             rdir = t;
@@ -1387,7 +1361,7 @@ int cgs_fused_impl(gkomi_stream_t s, int64_t n, const sysmat& A_, gkomi_apply_fn
                            r_tld, scal, part_rho, part_tau);
         return check_launch();
     };
-    return f.solve(issue, host_info);
+    return f.solve(issue, req.host_info);
 }
 
 }  // namespace
@@ -1398,10 +1372,9 @@ extern "C" int gkomi_cgs_solve_fused_f64_i32(
     void* precond_ctx, const double* b, double* x, int64_t max_iters, double reduction_factor,
     int baseline, int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
 {
-    return cgs_fused_impl(s, n, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy,
-                                                max_row_nnz_hint),
-                          precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every,
-                          workspace, workspace_bytes, host_info);
+    return cgs_fused_impl({s, n, 1, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 extern "C" int gkomi_cgs_solve_fused_op_f64(
@@ -1411,8 +1384,9 @@ extern "C" int gkomi_cgs_solve_fused_op_f64(
     size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return cgs_fused_impl(s, n, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x, max_iters,
-                          reduction_factor, baseline, check_every, workspace, workspace_bytes, host_info);
+    return cgs_fused_impl({s, n, 1, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 extern "C" int gkomi_cgs_solve_f64_i32(
@@ -1422,10 +1396,9 @@ extern "C" int gkomi_cgs_solve_f64_i32(
     double reduction_factor, int baseline, int64_t check_every, void* workspace,
     size_t workspace_bytes, double* host_info)
 {
-    return cgs_solve_impl(s, n, nrhs,
-                            make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
-                            precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every,
-                            workspace, workspace_bytes, host_info);
+    return cgs_solve_impl({s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 extern "C" int gkomi_cgs_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
@@ -1436,9 +1409,9 @@ extern "C" int gkomi_cgs_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
                                         size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return cgs_solve_impl(s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x,
-                            max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
-                            host_info);
+    return cgs_solve_impl({s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info});
 }
 
 // ---- BiCG / IR ---------------------------------------------------------------------------
@@ -1510,15 +1483,18 @@ extern "C" int gkomi_bicg_solve_f64_i32(
     int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
 {
     if ((precond == nullptr) != (precond_t == nullptr)) return GKOMI_EINVAL;
-    const sysmat A = make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint);
-    GKOMI_DRIVER_PROLOGUE(8);
-    double *r = V(0), *z = V(1), *p = V(2), *q = V(3), *r2 = V(4), *z2 = V(5), *p2 = V(6),
-           *q2 = V(7);
+    const solve_request req{s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info};
+    driver_common c;
+    GKOMI_TRY(c.init(req, 0));
+    double *sc = c.scalars, *r = c.vec(0), *z = c.vec(1), *p = c.vec(2), *q = c.vec(3), *r2 = c.vec(4), *z2 = c.vec(5),
+           *p2 = c.vec(6), *q2 = c.vec(7);
     double *beta = sc, *prev_rho = sc + nrhs, *rho = sc + 2 * nrhs;
     GKOMI_TRY(gkomi_bicg_initialize_f64(s, n, nrhs, b, nrhs, r, nrhs, z, nrhs, p, nrhs, q, nrhs,
                                         prev_rho, rho, r2, nrhs, z2, nrhs, p2, nrhs, q2, nrhs,
                                         c.stop_status));
-    GKOMI_TRY(c.start(b, x, r, baseline));
+    GKOMI_TRY(c.start(req, r));
     GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, r, nrhs, r2, nrhs));
     int64_t iter = -1;
     while (true) {
@@ -1558,23 +1534,22 @@ extern "C" int gkomi_ir_solve_f64_i32(
     int64_t max_iters, double reduction_factor, int baseline, void* workspace,
     size_t workspace_bytes, double* host_info)
 {
-    gkomi_apply_fn precond = inner;
-    void* precond_ctx = inner_ctx;
-    const int64_t check_every = 1;
-    const sysmat A = make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint);
-    GKOMI_DRIVER_PROLOGUE(2);
-    double *residual = V(0), *inner_solution = V(1);
-    double* relax = sc;
+    const solve_request req{s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        inner, inner_ctx, b, x, max_iters, reduction_factor, baseline, 1, workspace, workspace_bytes, host_info};
+    driver_common c;
+    GKOMI_TRY(c.init(req, 0));
+    double *residual = c.vec(0), *inner_solution = c.vec(1);
+    double* relax = c.scalars;
     GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, relax, nrhs, relaxation_factor));
     GKOMI_TRY(gkomi_ir_initialize(s, nrhs, c.stop_status));
     GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, b, nrhs, residual, nrhs));
-    GKOMI_TRY(c.start(b, x, residual, baseline));
+    GKOMI_TRY(c.start(req, residual));
     int64_t iter = -1;
     while (true) {
         ++iter;
         if (iter > 0) {
             GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, b, nrhs, residual, nrhs));
-            GKOMI_TRY(A.apply(s, nrhs, c.neg_one, x, c.one, residual));
+            GKOMI_TRY(c.A.apply(s, nrhs, c.neg_one, x, c.one, residual));
         }
         bool stop = false;
         GKOMI_TRY(c.check(iter, residual, true, 1, &stop));

@@ -1,6 +1,7 @@
-// Host side of the Krylov drivers (krylov.hip: BiCGSTAB, FCG, CGS, BiCG, IR; idr.hip: IDR(s)): the workspace layout,
-// what every reference-sequence driver shares (r = b - A x, the baseline norm, the deferred criterion), and what the
-// fused single-rhs drivers share on the host.  Included by the sources that hold a driver; everything is file-local.
+// Host side of the Krylov drivers (cg_solver.hip: CG; krylov.hip: BiCGSTAB, FCG, CGS, BiCG, IR; idr.hip: IDR(s)): what
+// a caller asks for, the workspace layout, what every reference-sequence driver shares (r = b - A x, the baseline norm,
+// the deferred criterion), and what the fused single-rhs drivers share on the host.  Included by the sources that hold
+// a driver; everything is file-local.
 #pragma once
 #include <algorithm>
 
@@ -30,6 +31,32 @@ __global__ void record_stop_kernel(const uint8_t* __restrict__ flags, long long 
 }
 
 // ---- drivers ------------------------------------------------------------------
+// what every solve entry point is asked for; the entry point fills it in once and the drivers hand it on whole
+struct solve_request {
+    gkomi_stream_t s;
+    int64_t n, nrhs;
+    sysmat A;
+    gkomi_apply_fn precond;
+    void* precond_ctx;
+    const double* b;
+    double* x;
+    int64_t max_iters;
+    double reduction_factor;
+    int baseline;
+    int64_t check_every;
+    void* workspace;
+    size_t workspace_bytes;
+    double* host_info;
+};
+
+// The fused single-rhs drivers move 16 B per lane through x: a view at an odd offset takes the driver's reference
+// sequence instead (*reference), and more rows than the kernels' 32-bit indices reach are refused.
+inline int fused_preflight(const solve_request& req, bool* reference)
+{
+    *reference = reinterpret_cast<uintptr_t>(req.x) % 16 != 0;
+    return req.n > INT32_MAX - 1024 ? GKOMI_ENOTSUPPORTED : 0;
+}
+
 struct solver_layout {
     size_t vec[8], small, red, parts, total;
 };
@@ -54,7 +81,7 @@ solver_layout make_solver_layout(int64_t n, int64_t nrhs, int nvec)
     return l;
 }
 
-// what the three drivers share: r = b - A x, the baseline norm, the criterion
+// what the drivers share: the carved workspace, r = b - A x, the baseline norm, the criterion
 struct driver_common {
     gkomi_stream_t s;
     hipStream_t stream;
@@ -64,12 +91,58 @@ struct driver_common {
     void* precond_ctx;
     int64_t max_iters;
     double reduction;
+    char* ws;
+    solver_layout l;
     double *tau, *orig_tau, *one, *neg_one;
+    double* scalars;  // 6 rows of nrhs for the solver's own
     uint8_t *stop_status, *dev_flags;
     void* red;
     size_t red_bytes;
     int converged = 0;
-    uint8_t host_flags[2] = {0, 0};
+    // Combined(Iteration, ResidualNorm): what check() reports; CG numbers them 1 and 2 (fused_krylov.hpp)
+    uint8_t iteration_id = 1, residual_id = 1;
+
+    // Checks the request and carves the workspace: `layout` for the shared part, `total` with the solver's own areas
+    // behind it.  working_vectors: what the solve moves between two applies of A decides how A is read (internal.hpp);
+    // 0 leaves A as the caller set it.
+    int init(const solve_request& req, int working_vectors, const solver_layout& layout, size_t total)
+    {
+        if (req.n < 0 || req.nrhs <= 0) return GKOMI_EINVAL;
+        if (req.workspace == nullptr || req.workspace_bytes < total) return GKOMI_EWORKSPACE;
+        if (req.max_iters < 0 || req.baseline < 0 || req.baseline > 2) return GKOMI_EINVAL;
+        s = req.s;
+        stream = to_stream(s);
+        n = req.n; nrhs = req.nrhs;
+        A = req.A;
+        if (working_vectors > 0) A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * nrhs * working_vectors);
+        precond = req.precond; precond_ctx = req.precond_ctx;
+        max_iters = req.max_iters; reduction = req.reduction_factor;
+        ws = static_cast<char*>(req.workspace);
+        l = layout;
+        double* small = reinterpret_cast<double*>(ws + l.small);
+        tau = small;
+        orig_tau = small + nrhs;
+        one = small + 2 * nrhs;
+        neg_one = small + 3 * nrhs;
+        scalars = small + 4 * nrhs;
+        stop_status = reinterpret_cast<uint8_t*>(small + 10 * nrhs);
+        dev_flags = stop_status + nrhs + (8 - nrhs % 8) % 8;
+        record = reinterpret_cast<stop_record*>(dev_flags + 16);
+        check_every = req.check_every < 1 ? 1 : req.check_every;
+        red = ws + l.red;
+        red_bytes = gkomi_dense_reduction_workspace_bytes(n, nrhs) + 8;
+        const stop_record init{-1, 0, 0};
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(record, &init, sizeof(init), hipMemcpyHostToDevice, stream)));
+        return static_cast<int>(hipStreamSynchronize(stream));  // `init` is a stack object
+    }
+    // a driver with no areas of its own: eight vectors
+    int init(const solve_request& req, int working_vectors)
+    {
+        if (req.n < 0 || req.nrhs <= 0) return GKOMI_EINVAL;
+        const solver_layout layout = make_solver_layout(req.n, req.nrhs, 8);
+        return init(req, working_vectors, layout, layout.total);
+    }
+    double* vec(int k) const { return reinterpret_cast<double*>(ws + l.vec[k]); }
 
     int spmv(const double* in, double* out) const
     {
@@ -84,8 +157,10 @@ struct driver_common {
     {
         return gkomi_dense_compute_dot_f64(s, n, nrhs, a, nrhs, b2, nrhs, result, red, red_bytes);
     }
-    int start(const double* b, const double* x, double* r, int baseline)
+    int start(const solve_request& req, double* r)
     {
+        const double *b = req.b, *x = req.x;
+        const int baseline = req.baseline;
         GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, one, nrhs, 1.0));
         GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, neg_one, nrhs, -1.0));
         // r = b - A x (r already holds b)
@@ -110,7 +185,7 @@ struct driver_common {
                                                   hipMemcpyDeviceToHost, stream)));
         return static_cast<int>(hipStreamSynchronize(stream));
     }
-    // Combined(Iteration [id 1], ResidualNorm [id 1]) on `residual`; *stop = every
+    // Combined(Iteration [iteration_id], ResidualNorm [residual_id]) on `residual`; *stop = every
     // column has stopped.  The criterion itself is evaluated on the device at
     // every call, exactly where the reference evaluates it; the host learns the
     // outcome every `check_every` calls (stop_iter() is then the iteration the
@@ -121,7 +196,7 @@ struct driver_common {
         if (iter >= max_iters) {
             GKOMI_TRY(poll());  // converged during the iterations not looked at yet?
             if (host_record.iter < 0) {
-                GKOMI_TRY(gkomi_set_all_statuses(s, nrhs, 1, set_finalized ? 1 : 0, stop_status));
+                GKOMI_TRY(gkomi_set_all_statuses(s, nrhs, iteration_id, set_finalized ? 1 : 0, stop_status));
                 converged = 0;
                 host_record.iter = iter;
                 host_record.phase = phase;
@@ -132,7 +207,7 @@ struct driver_common {
             return 0;
         }
         GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, residual, nrhs, tau, red, red_bytes));
-        GKOMI_TRY(gkomi_residual_norm_f64(s, nrhs, tau, orig_tau, reduction, 1,
+        GKOMI_TRY(gkomi_residual_norm_f64(s, nrhs, tau, orig_tau, reduction, residual_id,
                                           set_finalized ? 1 : 0, stop_status, dev_flags, nullptr));
         hipLaunchKernelGGL(record_stop_kernel, dim3(1), dim3(1), 0, stream, dev_flags,
                            static_cast<long long>(iter), phase, record);
@@ -165,37 +240,7 @@ struct driver_common {
     }
 };
 
-int make_common(driver_common& c, gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A,
-                gkomi_apply_fn precond, void* precond_ctx,
-                int64_t max_iters, double reduction, int baseline, int64_t check_every, char* ws,
-                const solver_layout& l, double** scalars)
-{
-    if (n < 0 || nrhs <= 0 || max_iters < 0 || baseline < 0 || baseline > 2) return GKOMI_EINVAL;
-    c.s = s;
-    c.stream = to_stream(s);
-    c.n = n; c.nrhs = nrhs;
-    c.A = A;
-    c.precond = precond; c.precond_ctx = precond_ctx;
-    c.max_iters = max_iters; c.reduction = reduction;
-    double* small = reinterpret_cast<double*>(ws + l.small);
-    c.tau = small;
-    c.orig_tau = small + nrhs;
-    c.one = small + 2 * nrhs;
-    c.neg_one = small + 3 * nrhs;
-    *scalars = small + 4 * nrhs;  // 6 rows for the solver's own scalars
-    c.stop_status = reinterpret_cast<uint8_t*>(small + 10 * nrhs);
-    c.dev_flags = c.stop_status + nrhs + (8 - nrhs % 8) % 8;
-    c.record = reinterpret_cast<stop_record*>(c.dev_flags + 16);
-    c.check_every = check_every < 1 ? 1 : check_every;
-    const stop_record init{-1, 0, 0};
-    if (int err = static_cast<int>(hipMemcpyAsync(c.record, &init, sizeof(init), hipMemcpyHostToDevice, c.stream))) return err;
-    if (int err = static_cast<int>(hipStreamSynchronize(c.stream))) return err;  // `init` is a stack object
-    c.red = ws + l.red;
-    c.red_bytes = gkomi_dense_reduction_workspace_bytes(n, nrhs) + 8;
-    return 0;
-}
-
-// what the three fused single-rhs drivers share on the host: the device scalars in front of the partial arrays
+// what the fused single-rhs drivers share on the host: the device scalars in front of the partial arrays
 // (solver_layout::parts), the grid of the vector kernels, how A leaves its dot partials, the pacing and the report
 template <class Scalars>
 struct fused_driver {
@@ -207,10 +252,10 @@ struct fused_driver {
     int nb;               // partials of an apply of A: the epilogue's, or those of the partials kernel after it
     size_t per_spmv;
     host_watch watch;
-    fused_driver(const driver_common& c_, char* ws, const solver_layout& l)
-        : c(c_), scal(reinterpret_cast<Scalars*>(ws + l.parts)), g(fused_vec_grid(c_.n)), spmv(c_.A),
+    explicit fused_driver(const driver_common& c_)
+        : c(c_), scal(reinterpret_cast<Scalars*>(c_.ws + c_.l.parts)), g(fused_vec_grid(c_.n)), spmv(c_.A),
           nb(spmv.fused() ? spmv.num_partials : g), per_spmv(spmv_dot_partials_room(c_.n)),
-          next(reinterpret_cast<double*>(ws + l.parts) + 32)
+          next(reinterpret_cast<double*>(c_.ws + c_.l.parts) + 32)
     {}
     // the arrays are handed out in order; the layout has room for three of each kind
     double* vec_partials() { return take(fused_vec_max_parts); }

@@ -114,6 +114,23 @@ def test_baselines_and_nonzero_initial_guess(gk, oracle, mode):
         assert matgen.rel_err(host(res["x"]), xe) <= 1e-6, name
 
 
+@pytest.mark.parametrize("mode", [0, 1])
+def test_zero_iterations_allowed_reports_like_the_oracle(gk, oracle, mode):
+    """max_iters = 0: the Iteration criterion fires at the first check, before the residual norm is asked -- zero
+    iterations, not converged, x untouched, in the reference kernel sequence and in the fused driver alike."""
+    n, rp, ci, v = matgen.poisson_2d_5pt(24, 24)
+    b = np.sin(0.1 * np.arange(n))
+    xe = np.zeros(n)
+    it = oracle.ref_cg_solve(n, rp, ci, v, b, xe, 0, 1e-10, 0, None, 0)
+    assert it == 0
+    res = _solve(gk, rp, ci, v, b, np.zeros(n), mode, max_iters=0, reduction=1e-10, check_every=4)
+    assert res["iterations"] == it and not res["converged"]
+    assert not host(res["x"]).any()
+    # r = b - A 0 = b: both norms are ||b||, each a sum of 576 squares in its own order (<= n eps relative, 1.3e-13)
+    for norm in (res["residual_norm"][0], res["baseline_norm"][0]):
+        assert abs(norm - np.linalg.norm(b)) <= 1e-12 * np.linalg.norm(b)
+
+
 def test_already_converged_rhs_zero_iterations(gk):
     # x0 is the exact solution: the first check (iter 0) fires, x untouched
     n, rp, ci, v = matgen.poisson_2d_5pt(10, 10)
@@ -134,6 +151,38 @@ def test_workspace_too_small(gk):
         gk.cg_solve_f64_i32(None, n, 1, int(rp[-1]), dev(rp), dev(ci), dev(v), 0, -1, None, None, b,
                             torch.zeros_like(b), 10, 1e-6, 0, 0, 1, ws, 16, info)
     assert e.value.code == -4
+
+
+def test_workspace_one_byte_short_is_refused_before_anything_runs(gk):
+    import gkomi
+    n, rp, ci, v = matgen.poisson_2d_5pt(24, 24)
+    nbytes = gk.cg_workspace_bytes(n, 1)
+    ws = torch.full((nbytes,), 0x5a, dtype=torch.uint8, device="cuda:0")
+    b = dev(np.ones((n, 1)))
+    x = torch.full_like(b, 7.0)
+    info = np.full(4, -3.0)
+    for mode in (0, 1):
+        with pytest.raises(gkomi.GkomiError) as e:
+            gk.cg_solve_f64_i32(None, n, 1, int(rp[-1]), dev(rp), dev(ci), dev(v), 0, -1, None, None, b, x, 10, 1e-6, 0,
+                                mode, 1, ws, nbytes - 1, info)
+        assert e.value.code == -4
+    # nothing was launched: workspace, x and host_info are as the caller left them
+    assert bool((ws == 0x5a).all()) and bool((x == 7.0).all()) and (info == -3.0).all()
+
+
+def test_fused_mode_on_a_misaligned_x_is_the_reference_sequence_bit_for_bit(gk):
+    n, rp, ci, v = matgen.poisson_2d_5pt(24, 24)
+    b = dev(np.sin(0.1 * np.arange(n)))
+    x = torch.zeros(n + 1, dtype=torch.float64, device="cuda:0")[1:]
+    assert x.data_ptr() % 16 == 8
+    for max_iters in (5, 1000):
+        x.zero_()
+        fused = solvers.cg_solve(gk, n, dev(rp), dev(ci), dev(v), b, x=x, mode=1, max_iters=max_iters, reduction=1e-10)
+        seq = solvers.cg_solve(gk, n, dev(rp), dev(ci), dev(v), b, mode=0, max_iters=max_iters, reduction=1e-10)
+        assert fused["iterations"] == seq["iterations"] and fused["converged"] == seq["converged"]
+        assert fused["converged"] == (max_iters == 1000)
+        assert host(fused["x"]).tobytes() == host(seq["x"]).tobytes()
+        assert fused["residual_norm"].tobytes() == seq["residual_norm"].tobytes()
 
 
 def test_fused_mode_on_views_at_odd_offsets(gk, oracle):

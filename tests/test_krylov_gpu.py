@@ -307,6 +307,22 @@ def test_fused_drivers_on_every_matrix_format(gk, solver, precond):
                 assert matgen.rel_err(host(res["x"]), host(base["x"])) < 1e-8
 
 
+def test_bicgstab_workspace_one_byte_short_is_refused_before_anything_runs(gk):
+    import gkomi
+    n, rp, ci, v = matgen.poisson_2d_5pt(24, 24)
+    nbytes = gk.krylov_workspace_bytes(n, 1)
+    ws = torch.full((nbytes,), 0x5a, dtype=torch.uint8, device="cuda:0")
+    b = dev(np.ones((n, 1)))
+    x = torch.full_like(b, 7.0)
+    info = np.full(4, -3.0)
+    with pytest.raises(gkomi.GkomiError) as e:
+        gk.bicgstab_solve_f64_i32(None, n, 1, int(rp[-1]), dev(rp), dev(ci), dev(v), 0, -1, None, None, b, x, 10, 1e-6, 0,
+                                  1, ws, nbytes - 1, info)
+    assert e.value.code == -4
+    # nothing was launched: workspace, x and host_info are as the caller left them
+    assert bool((ws == 0x5a).all()) and bool((x == 7.0).all()) and (info == -3.0).all()
+
+
 # ---- fused single-rhs BiCGSTAB (6 launches per iteration) ---------------------------
 def _convection(n3=12):
     n, rp, ci, v = matgen.poisson_3d_7pt(n3)
