@@ -8,6 +8,25 @@
 
 #define CHECK(cond) do { if (!(cond)) { std::cerr << "FAILED: " #cond " at line " << __LINE__ << "\n"; return 1; } } while (0)
 
+// A solver generated on a host executor from the square A: its getters, apply refused as NotCompiled; from the
+// 3 x 2 W: generate refused as DimensionMismatch.  Returns the line of the first check that fails, 0 if none does.
+template <typename Solver>
+static int solver_base_checks(std::shared_ptr<const gko::Executor> ref, std::shared_ptr<const gko::LinOp> A, std::shared_ptr<const gko::LinOp> W,
+                              const gko::LinOp* b, gko::LinOp* x)
+{
+    auto solver = Solver::build().with_criteria(gko::stop::Iteration::build().with_max_iters(5u).on(ref)).on(ref)->generate(A);
+    if (solver->get_system_matrix() != A) return __LINE__;
+    if (solver->get_preconditioner() != nullptr) return __LINE__;
+    if (solver->get_stop_settings().max_iters != 5 || solver->get_last_iteration_count() != -1 || solver->has_converged()) return __LINE__;
+    bool not_compiled = false;
+    try { solver->apply(b, x); } catch (const gko::NotCompiled&) { not_compiled = true; }
+    if (!not_compiled) return __LINE__;
+    bool mismatch = false;
+    try { Solver::build().on(ref)->generate(W); } catch (const gko::DimensionMismatch&) { mismatch = true; }
+    if (!mismatch) return __LINE__;
+    return 0;
+}
+
 int main()
 {
     using vec = gko::matrix::Dense<double>;
@@ -49,6 +68,24 @@ int main()
     bool solver_not_compiled = false;
     try { solver->apply(b.get(), x.get()); } catch (const gko::NotCompiled&) { solver_not_compiled = true; }
     CHECK(solver_not_compiled);
+    // what every iterative solver has from solver::detail::iterative_solver, on a host executor
+    {
+        std::istringstream wide("%%MatrixMarket matrix coordinate real general\n3 2 2\n1 1 1.0\n3 2 1.0\n");
+        auto W = gko::share(gko::read<csr>(wide, ref));
+#define SOLVER_BASE(S)                                                                                      \
+    if (int line = solver_base_checks<gko::solver::S<double>>(ref, A, W, b.get(), x.get())) {                   \
+        std::cerr << "FAILED: " #S " at line " << line << "\n";                                                 \
+        return 1;                                                                                               \
+    }
+        SOLVER_BASE(Cg) SOLVER_BASE(Bicgstab) SOLVER_BASE(Fcg) SOLVER_BASE(Cgs) SOLVER_BASE(Idr) SOLVER_BASE(Ir) SOLVER_BASE(Gmres)
+#undef SOLVER_BASE
+        auto ir = gko::solver::Ir<double>::build().on(ref)->generate(A);
+        CHECK(ir->get_solver() == nullptr);
+        // Bicg transposes the system matrix at generate: a kernel, so already that is refused here
+        bool bicg_not_compiled = false;
+        try { gko::solver::Bicg<double>::build().on(ref)->generate(A); } catch (const gko::NotCompiled&) { bicg_not_compiled = true; }
+        CHECK(bicg_not_compiled);
+    }
     // matrix_data helpers and device_matrix_data on a host memory space
     gko::matrix_data<double, int> md;
     md.size = gko::dim<2>(3, 3);

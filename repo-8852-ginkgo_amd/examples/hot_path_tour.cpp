@@ -395,6 +395,35 @@ int main()
                       << exec->copy_val_to_host(rn->get_const_values()) / exec->copy_val_to_host(bn->get_const_values()) << "\n";
         }
 
+        // the advanced apply every solver has from the common base: x = alpha * solve(b) + beta * x0 through Cg (on A)
+        // and Gmres (on B), against the same expression put together from the plain apply -- the same solve from the
+        // same initial guess, then the same scale and add_scaled, so the difference is exactly 0
+        {
+            auto alpha = gko::initialize<vec>({0.75}, exec);
+            auto beta = gko::initialize<vec>({-0.5}, exec);
+            auto check = [&](const char* name, const gko::LinOp* solver) {
+                auto advanced = x->clone();
+                solver->apply(alpha.get(), b.get(), beta.get(), advanced.get());
+                auto solved = x->clone();
+                solver->apply(b.get(), solved.get());
+                auto plain = x->clone();
+                plain->scale(beta.get());
+                plain->add_scaled(alpha.get(), solved.get());
+                std::cout << name << " " << diff_norm(exec, advanced.get(), plain.get()) << "\n";
+            };
+            auto cg = gko::solver::Cg<double>::build()
+                          .with_criteria(gko::stop::Iteration::build().with_max_iters(400u).on(exec),
+                                         gko::stop::ResidualNorm<double>::build().with_reduction_factor(1e-8).on(exec))
+                          .on(exec)->generate(A);
+            check("cg_advanced_diff", cg.get());
+            auto gmres = gko::solver::Gmres<double>::build()
+                             .with_krylov_dim(30u)
+                             .with_criteria(gko::stop::Iteration::build().with_max_iters(120u).on(exec),
+                                            gko::stop::ResidualNorm<double>::build().with_reduction_factor(1e-8).on(exec))
+                             .on(exec)->generate(B);
+            check("gmres_advanced_diff", gmres.get());
+        }
+
         // assembly on the device: shuffled triplets with duplicates and zeros ->
         // device_matrix_data::sum_duplicates / remove_zeros -> Csr::read
         {

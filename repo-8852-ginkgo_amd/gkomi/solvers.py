@@ -25,75 +25,79 @@ def _check_precond(precond, nrhs):
                          f"pass nrhs={int(nrhs)} to its generate call")
 
 
+# The frame of every solve function below: operands, workspace, one call of the C ABI, report.
+
+def _operands(n, b, x, *preconds):
+    """b as n x nrhs, x (zeros when None) likewise, nrhs; every preconditioner checked against nrhs.  The C ABI
+    receives bare pointers and reads them as contiguous n x nrhs vectors, so both must be."""
+    b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
+    nrhs = b2.shape[1]
+    for p in preconds:
+        _check_precond(p, nrhs)
+    if x is None:
+        x = torch.zeros_like(b2)
+    x2 = x.reshape(n, nrhs)
+    assert b2.is_contiguous() and x2.is_contiguous()
+    return b2, x2, nrhs
+
+
+def _workspace(nbytes, nrhs, device):
+    """the driver's device workspace, its info record (2 + 2 nrhs doubles) and the current stream"""
+    return (torch.empty(nbytes, dtype=torch.uint8, device=device), np.zeros(2 + 2 * nrhs, dtype=np.float64),
+            torch.cuda.current_stream().cuda_stream)
+
+
+def _callback(precond):
+    """(gkomi_apply_fn, context) of a Preconditioner; (None, None): Identity"""
+    return (precond.fn, precond.ctx_ptr) if precond is not None else (None, None)
+
+
+def _report(info, x2, b, n):
+    """the result dict from a driver's info record; x in the shape b came in"""
+    res, base = info[2::2].copy(), info[3::2].copy()
+    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]), "converged": bool(info[1]),
+            "residual_norm": res, "baseline_norm": base,
+            "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
+
+
 def cg_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=1000, reduction=1e-10,
              baseline="rhs_norm", mode=1, check_every=16, strategy=0, max_row_nnz=-1,
              precond=None, precond_ctx=None):
     """Cg with Combined(Iteration(max_iters), ResidualNorm(reduction, baseline)).
 
-    b: (n,) or (n, nrhs) float64 device tensor.  precond: None (Identity) or an
-    integer address / ctypes function pointer of a gkomi_apply_fn.
+    b: (n,) or (n, nrhs) float64 device tensor.  precond: None (Identity), a Preconditioner, or an
+    integer address / ctypes function pointer of a gkomi_apply_fn with precond_ctx as its context.
     Returns dict(x, iterations, converged, residual_norm, baseline_norm, rel_residual)."""
-    b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
-    nrhs = b2.shape[1]
-    _check_precond(precond, nrhs)
+    b2, x2, nrhs = _operands(n, b, x, precond)
     if mode == 1 and nrhs != 1:
         mode = 0
-    if x is None:
-        x = torch.zeros_like(b2)
-    x2 = x.reshape(n, nrhs)
-    assert b2.is_contiguous() and x2.is_contiguous()
-    nnz = int(vals.numel())
     nbytes = gk.cg_workspace_bytes(n, nrhs)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-    info = np.zeros(2 + 2 * nrhs, dtype=np.float64)
-    stream = torch.cuda.current_stream().cuda_stream
-    pc = None
-    if precond is not None and hasattr(precond, "ctx_ptr"):
-        pc, precond_ctx = precond.fn, precond.ctx_ptr
-    elif precond is not None:
-        pc = ctypes.cast(precond, ctypes.c_void_p).value if not isinstance(precond, int) else precond
-    gk.cg_solve_f64_i32(stream, n, nrhs, nnz, row_ptrs, col_idxs, vals, strategy, max_row_nnz,
+    ws, info, stream = _workspace(nbytes, nrhs, b.device)
+    if hasattr(precond, "ctx_ptr"):
+        pc, precond_ctx = _callback(precond)
+    else:
+        pc = precond if precond is None or isinstance(precond, int) else ctypes.cast(precond, ctypes.c_void_p).value
+    gk.cg_solve_f64_i32(stream, n, nrhs, int(vals.numel()), row_ptrs, col_idxs, vals, strategy, max_row_nnz,
                         pc, precond_ctx, b2, x2, max_iters, reduction, BASELINES[baseline], mode,
                         check_every, ws, nbytes, info)
-    res = info[2::2].copy()
-    base = info[3::2].copy()
-    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]),
-            "converged": bool(info[1]), "residual_norm": res, "baseline_norm": base,
-            "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
+    return _report(info, x2, b, n)
 
 
 def krylov_solve(gk, solver, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=1000, reduction=1e-10,
                  baseline="rhs_norm", strategy=0, max_row_nnz=-1, precond=None, check_every=8, fused=False):
     """solver in {"bicgstab", "fcg", "cgs"}: {Bicgstab,Fcg,Cgs}::apply with
     Combined(Iteration(max_iters), ResidualNorm(reduction, baseline)); precond: None or a Preconditioner.
-    fused (bicgstab, one right-hand side): the 6-launch driver instead of the reference kernel sequence."""
+    fused (one right-hand side): the fused driver instead of the reference kernel sequence."""
     assert solver in ("bicgstab", "fcg", "cgs")
-    b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
-    nrhs = b2.shape[1]
-    _check_precond(precond, nrhs)
-    if x is None:
-        x = torch.zeros_like(b2)
-    x2 = x.reshape(n, nrhs)
-    assert b2.is_contiguous() and x2.is_contiguous()
-    nnz = int(vals.numel())
+    b2, x2, nrhs = _operands(n, b, x, precond)
+    assert nrhs == 1 or not fused
     nbytes = gk.krylov_workspace_bytes(n, nrhs)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-    info = np.zeros(2 + 2 * nrhs, dtype=np.float64)
-    stream = torch.cuda.current_stream().cuda_stream
-    fn = precond.fn if precond is not None else None
-    ctx = precond.ctx_ptr if precond is not None else None
-    if fused:
-        assert solver in ("bicgstab", "fcg", "cgs") and nrhs == 1
-        getattr(gk, solver + "_solve_fused_f64_i32")(stream, n, nnz, row_ptrs, col_idxs, vals, strategy, max_row_nnz, fn, ctx, b2, x2,
-                                        max_iters, reduction, BASELINES[baseline], check_every, ws, nbytes, info)
-    else:
-        getattr(gk, solver + "_solve_f64_i32")(stream, n, nrhs, nnz, row_ptrs, col_idxs, vals, strategy, max_row_nnz, fn,
-                                               ctx, b2, x2, max_iters, reduction, BASELINES[baseline], check_every, ws,
-                                               nbytes, info)
-    res, base = info[2::2].copy(), info[3::2].copy()
-    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]), "converged": bool(info[1]),
-            "residual_norm": res, "baseline_norm": base,
-            "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
+    ws, info, stream = _workspace(nbytes, nrhs, b.device)
+    lead = (stream, n) if fused else (stream, n, nrhs)
+    getattr(gk, solver + ("_solve_fused_f64_i32" if fused else "_solve_f64_i32"))(
+        *lead, int(vals.numel()), row_ptrs, col_idxs, vals, strategy, max_row_nnz, *_callback(precond), b2, x2,
+        max_iters, reduction, BASELINES[baseline], check_every, ws, nbytes, info)
+    return _report(info, x2, b, n)
 
 
 def bicg_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=1000, reduction=1e-10, baseline="rhs_norm",
@@ -101,51 +105,40 @@ def bicg_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=1000, reduc
     """Bicg::apply: the transposed system matrix is built once here (csr::transpose)
     unless `transposed` = (row_ptrs, col_idxs, vals) is given; precond_t is the
     transposed preconditioner (pass the same object for a symmetric one)."""
-    b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
-    nrhs = b2.shape[1]
-    _check_precond(precond, nrhs)
-    if x is None:
-        x = torch.zeros_like(b2)
-    x2 = x.reshape(n, nrhs)
-    nnz = int(vals.numel())
+    b2, x2, nrhs = _operands(n, b, x, precond, precond_t)
     trp, tci, tv = transposed if transposed is not None else _transpose(gk, n, row_ptrs, col_idxs, vals)
     nbytes = gk.krylov_workspace_bytes(n, nrhs)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-    info = np.zeros(2 + 2 * nrhs, dtype=np.float64)
-    stream = torch.cuda.current_stream().cuda_stream
-    args = [p.fn if p is not None else None for p in (precond, precond_t)]
-    ctxs = [p.ctx_ptr if p is not None else None for p in (precond, precond_t)]
-    gk.bicg_solve_f64_i32(stream, n, nrhs, nnz, row_ptrs, col_idxs, vals, trp, tci, tv, strategy, max_row_nnz, args[0],
-                          ctxs[0], args[1], ctxs[1], b2, x2, max_iters, reduction, BASELINES[baseline], check_every, ws,
-                          nbytes, info)
-    res, base = info[2::2].copy(), info[3::2].copy()
-    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]), "converged": bool(info[1]),
-            "residual_norm": res, "baseline_norm": base,
-            "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
+    ws, info, stream = _workspace(nbytes, nrhs, b.device)
+    gk.bicg_solve_f64_i32(stream, n, nrhs, int(vals.numel()), row_ptrs, col_idxs, vals, trp, tci, tv, strategy,
+                          max_row_nnz, *_callback(precond), *_callback(precond_t), b2, x2, max_iters, reduction,
+                          BASELINES[baseline], check_every, ws, nbytes, info)
+    return _report(info, x2, b, n)
 
 
 def ir_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, relaxation_factor=1.0, inner=None, max_iters=1000,
              reduction=1e-10, baseline="rhs_norm", strategy=0, max_row_nnz=-1):
     """Ir::apply with x as the initial guess; inner: None (Richardson) or a
     Preconditioner-like object whose apply approximates A^-1."""
-    b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
-    nrhs = b2.shape[1]
-    _check_precond(inner, nrhs)
-    if x is None:
-        x = torch.zeros_like(b2)
-    x2 = x.reshape(n, nrhs)
-    nnz = int(vals.numel())
+    b2, x2, nrhs = _operands(n, b, x, inner)
     nbytes = gk.krylov_workspace_bytes(n, nrhs)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-    info = np.zeros(2 + 2 * nrhs, dtype=np.float64)
-    stream = torch.cuda.current_stream().cuda_stream
-    gk.ir_solve_f64_i32(stream, n, nrhs, nnz, row_ptrs, col_idxs, vals, strategy, max_row_nnz,
-                        inner.fn if inner is not None else None, inner.ctx_ptr if inner is not None else None,
-                        relaxation_factor, b2, x2, max_iters, reduction, BASELINES[baseline], ws, nbytes, info)
-    res, base = info[2::2].copy(), info[3::2].copy()
-    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]), "converged": bool(info[1]),
-            "residual_norm": res, "baseline_norm": base,
-            "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
+    ws, info, stream = _workspace(nbytes, nrhs, b.device)
+    gk.ir_solve_f64_i32(stream, n, nrhs, int(vals.numel()), row_ptrs, col_idxs, vals, strategy, max_row_nnz,
+                        *_callback(inner), relaxation_factor, b2, x2, max_iters, reduction, BASELINES[baseline], ws,
+                        nbytes, info)
+    return _report(info, x2, b, n)
+
+
+def gmres_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, krylov_dim=100, max_iters=1000, reduction=1e-10,
+                baseline="rhs_norm", strategy=0, max_row_nnz=-1, precond=None):
+    """Gmres with Combined(Iteration(max_iters), ResidualNorm(reduction, baseline)).
+    precond: None or a Preconditioner."""
+    b2, x2, nrhs = _operands(n, b, x, precond)
+    nbytes = gk.gmres_workspace_bytes(n, nrhs, krylov_dim)
+    ws, info, stream = _workspace(nbytes, nrhs, b.device)
+    gk.gmres_solve_f64_i32(stream, n, nrhs, int(vals.numel()), row_ptrs, col_idxs, vals, strategy, max_row_nnz,
+                           *_callback(precond), b2, x2, krylov_dim, max_iters, reduction, BASELINES[baseline], ws,
+                           nbytes, info)
+    return _report(info, x2, b, n)
 
 
 def ir_mixed(gk, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=100, reduction=1e-12, baseline="rhs_norm",
@@ -155,19 +148,15 @@ def ir_mixed(gk, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=100, reductio
     initial guess: the outer residual and x stay in double, each correction comes from the fused float
     CG.  vals is the float64 value array; its float copy is made here for this call (one pass over the
     values).  Returns dict(x, iterations, converged, residual_norm, baseline_norm, rel_residual,
-    inner_iterations, inner_capped)."""
-    b2 = b.reshape(n, 1)
-    if x is None:
-        x = torch.zeros_like(b2)
-    x2 = x.reshape(n, 1)
-    assert b2.is_contiguous() and x2.is_contiguous()
+    inner_iterations, inner_capped) with float residual_norm / baseline_norm (one right-hand side)."""
+    b2, x2, _ = _operands(n, b.reshape(n, 1), x)
     nnz = int(vals.numel())
     stream = torch.cuda.current_stream().cuda_stream
     vals_f32 = torch.empty(nnz, dtype=torch.float32, device=vals.device)
     gk.dense_convert_f64_to_f32(stream, nnz, 1, vals, 1, vals_f32, 1)
     nbytes = gk.ir_mixed_workspace_bytes(n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-    info = np.zeros(6, dtype=np.float64)
+    info = np.zeros(6, dtype=np.float64)   # this driver's own record: one column and the two inner counts
     gk.ir_mixed_solve_f64_i32(stream, n, 1, nnz, row_ptrs, col_idxs, vals, vals_f32, strategy, max_row_nnz, b2, x2,
                               max_iters, reduction, BASELINES[baseline], inner_max_iters, inner_reduction,
                               BASELINES[inner_baseline], relaxation_factor, ws, nbytes, info)
@@ -195,24 +184,14 @@ def idr_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, subspace_dim=2, kappa=
     iterations (s + 1 applies of A each).  subspace: None or an s x n float64 device tensor, orthonormalised in place.
     fused (one right-hand side, s <= 8): the driver with 4 s + 2 launches per outer iteration instead of the
     reference kernel sequence.  matrix: a gkomi.formats object instead of the CSR arrays (solve_op)."""
-    b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
-    nrhs = b2.shape[1]
-    _check_precond(precond, nrhs)
-    if x is None:
-        x = torch.zeros_like(b2)
-    x2 = x.reshape(n, nrhs)
-    assert b2.is_contiguous() and x2.is_contiguous()
+    b2, x2, nrhs = _operands(n, b, x, precond)
     if subspace is None:
         subspace = idr_subspace(subspace_dim, n, b.device)
     assert subspace.dtype == torch.float64 and subspace.is_contiguous() and tuple(subspace.shape) == (subspace_dim, n)
     nbytes = gk.idr_workspace_bytes(n, nrhs, subspace_dim)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-    info = np.zeros(2 + 2 * nrhs, dtype=np.float64)
-    stream = torch.cuda.current_stream().cuda_stream
-    fn = precond.fn if precond is not None else None
-    ctx = precond.ctx_ptr if precond is not None else None
-    tail = (fn, ctx, subspace_dim, kappa, subspace, b2, x2, max_iters, reduction, BASELINES[baseline], check_every, ws,
-            nbytes, info)
+    ws, info, stream = _workspace(nbytes, nrhs, b.device)
+    tail = (*_callback(precond), subspace_dim, kappa, subspace, b2, x2, max_iters, reduction, BASELINES[baseline],
+            check_every, ws, nbytes, info)
     name = "idr_solve_fused" if fused else "idr_solve"
     if matrix is not None:
         cb = matrix.callback()
@@ -220,10 +199,7 @@ def idr_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, subspace_dim=2, kappa=
     else:
         getattr(gk, name + "_f64_i32")(stream, n, nrhs, int(vals.numel()), row_ptrs, col_idxs, vals, strategy, max_row_nnz,
                                        *tail)
-    res, base = info[2::2].copy(), info[3::2].copy()
-    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]), "converged": bool(info[1]),
-            "residual_norm": res, "baseline_norm": base,
-            "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
+    return _report(info, x2, b, n)
 
 
 def solve_op(gk, solver, matrix, b, x=None, max_iters=1000, reduction=1e-10, baseline="rhs_norm", precond=None,
@@ -235,48 +211,24 @@ def solve_op(gk, solver, matrix, b, x=None, max_iters=1000, reduction=1e-10, bas
         return idr_solve(gk, n, None, None, None, b, x=x, subspace_dim=subspace_dim, kappa=kappa, subspace=subspace,
                          max_iters=max_iters, reduction=reduction, baseline=baseline, precond=precond,
                          check_every=check_every, fused=fused, matrix=matrix)
-    b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
-    nrhs = b2.shape[1]
-    _check_precond(precond, nrhs)
-    if x is None:
-        x = torch.zeros_like(b2)
-    x2 = x.reshape(n, nrhs)
+    b2, x2, nrhs = _operands(n, b, x, precond)
     cb = matrix.callback()
-    info = np.zeros(2 + 2 * nrhs, dtype=np.float64)
-    stream = torch.cuda.current_stream().cuda_stream
-    fn = precond.fn if precond is not None else None
-    ctx = precond.ctx_ptr if precond is not None else None
-    if solver == "cg" and fused:
-        assert nrhs == 1
-        nbytes = gk.cg_workspace_bytes(n, 1)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-        gk.cg_solve_fused_op_f64(stream, n, cb.fn, cb.ctx_ptr, fn, ctx, b2, x2, max_iters, reduction,
-                                 BASELINES[baseline], check_every, ws, nbytes, info)
+    # per solver: its workspace size, then the arguments it takes before max_iters and whether it takes check_every
+    # (gmres has no fused driver; the fused ones take one right-hand side and no nrhs)
+    fused = fused and solver != "gmres"
+    assert nrhs == 1 or not fused
+    if solver == "gmres":
+        nbytes, dim, pace = gk.gmres_workspace_bytes(n, nrhs, krylov_dim), (krylov_dim,), ()
     elif solver == "cg":
-        nbytes = gk.cg_workspace_bytes(n, nrhs)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-        gk.cg_solve_op_f64(stream, n, nrhs, cb.fn, cb.ctx_ptr, fn, ctx, b2, x2, max_iters, reduction, BASELINES[baseline],
-                           ws, nbytes, info)
-    elif solver == "gmres":
-        nbytes = gk.gmres_workspace_bytes(n, nrhs, krylov_dim)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-        gk.gmres_solve_op_f64(stream, n, nrhs, cb.fn, cb.ctx_ptr, fn, ctx, b2, x2, krylov_dim, max_iters, reduction,
-                              BASELINES[baseline], ws, nbytes, info)
-    elif fused:
-        assert solver in ("bicgstab", "fcg", "cgs") and nrhs == 1
-        nbytes = gk.krylov_workspace_bytes(n, 1)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-        getattr(gk, solver + "_solve_fused_op_f64")(stream, n, cb.fn, cb.ctx_ptr, fn, ctx, b2, x2, max_iters, reduction,
-                                       BASELINES[baseline], check_every, ws, nbytes, info)
+        nbytes, dim, pace = gk.cg_workspace_bytes(n, nrhs), (), ((check_every,) if fused else ())
     else:
-        nbytes = gk.krylov_workspace_bytes(n, nrhs)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-        getattr(gk, solver + "_solve_op_f64")(stream, n, nrhs, cb.fn, cb.ctx_ptr, fn, ctx, b2, x2, max_iters, reduction,
-                                              BASELINES[baseline], check_every, ws, nbytes, info)
-    res, base = info[2::2].copy(), info[3::2].copy()
-    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]), "converged": bool(info[1]),
-            "residual_norm": res, "baseline_norm": base,
-            "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
+        nbytes, dim, pace = gk.krylov_workspace_bytes(n, nrhs), (), (check_every,)
+    ws, info, stream = _workspace(nbytes, nrhs, b.device)
+    lead = (stream, n) if fused else (stream, n, nrhs)
+    getattr(gk, solver + ("_solve_fused_op_f64" if fused else "_solve_op_f64"))(
+        *lead, cb.fn, cb.ctx_ptr, *_callback(precond), b2, x2, *dim, max_iters, reduction, BASELINES[baseline], *pace,
+        ws, nbytes, info)
+    return _report(info, x2, b, n)
 
 
 class JacobiCtx(ctypes.Structure):
@@ -531,31 +483,6 @@ def ilu_from_factors(gk, n, L, U, nrhs=1, l_unit_diag=False, analyse=True, brick
     p = Preconditioner(gk, "gkomi_ilu_apply_cb", ctx, (L, U, inter, tws, pl, pu, bl, bu))
     p.l_plan, p.u_plan, p.l_bricks, p.u_bricks = pl, pu, bl, bu
     return p
-
-
-def gmres_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, krylov_dim=100, max_iters=1000, reduction=1e-10,
-                baseline="rhs_norm", strategy=0, max_row_nnz=-1, precond=None):
-    """Gmres with Combined(Iteration(max_iters), ResidualNorm(reduction, baseline)).
-    precond: None or a Preconditioner."""
-    b2 = b.reshape(n, -1) if n > 0 else b.reshape(0, b.shape[1] if b.dim() > 1 else 1)
-    nrhs = b2.shape[1]
-    _check_precond(precond, nrhs)
-    if x is None:
-        x = torch.zeros_like(b2)
-    x2 = x.reshape(n, nrhs)
-    nnz = int(vals.numel())
-    nbytes = gk.gmres_workspace_bytes(n, nrhs, krylov_dim)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-    info = np.zeros(2 + 2 * nrhs, dtype=np.float64)
-    stream = torch.cuda.current_stream().cuda_stream
-    fn = precond.fn if precond is not None else None
-    ctx = precond.ctx_ptr if precond is not None else None
-    gk.gmres_solve_f64_i32(stream, n, nrhs, nnz, row_ptrs, col_idxs, vals, strategy, max_row_nnz, fn, ctx, b2, x2,
-                           krylov_dim, max_iters, reduction, BASELINES[baseline], ws, nbytes, info)
-    res, base = info[2::2].copy(), info[3::2].copy()
-    return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": int(info[0]), "converged": bool(info[1]),
-            "residual_norm": res, "baseline_norm": base,
-            "rel_residual": float(np.max(res / np.where(base == 0, 1.0, base)))}
 
 
 def _with_diagonal(gk, n, row_ptrs, col_idxs, vals):

@@ -2307,12 +2307,15 @@ public:
 };
 
 inline int baseline_code(stop::mode m) { return m == stop::mode::rhs_norm ? 0 : (m == stop::mode::initial_resnorm ? 1 : 2); }
-}  // namespace detail
 
-template <typename V = double>
-class Cg : public LinOp {
+// What Cg, Bicgstab / Fcg / Cgs, Idr, Bicg, Ir and Gmres share: the system matrix, the generated or given preconditioner,
+// the stop settings, the outcome of the last apply, the advanced apply and the frame of a plain apply.  A derived class
+// adds the parameters of its Factory, its workspace size and its one driver call.
+template <typename Derived>
+class iterative_solver : public LinOp {
 public:
-    class Factory : public detail::factory_base<Cg> {};
+    // a solver with factory parameters of its own declares its own Factory and build()
+    class Factory : public factory_base<Derived> {};
     static Factory build() { return Factory{}; }
     std::shared_ptr<const LinOp> get_system_matrix() const { return A_; }
     std::shared_ptr<const LinOp> get_preconditioner() const { return precond_; }
@@ -2322,132 +2325,14 @@ public:
     // what the criteria of the factory amount to (the role of get_stop_criterion_factory())
     const stop::criterion_settings& get_stop_settings() const noexcept { return settings_; }
 protected:
-    friend class detail::factory_base<Cg>;
-    Cg(const Factory* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings())
-    {
-        if (size_[0] != size_[1]) throw DimensionMismatch(__FILE__, __LINE__, "Cg needs a square system matrix");
-        precond_ = f->precond_ ? f->precond_ : (f->precond_factory_ ? std::shared_ptr<const LinOp>(f->precond_factory_->generate_impl(A_)) : nullptr);
-    }
-    void apply_impl(const LinOp* b, LinOp* x) const override { solve_as(V{}, b, x); }
-    // Cg<float>: the single-precision instantiation -- the reference's kernel sequence on the _f32 kernels (gkomi_cg_solve_f32):
-    // a Csr<float, int32> system matrix, Dense<float> vectors with one column, no preconditioner, Iteration + ResidualNorm
-    void solve_as(float, const LinOp* b, LinOp* x) const
-    {
-        ::gko::detail::require_device(exec_, "cg::apply");
-        auto A = dynamic_cast<const matrix::Csr<float, int32>*>(A_.get());
-        auto db = dynamic_cast<const matrix::Dense<float>*>(b);
-        auto dx = dynamic_cast<matrix::Dense<float>*>(x);
-        auto db64 = A ? dynamic_cast<const matrix::Dense<double>*>(b) : nullptr;
-        auto dx64 = A ? dynamic_cast<matrix::Dense<double>*>(x) : nullptr;
-        if (db64 && dx64) {
-            // Dense<double> operands: through temporary float copies (precision_dispatch, precision_dispatch.hpp:73-96)
-            auto bf = matrix::Dense<float>::create(exec_, db64->get_size());
-            auto xf = matrix::Dense<float>::create(exec_, dx64->get_size());
-            db64->convert_to(bf.get());
-            dx64->convert_to(xf.get());
-            solve_as(float{}, bf.get(), xf.get());
-            xf->convert_to(dx64);
-            return;
-        }
-        if (!A || !db || !dx || precond_ || settings_.implicit || db->get_size()[1] != 1 || db->get_stride() != 1 || dx->get_stride() != 1) {
-            GKO_NOT_SUPPORTED("Cg<float>: Csr<float, int32> system, Dense<float> vectors of one contiguous column, Iteration + ResidualNorm, no preconditioner");
-        }
-        const int64_t n = size_[0];
-        array<char> ws(exec_, gkomi_cg_workspace_bytes_f32(n));
-        double info[4] = {};
-        GKOMI_CALL(gkomi_cg_solve_f32(nullptr, n, static_cast<int64_t>(A->get_num_stored_elements()), A->get_const_row_ptrs(), A->get_const_col_idxs(),
-                                      A->get_const_values(), db->get_const_values(), dx->get_values(), settings_.max_iters,
-                                      static_cast<float>(settings_.reduction_factor), detail::baseline_code(settings_.baseline), ws.get_data(),
-                                      ws.get_num_elems(), info));
-        last_iters_ = static_cast<int64_t>(info[0]);
-        last_converged_ = info[1] != 0.0;
-    }
-    void solve_as(double, const LinOp* b, LinOp* x) const
-    {
-        ::gko::detail::require_device(exec_, "cg::apply");
-        if (auto ds = dynamic_cast<const ::gko::detail::distributed_system*>(A_.get())) {
-            // experimental::distributed::Matrix + Vectors: the row-partitioned driver
-            ds->cg_solve(b, x, settings_, precond_.get(), &last_iters_, &last_converged_);
-            return;
-        }
-        auto db = matrix::detail_fmt::dense(b); auto dx = matrix::detail_fmt::dense(x);
-        const int64_t n = size_[0], nrhs = db->cols();
-        if (db->get_stride() != static_cast<size_type>(nrhs) || dx->get_stride() != static_cast<size_type>(nrhs)) GKO_NOT_SUPPORTED("solver vectors must be contiguous (stride == #columns)");
-        array<char> ws(exec_, gkomi_cg_workspace_bytes(n, nrhs));
-        std::vector<double> info(2 + 2 * nrhs, 0.0);
-        ::gko::detail::precond_callback cb(precond_.get(), exec_, static_cast<size_type>(n), static_cast<size_type>(nrhs));
-        auto pfn = cb.fn;
-        void* pctx = cb.ctx;
-        // a Csr system matrix travels as its record (srow, row statistic): detail::system_callback
-        ::gko::detail::system_callback mcb(A_.get(), exec_, static_cast<size_type>(n));
-        if (nrhs == 1) {  // the fused loop; Ell / Sellp with the dot in the SpMV's epilogue
-            GKOMI_CALL(gkomi_cg_solve_fused_op_f64(nullptr, n, mcb.fn, mcb.ctx, pfn, pctx, db->get_const_values(), dx->get_values(), settings_.max_iters,
-                                                   settings_.reduction_factor, detail::baseline_code(settings_.baseline), 8, ws.get_data(), ws.get_num_elems(), info.data()));
-        } else {
-            GKOMI_CALL(gkomi_cg_solve_op_f64(nullptr, n, nrhs, mcb.fn, mcb.ctx, pfn, pctx, db->get_const_values(), dx->get_values(), settings_.max_iters,
-                                             settings_.reduction_factor, detail::baseline_code(settings_.baseline), ws.get_data(), ws.get_num_elems(), info.data()));
-        }
-        last_iters_ = static_cast<int64_t>(info[0]);
-        last_converged_ = info[1] != 0.0;
-    }
-    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override { advanced_as(V{}, alpha, b, beta, x); }
-    void advanced_as(float, const LinOp*, const LinOp*, const LinOp*, LinOp*) const { GKO_NOT_SUPPORTED("Cg<float>: plain apply only"); }
-    void advanced_as(double, const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const
-    {
-        // x = alpha * solve(b) + beta * x  (core/solver/cg.cpp:196-210)
-        auto dx = matrix::detail_fmt::dense(x);
-        auto x_clone = dx->clone();
-        this->apply_impl(b, x_clone.get());
-        dx->scale(matrix::detail_fmt::dense(beta));
-        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
-    }
-    std::shared_ptr<const LinOp> A_;
-    std::shared_ptr<const LinOp> precond_;
-    stop::criterion_settings settings_;
-    mutable int64_t last_iters_{-1};
-    mutable bool last_converged_{false};
-};
-
-// Bicgstab / Fcg / Cgs (include/ginkgo/core/solver/{bicgstab,fcg,cgs}.hpp): same
-// factory parameters as Cg, native drivers of csrc/krylov.hip
-namespace detail {
-using krylov_driver = int (*)(gkomi_stream_t, int64_t, int64_t, int64_t, const int32_t*, const int32_t*, const double*, int, int64_t, gkomi_apply_fn, void*,
-                              const double*, double*, int64_t, double, int, int64_t, void*, size_t, double*);
-using krylov_op_driver = int (*)(gkomi_stream_t, int64_t, int64_t, gkomi_matrix_apply_fn, void*, gkomi_apply_fn, void*, const double*, double*, int64_t, double, int, int64_t,
-                                 void*, size_t, double*);
-template <typename Derived, krylov_driver Driver, krylov_op_driver OpDriver>
-class krylov_solver : public LinOp {
-public:
-    class Factory : public factory_base<Derived> {};
-    static Factory build() { return Factory{}; }
-    std::shared_ptr<const LinOp> get_system_matrix() const { return A_; }
-    std::shared_ptr<const LinOp> get_preconditioner() const { return precond_; }
-    int64_t get_last_iteration_count() const noexcept { return last_iters_; }
-    bool has_converged() const noexcept { return last_converged_; }
-protected:
-    krylov_solver(const Factory* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings())
+    template <typename F>
+    iterative_solver(const F* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings())
     {
         if (size_[0] != size_[1]) throw DimensionMismatch(__FILE__, __LINE__, "the solver needs a square system matrix");
         precond_ = f->precond_ ? f->precond_ : (f->precond_factory_ ? std::shared_ptr<const LinOp>(f->precond_factory_->generate_impl(A_)) : nullptr);
     }
-    void apply_impl(const LinOp* b, LinOp* x) const override
-    {
-        ::gko::detail::require_device(exec_, "solver::apply");
-        auto db = matrix::detail_fmt::dense(b); auto dx = matrix::detail_fmt::dense(x);
-        const int64_t n = size_[0], nrhs = db->cols();
-        if (db->get_stride() != static_cast<size_type>(nrhs) || dx->get_stride() != static_cast<size_type>(nrhs)) GKO_NOT_SUPPORTED("solver vectors must be contiguous (stride == #columns)");
-        array<char> ws(exec_, gkomi_krylov_workspace_bytes(n, nrhs));
-        std::vector<double> info(2 + 2 * nrhs, 0.0);
-        ::gko::detail::precond_callback cb(precond_.get(), exec_, static_cast<size_type>(n), static_cast<size_type>(nrhs));
-        auto pfn = cb.fn;
-        void* pctx = cb.ctx;
-        // a Csr system matrix travels as its record (srow, row statistic): detail::system_callback
-        ::gko::detail::system_callback mcb(A_.get(), exec_, static_cast<size_type>(n));
-        GKOMI_CALL(OpDriver(nullptr, n, nrhs, mcb.fn, mcb.ctx, pfn, pctx, db->get_const_values(), dx->get_values(), settings_.max_iters,
-                            settings_.reduction_factor, baseline_code(settings_.baseline), 8, ws.get_data(), ws.get_num_elems(), info.data()));
-        last_iters_ = static_cast<int64_t>(info[0]);
-        last_converged_ = info[1] != 0.0;
-    }
+    using LinOp::apply_impl;
+    // x = alpha * solve(b) + beta * x  (core/solver/cg.cpp:196-210)
     void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
     {
         auto dx = matrix::detail_fmt::dense(x);
@@ -2456,6 +2341,41 @@ protected:
         dx->scale(matrix::detail_fmt::dense(beta));
         dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
     }
+    // the first two entries of a driver's info record
+    void report(const double* info) const
+    {
+        last_iters_ = static_cast<int64_t>(info[0]);
+        last_converged_ = info[1] != 0.0;
+    }
+    // The operands of a plain apply on the device: b and x as contiguous Dense<double>, their sizes, the info record.
+    struct operands {
+        const iterative_solver& solver;
+        const matrix::Dense<double>* db;
+        matrix::Dense<double>* dx;
+        int64_t n, nrhs;
+        std::vector<double> info;
+        operands(const iterative_solver& s, const LinOp* b, LinOp* x) : solver(s)
+        {
+            ::gko::detail::require_device(s.exec_, "solver::apply");
+            db = matrix::detail_fmt::dense(b);
+            dx = matrix::detail_fmt::dense(x);
+            n = s.size_[0];
+            nrhs = db->cols();
+            if (db->get_stride() != static_cast<size_type>(nrhs) || dx->get_stride() != static_cast<size_type>(nrhs)) GKO_NOT_SUPPORTED("solver vectors must be contiguous (stride == #columns)");
+            info.assign(2 + 2 * nrhs, 0.0);
+        }
+        void report() const { solver.report(info.data()); }
+    };
+    // ... and the two callbacks of the *_solve_op_f64 drivers: the preconditioner (detail::precond_callback) and the
+    // system matrix, a Csr as its record with srow and row statistic (detail::system_callback)
+    struct frame : operands {
+        ::gko::detail::precond_callback precond;
+        ::gko::detail::system_callback system;
+        frame(const iterative_solver& s, const LinOp* b, LinOp* x)
+            : operands(s, b, x), precond(s.precond_.get(), s.exec_, static_cast<size_type>(this->n), static_cast<size_type>(this->nrhs)),
+              system(s.A_.get(), s.exec_, static_cast<size_type>(this->n))
+        {}
+    };
     std::shared_ptr<const LinOp> A_;
     std::shared_ptr<const LinOp> precond_;
     stop::criterion_settings settings_;
@@ -2464,58 +2384,110 @@ protected:
 };
 }  // namespace detail
 
-#define GKOMI_KRYLOV_SOLVER(Name, driver, op_driver)                                               \
+template <typename V = double>
+class Cg : public detail::iterative_solver<Cg<V>> {
+    using base = detail::iterative_solver<Cg<V>>;
+protected:
+    friend class detail::factory_base<Cg>;
+    Cg(const typename base::Factory* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A)) {}
+    using base::apply_impl;
+    void apply_impl(const LinOp* b, LinOp* x) const override { solve_as(V{}, b, x); }
+    // Cg<float>: the single-precision instantiation -- the reference's kernel sequence on the _f32 kernels (gkomi_cg_solve_f32):
+    // a Csr<float, int32> system matrix, Dense<float> vectors with one column, no preconditioner, Iteration + ResidualNorm
+    void solve_as(float, const LinOp* b, LinOp* x) const
+    {
+        const auto& exec = this->exec_;
+        const auto& st = this->settings_;
+        ::gko::detail::require_device(exec, "cg::apply");
+        auto A = dynamic_cast<const matrix::Csr<float, int32>*>(this->A_.get());
+        auto db = dynamic_cast<const matrix::Dense<float>*>(b);
+        auto dx = dynamic_cast<matrix::Dense<float>*>(x);
+        auto db64 = A ? dynamic_cast<const matrix::Dense<double>*>(b) : nullptr;
+        auto dx64 = A ? dynamic_cast<matrix::Dense<double>*>(x) : nullptr;
+        if (db64 && dx64) {
+            // Dense<double> operands: through temporary float copies (precision_dispatch, precision_dispatch.hpp:73-96)
+            auto bf = matrix::Dense<float>::create(exec, db64->get_size());
+            auto xf = matrix::Dense<float>::create(exec, dx64->get_size());
+            db64->convert_to(bf.get());
+            dx64->convert_to(xf.get());
+            solve_as(float{}, bf.get(), xf.get());
+            xf->convert_to(dx64);
+            return;
+        }
+        if (!A || !db || !dx || this->precond_ || st.implicit || db->get_size()[1] != 1 || db->get_stride() != 1 || dx->get_stride() != 1) {
+            GKO_NOT_SUPPORTED("Cg<float>: Csr<float, int32> system, Dense<float> vectors of one contiguous column, Iteration + ResidualNorm, no preconditioner");
+        }
+        const int64_t n = this->size_[0];
+        array<char> ws(exec, gkomi_cg_workspace_bytes_f32(n));
+        double info[4] = {};
+        GKOMI_CALL(gkomi_cg_solve_f32(nullptr, n, static_cast<int64_t>(A->get_num_stored_elements()), A->get_const_row_ptrs(), A->get_const_col_idxs(),
+                                      A->get_const_values(), db->get_const_values(), dx->get_values(), st.max_iters,
+                                      static_cast<float>(st.reduction_factor), detail::baseline_code(st.baseline), ws.get_data(),
+                                      ws.get_num_elems(), info));
+        this->report(info);
+    }
+    void solve_as(double, const LinOp* b, LinOp* x) const
+    {
+        const auto& st = this->settings_;
+        if (auto ds = dynamic_cast<const ::gko::detail::distributed_system*>(this->A_.get())) {
+            // experimental::distributed::Matrix + Vectors: the row-partitioned driver
+            ds->cg_solve(b, x, st, this->precond_.get(), &this->last_iters_, &this->last_converged_);
+            return;
+        }
+        typename base::frame f(*this, b, x);
+        array<char> ws(this->exec_, gkomi_cg_workspace_bytes(f.n, f.nrhs));
+        if (f.nrhs == 1) {  // the fused loop; Ell / Sellp with the dot in the SpMV's epilogue
+            GKOMI_CALL(gkomi_cg_solve_fused_op_f64(nullptr, f.n, f.system.fn, f.system.ctx, f.precond.fn, f.precond.ctx, f.db->get_const_values(), f.dx->get_values(),
+                                                   st.max_iters, st.reduction_factor, detail::baseline_code(st.baseline), 8, ws.get_data(), ws.get_num_elems(), f.info.data()));
+        } else {
+            GKOMI_CALL(gkomi_cg_solve_op_f64(nullptr, f.n, f.nrhs, f.system.fn, f.system.ctx, f.precond.fn, f.precond.ctx, f.db->get_const_values(), f.dx->get_values(),
+                                             st.max_iters, st.reduction_factor, detail::baseline_code(st.baseline), ws.get_data(), ws.get_num_elems(), f.info.data()));
+        }
+        f.report();
+    }
+};
+
+// Bicgstab / Fcg / Cgs (include/ginkgo/core/solver/{bicgstab,fcg,cgs}.hpp): same factory parameters as Cg, native
+// drivers of csrc/krylov.hip -- the fused one for one right-hand side, the reference kernel sequence otherwise
+namespace detail {
+using krylov_fused_op_driver = int (*)(gkomi_stream_t, int64_t, gkomi_matrix_apply_fn, void*, gkomi_apply_fn, void*, const double*, double*, int64_t, double, int, int64_t,
+                                       void*, size_t, double*);
+using krylov_op_driver = int (*)(gkomi_stream_t, int64_t, int64_t, gkomi_matrix_apply_fn, void*, gkomi_apply_fn, void*, const double*, double*, int64_t, double, int, int64_t,
+                                 void*, size_t, double*);
+template <typename Derived, krylov_fused_op_driver FusedOpDriver, krylov_op_driver OpDriver>
+class krylov_solver : public iterative_solver<Derived> {
+protected:
+    using base = iterative_solver<Derived>;
+    template <typename F>
+    krylov_solver(const F* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A)) {}
+    using base::apply_impl;
+    void apply_impl(const LinOp* b, LinOp* x) const override
+    {
+        const auto& st = this->settings_;
+        typename base::frame f(*this, b, x);
+        array<char> ws(this->exec_, gkomi_krylov_workspace_bytes(f.n, f.nrhs));
+        if (f.nrhs == 1) {
+            GKOMI_CALL(FusedOpDriver(nullptr, f.n, f.system.fn, f.system.ctx, f.precond.fn, f.precond.ctx, f.db->get_const_values(), f.dx->get_values(), st.max_iters,
+                                     st.reduction_factor, baseline_code(st.baseline), 8, ws.get_data(), ws.get_num_elems(), f.info.data()));
+        } else {
+            GKOMI_CALL(OpDriver(nullptr, f.n, f.nrhs, f.system.fn, f.system.ctx, f.precond.fn, f.precond.ctx, f.db->get_const_values(), f.dx->get_values(), st.max_iters,
+                                st.reduction_factor, baseline_code(st.baseline), 8, ws.get_data(), ws.get_num_elems(), f.info.data()));
+        }
+        f.report();
+    }
+};
+}  // namespace detail
+
+#define GKOMI_KRYLOV_SOLVER(Name, fused_op_driver, op_driver)                                      \
     template <typename V = double>                                                                 \
-    class Name : public detail::krylov_solver<Name<V>, driver, op_driver> {                        \
-        using base = detail::krylov_solver<Name<V>, driver, op_driver>;                            \
+    class Name : public detail::krylov_solver<Name<V>, fused_op_driver, op_driver> {               \
+        using base = detail::krylov_solver<Name<V>, fused_op_driver, op_driver>;                   \
         friend class detail::factory_base<Name>;                                                   \
         Name(const typename base::Factory* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A)) {} \
     }
-namespace detail {
-// one right-hand side: the fused 6-launch BiCGSTAB driver (csrc/krylov.hip)
-inline int bicgstab_driver(gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* v, int strategy, int64_t hint,
-                           gkomi_apply_fn pfn, void* pctx, const double* b, double* x, int64_t max_iters, double reduction, int baseline, int64_t check_every, void* ws,
-                           size_t ws_bytes, double* info)
-{
-    if (nrhs == 1) return gkomi_bicgstab_solve_fused_f64_i32(s, n, nnz, rp, ci, v, strategy, hint, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-    return gkomi_bicgstab_solve_f64_i32(s, n, nrhs, nnz, rp, ci, v, strategy, hint, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-}
-inline int bicgstab_op_driver(gkomi_stream_t s, int64_t n, int64_t nrhs, gkomi_matrix_apply_fn mfn, void* mctx, gkomi_apply_fn pfn, void* pctx, const double* b, double* x,
-                              int64_t max_iters, double reduction, int baseline, int64_t check_every, void* ws, size_t ws_bytes, double* info)
-{
-    if (nrhs == 1) return gkomi_bicgstab_solve_fused_op_f64(s, n, mfn, mctx, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-    return gkomi_bicgstab_solve_op_f64(s, n, nrhs, mfn, mctx, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-}
-inline int fcg_driver(gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* v, int strategy, int64_t hint,
-                      gkomi_apply_fn pfn, void* pctx, const double* b, double* x, int64_t max_iters, double reduction, int baseline, int64_t check_every, void* ws,
-                      size_t ws_bytes, double* info)
-{
-    if (nrhs == 1) return gkomi_fcg_solve_fused_f64_i32(s, n, nnz, rp, ci, v, strategy, hint, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-    return gkomi_fcg_solve_f64_i32(s, n, nrhs, nnz, rp, ci, v, strategy, hint, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-}
-inline int fcg_op_driver(gkomi_stream_t s, int64_t n, int64_t nrhs, gkomi_matrix_apply_fn mfn, void* mctx, gkomi_apply_fn pfn, void* pctx, const double* b, double* x,
-                         int64_t max_iters, double reduction, int baseline, int64_t check_every, void* ws, size_t ws_bytes, double* info)
-{
-    if (nrhs == 1) return gkomi_fcg_solve_fused_op_f64(s, n, mfn, mctx, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-    return gkomi_fcg_solve_op_f64(s, n, nrhs, mfn, mctx, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-}
-inline int cgs_driver(gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* v, int strategy, int64_t hint,
-                      gkomi_apply_fn pfn, void* pctx, const double* b, double* x, int64_t max_iters, double reduction, int baseline, int64_t check_every, void* ws,
-                      size_t ws_bytes, double* info)
-{
-    if (nrhs == 1) return gkomi_cgs_solve_fused_f64_i32(s, n, nnz, rp, ci, v, strategy, hint, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-    return gkomi_cgs_solve_f64_i32(s, n, nrhs, nnz, rp, ci, v, strategy, hint, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-}
-inline int cgs_op_driver(gkomi_stream_t s, int64_t n, int64_t nrhs, gkomi_matrix_apply_fn mfn, void* mctx, gkomi_apply_fn pfn, void* pctx, const double* b, double* x,
-                         int64_t max_iters, double reduction, int baseline, int64_t check_every, void* ws, size_t ws_bytes, double* info)
-{
-    if (nrhs == 1) return gkomi_cgs_solve_fused_op_f64(s, n, mfn, mctx, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-    return gkomi_cgs_solve_op_f64(s, n, nrhs, mfn, mctx, pfn, pctx, b, x, max_iters, reduction, baseline, check_every, ws, ws_bytes, info);
-}
-}  // namespace detail
-GKOMI_KRYLOV_SOLVER(Bicgstab, detail::bicgstab_driver, detail::bicgstab_op_driver);
-GKOMI_KRYLOV_SOLVER(Fcg, detail::fcg_driver, detail::fcg_op_driver);
-GKOMI_KRYLOV_SOLVER(Cgs, detail::cgs_driver, detail::cgs_op_driver);
+GKOMI_KRYLOV_SOLVER(Bicgstab, gkomi_bicgstab_solve_fused_op_f64, gkomi_bicgstab_solve_op_f64);
+GKOMI_KRYLOV_SOLVER(Fcg, gkomi_fcg_solve_fused_op_f64, gkomi_fcg_solve_op_f64);
+GKOMI_KRYLOV_SOLVER(Cgs, gkomi_cgs_solve_fused_op_f64, gkomi_cgs_solve_op_f64);
 #undef GKOMI_KRYLOV_SOLVER
 
 // Idr (include/ginkgo/core/solver/idr.hpp): IDR(s) with a real subspace, native drivers of csrc/idr.hip (the fused
@@ -2524,7 +2496,8 @@ GKOMI_KRYLOV_SOLVER(Cgs, detail::cgs_driver, detail::cgs_op_driver);
 // std::random_device otherwise; the device orthonormalises its rows.  get_last_iteration_count() counts outer
 // iterations (s + 1 applies of the system matrix each).
 template <typename V = double>
-class Idr : public LinOp {
+class Idr : public detail::iterative_solver<Idr<V>> {
+    using base = detail::iterative_solver<Idr<V>>;
 public:
     class Factory : public detail::factory_base<Idr> {
     public:
@@ -2541,62 +2514,38 @@ public:
         bool deterministic_{false};
     };
     static Factory build() { return Factory{}; }
-    std::shared_ptr<const LinOp> get_system_matrix() const { return A_; }
-    std::shared_ptr<const LinOp> get_preconditioner() const { return precond_; }
     size_type get_subspace_dim() const noexcept { return subspace_dim_; }
     V get_kappa() const noexcept { return kappa_; }
     bool get_deterministic() const noexcept { return deterministic_; }
     bool get_complex_subspace() const noexcept { return false; }
-    int64_t get_last_iteration_count() const noexcept { return last_iters_; }
-    bool has_converged() const noexcept { return last_converged_; }
 protected:
     friend class detail::factory_base<Idr>;
-    Idr(const Factory* f, std::shared_ptr<const LinOp> A)
-        : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings()), subspace_dim_(f->subspace_dim_), kappa_(f->kappa_),
-          deterministic_(f->deterministic_)
+    Idr(const Factory* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A)), subspace_dim_(f->subspace_dim_), kappa_(f->kappa_), deterministic_(f->deterministic_)
     {
         static_assert(std::is_same<V, double>::value, "Idr: fp64 only");
-        if (size_[0] != size_[1]) throw DimensionMismatch(__FILE__, __LINE__, "Idr needs a square system matrix");
-        precond_ = f->precond_ ? f->precond_ : (f->precond_factory_ ? std::shared_ptr<const LinOp>(f->precond_factory_->generate_impl(A_)) : nullptr);
     }
+    using base::apply_impl;
     void apply_impl(const LinOp* b, LinOp* x) const override
     {
-        ::gko::detail::require_device(exec_, "idr::apply");
-        auto db = matrix::detail_fmt::dense(b); auto dx = matrix::detail_fmt::dense(x);
-        const int64_t n = size_[0], nrhs = db->cols(), s = static_cast<int64_t>(subspace_dim_);
-        if (db->get_stride() != static_cast<size_type>(nrhs) || dx->get_stride() != static_cast<size_type>(nrhs)) GKO_NOT_SUPPORTED("solver vectors must be contiguous (stride == #columns)");
-        std::vector<double> host_p(static_cast<size_t>(s * n));
+        const auto& exec = this->exec_;
+        const auto& st = this->settings_;
+        typename base::frame f(*this, b, x);
+        const int64_t s = static_cast<int64_t>(subspace_dim_);
+        std::vector<double> host_p(static_cast<size_t>(s * f.n));
         std::default_random_engine engine(deterministic_ ? 15u : std::random_device{}());
         std::normal_distribution<> dist(0.0, 1.0);
         for (auto& v : host_p) v = dist(engine);
-        array<double> p(exec_, host_p.size());
-        exec_->copy_from(exec_->get_master().get(), host_p.size(), host_p.data(), p.get_data());
-        array<char> ws(exec_, gkomi_idr_workspace_bytes(n, nrhs, s));
-        std::vector<double> info(2 + 2 * nrhs, 0.0);
-        ::gko::detail::precond_callback cb(precond_.get(), exec_, static_cast<size_type>(n), static_cast<size_type>(nrhs));
-        ::gko::detail::system_callback mcb(A_.get(), exec_, static_cast<size_type>(n));
-        auto driver = nrhs == 1 && s <= 8 ? &gkomi_idr_solve_fused_op_f64 : &gkomi_idr_solve_op_f64;
-        GKOMI_CALL(driver(nullptr, n, nrhs, mcb.fn, mcb.ctx, cb.fn, cb.ctx, s, kappa_, p.get_data(), db->get_const_values(), dx->get_values(), settings_.max_iters,
-                          settings_.reduction_factor, detail::baseline_code(settings_.baseline), 8, ws.get_data(), ws.get_num_elems(), info.data()));
-        last_iters_ = static_cast<int64_t>(info[0]);
-        last_converged_ = info[1] != 0.0;
+        array<double> p(exec, host_p.size());
+        exec->copy_from(exec->get_master().get(), host_p.size(), host_p.data(), p.get_data());
+        array<char> ws(exec, gkomi_idr_workspace_bytes(f.n, f.nrhs, s));
+        auto driver = f.nrhs == 1 && s <= 8 ? &gkomi_idr_solve_fused_op_f64 : &gkomi_idr_solve_op_f64;
+        GKOMI_CALL(driver(nullptr, f.n, f.nrhs, f.system.fn, f.system.ctx, f.precond.fn, f.precond.ctx, s, kappa_, p.get_data(), f.db->get_const_values(), f.dx->get_values(),
+                          st.max_iters, st.reduction_factor, detail::baseline_code(st.baseline), 8, ws.get_data(), ws.get_num_elems(), f.info.data()));
+        f.report();
     }
-    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
-    {
-        auto dx = matrix::detail_fmt::dense(x);
-        auto x_clone = dx->clone();
-        this->apply_impl(b, x_clone.get());
-        dx->scale(matrix::detail_fmt::dense(beta));
-        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
-    }
-    std::shared_ptr<const LinOp> A_;
-    std::shared_ptr<const LinOp> precond_;
-    stop::criterion_settings settings_;
     size_type subspace_dim_;
     V kappa_;
     bool deterministic_;
-    mutable int64_t last_iters_{-1};
-    mutable bool last_converged_{false};
 };
 
 // Bicg (include/ginkgo/core/solver/bicg.hpp): the transposed system matrix is
@@ -2604,67 +2553,47 @@ protected:
 // the transposed preconditioner (bicg.cpp:169-171 asks the preconditioner for its
 // Transposable interface: Jacobi here).
 template <typename V = double>
-class Bicg : public LinOp {
-public:
-    class Factory : public detail::factory_base<Bicg> {};
-    static Factory build() { return Factory{}; }
-    std::shared_ptr<const LinOp> get_system_matrix() const { return A_; }
-    int64_t get_last_iteration_count() const noexcept { return last_iters_; }
-    bool has_converged() const noexcept { return last_converged_; }
+class Bicg : public detail::iterative_solver<Bicg<V>> {
+    using base = detail::iterative_solver<Bicg<V>>;
 protected:
     friend class detail::factory_base<Bicg>;
-    Bicg(const Factory* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings())
+    Bicg(const typename base::Factory* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A))
     {
-        if (size_[0] != size_[1]) throw DimensionMismatch(__FILE__, __LINE__, "Bicg needs a square system matrix");
-        precond_ = f->precond_ ? f->precond_ : (f->precond_factory_ ? std::shared_ptr<const LinOp>(f->precond_factory_->generate_impl(A_)) : nullptr);
-        if (precond_) {
-            auto tr = dynamic_cast<const Transposable*>(precond_.get());
+        if (this->precond_) {
+            auto tr = dynamic_cast<const Transposable*>(this->precond_.get());
             if (tr == nullptr) GKO_NOT_SUPPORTED("Bicg: the preconditioner must be Transposable");
             precond_t_ = std::shared_ptr<const LinOp>(tr->conj_transpose());
         }
-        At_ = as<const matrix::Csr<V, int32>>(A_.get())->transpose();
+        At_ = as<const matrix::Csr<V, int32>>(this->A_.get())->transpose();
     }
+    using base::apply_impl;
     void apply_impl(const LinOp* b, LinOp* x) const override
     {
-        ::gko::detail::require_device(exec_, "bicg::apply");
-        auto csr = as<const matrix::Csr<V, int32>>(A_.get());
-        auto db = matrix::detail_fmt::dense(b); auto dx = matrix::detail_fmt::dense(x);
-        const int64_t n = size_[0], nrhs = db->cols();
-        if (db->get_stride() != static_cast<size_type>(nrhs) || dx->get_stride() != static_cast<size_type>(nrhs)) GKO_NOT_SUPPORTED("solver vectors must be contiguous (stride == #columns)");
-        array<char> ws(exec_, gkomi_krylov_workspace_bytes(n, nrhs));
-        std::vector<double> info(2 + 2 * nrhs, 0.0);
-        ::gko::detail::linop_callback cb{precond_.get(), exec_, static_cast<size_type>(n), static_cast<size_type>(nrhs)};
-        ::gko::detail::linop_callback cbt{precond_t_.get(), exec_, static_cast<size_type>(n), static_cast<size_type>(nrhs)};
-        auto pfn = precond_ ? &::gko::detail::linop_callback::call : nullptr;
-        GKOMI_CALL(gkomi_bicg_solve_f64_i32(nullptr, n, nrhs, csr->get_num_stored_elements(), csr->get_const_row_ptrs(), csr->get_const_col_idxs(), csr->get_const_values(),
+        const auto& st = this->settings_;
+        const bool pre = this->precond_ != nullptr;
+        typename base::operands f(*this, b, x);
+        auto csr = as<const matrix::Csr<V, int32>>(this->A_.get());
+        array<char> ws(this->exec_, gkomi_krylov_workspace_bytes(f.n, f.nrhs));
+        ::gko::detail::linop_callback cb{this->precond_.get(), this->exec_, static_cast<size_type>(f.n), static_cast<size_type>(f.nrhs)};
+        ::gko::detail::linop_callback cbt{precond_t_.get(), this->exec_, static_cast<size_type>(f.n), static_cast<size_type>(f.nrhs)};
+        auto pfn = pre ? &::gko::detail::linop_callback::call : nullptr;
+        GKOMI_CALL(gkomi_bicg_solve_f64_i32(nullptr, f.n, f.nrhs, csr->get_num_stored_elements(), csr->get_const_row_ptrs(), csr->get_const_col_idxs(), csr->get_const_values(),
                                             At_->get_const_row_ptrs(), At_->get_const_col_idxs(), At_->get_const_values(), csr->get_strategy()->get_code(), csr->get_max_row_nnz(),
-                                            pfn, precond_ ? &cb : nullptr, pfn, precond_ ? &cbt : nullptr, db->get_const_values(), dx->get_values(), settings_.max_iters, settings_.reduction_factor,
-                                            detail::baseline_code(settings_.baseline), 8, ws.get_data(), ws.get_num_elems(), info.data()));
-        last_iters_ = static_cast<int64_t>(info[0]);
-        last_converged_ = info[1] != 0.0;
+                                            pfn, pre ? &cb : nullptr, pfn, pre ? &cbt : nullptr, f.db->get_const_values(), f.dx->get_values(), st.max_iters, st.reduction_factor,
+                                            detail::baseline_code(st.baseline), 8, ws.get_data(), ws.get_num_elems(), f.info.data()));
+        f.report();
     }
-    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
-    {
-        auto dx = matrix::detail_fmt::dense(x);
-        auto x_clone = dx->clone();
-        this->apply_impl(b, x_clone.get());
-        dx->scale(matrix::detail_fmt::dense(beta));
-        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
-    }
-    std::shared_ptr<const LinOp> A_;
-    std::shared_ptr<const LinOp> precond_, precond_t_;
+    std::shared_ptr<const LinOp> precond_t_;
     std::unique_ptr<matrix::Csr<V, int32>> At_;
-    stop::criterion_settings settings_;
-    mutable int64_t last_iters_{-1};
-    mutable bool last_converged_{false};
 };
 
 // Ir (include/ginkgo/core/solver/ir.hpp): x += relaxation_factor * solver(b - A x);
-// without an inner solver it is the Richardson iteration.  with_preconditioner /
-// with_generated_preconditioner of the common factory play with_solver /
-// with_generated_solver.
+// without an inner solver it is the Richardson iteration.  The inner solver sits in the
+// preconditioner slot of the common base and factory: with_solver / with_generated_solver
+// are with_preconditioner / with_generated_preconditioner, get_solver() is get_preconditioner().
 template <typename V = double>
-class Ir : public LinOp {
+class Ir : public detail::iterative_solver<Ir<V>> {
+    using base = detail::iterative_solver<Ir<V>>;
 public:
     class Factory : public detail::factory_base<Ir> {
     public:
@@ -2674,88 +2603,67 @@ public:
         V relaxation_factor_{1.0};
     };
     static Factory build() { return Factory{}; }
-    std::shared_ptr<const LinOp> get_system_matrix() const { return A_; }
-    std::shared_ptr<const LinOp> get_solver() const { return inner_; }
-    int64_t get_last_iteration_count() const noexcept { return last_iters_; }
-    bool has_converged() const noexcept { return last_converged_; }
+    std::shared_ptr<const LinOp> get_solver() const { return this->precond_; }
     // inner iterations of the last apply, summed over its inner solves: known when it ran as the native
     // mixed-precision driver (-1 otherwise)
     int64_t get_last_inner_iteration_count() const noexcept { return last_inner_iters_; }
 protected:
     friend class detail::factory_base<Ir>;
-    Ir(const Factory* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings()), relaxation_factor_(f->relaxation_factor_)
-    {
-        if (size_[0] != size_[1]) throw DimensionMismatch(__FILE__, __LINE__, "Ir needs a square system matrix");
-        inner_ = f->precond_ ? f->precond_ : (f->precond_factory_ ? std::shared_ptr<const LinOp>(f->precond_factory_->generate_impl(A_)) : nullptr);
-    }
+    Ir(const Factory* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A)), relaxation_factor_(f->relaxation_factor_) {}
     // Ir<double> over a generated Cg<float> on a Csr<float, int32> (the float copy of the Csr<double, int32> system),
     // both with Iteration + ResidualNorm, no inner preconditioner, one column: mixed-precision iterative refinement as one
     // native driver (gkomi_ir_mixed_solve_f64_i32).  false: not this configuration, the general path runs.
     bool mixed_as(float, const LinOp*, LinOp*) const { return false; }
     bool mixed_as(double, const LinOp* b, LinOp* x) const
     {
-        auto inner = dynamic_cast<const Cg<float>*>(inner_.get());
-        if (!inner || inner->get_preconditioner() || settings_.implicit || settings_.reduction_factor < 0) return false;
+        const auto& st = this->settings_;
+        auto inner = dynamic_cast<const Cg<float>*>(this->precond_.get());
+        if (!inner || inner->get_preconditioner() || st.implicit || st.reduction_factor < 0) return false;
         const auto& is = inner->get_stop_settings();
         if (is.implicit || is.reduction_factor < 0) return false;
-        auto A = dynamic_cast<const matrix::Csr<double, int32>*>(A_.get());
+        auto A = dynamic_cast<const matrix::Csr<double, int32>*>(this->A_.get());
         auto Af = dynamic_cast<const matrix::Csr<float, int32>*>(inner->get_system_matrix().get());
         auto db = dynamic_cast<const matrix::Dense<double>*>(b);
         auto dx = dynamic_cast<matrix::Dense<double>*>(x);
         if (!A || !Af || !db || !dx || db->get_size()[1] != 1 || db->get_stride() != 1 || dx->get_stride() != 1) return false;
         if (Af->get_size() != A->get_size() || Af->get_num_stored_elements() != A->get_num_stored_elements()) return false;
-        ::gko::detail::require_device(exec_, "ir::apply");
-        const int64_t n = size_[0];
-        array<char> ws(exec_, gkomi_ir_mixed_workspace_bytes(n));
+        ::gko::detail::require_device(this->exec_, "ir::apply");
+        const int64_t n = this->size_[0];
+        array<char> ws(this->exec_, gkomi_ir_mixed_workspace_bytes(n));
         double info[6] = {};
         GKOMI_CALL(gkomi_ir_mixed_solve_f64_i32(nullptr, n, 1, A->get_num_stored_elements(), A->get_const_row_ptrs(), A->get_const_col_idxs(),
                                                 A->get_const_values(), Af->get_const_values(), A->get_strategy()->get_code(), A->get_max_row_nnz(),
-                                                db->get_const_values(), dx->get_values(), settings_.max_iters, settings_.reduction_factor,
-                                                detail::baseline_code(settings_.baseline), is.max_iters, is.reduction_factor,
+                                                db->get_const_values(), dx->get_values(), st.max_iters, st.reduction_factor,
+                                                detail::baseline_code(st.baseline), is.max_iters, is.reduction_factor,
                                                 detail::baseline_code(is.baseline), relaxation_factor_, ws.get_data(), ws.get_num_elems(), info));
-        last_iters_ = static_cast<int64_t>(info[0]);
-        last_converged_ = info[1] != 0.0;
+        this->report(info);
         last_inner_iters_ = static_cast<int64_t>(info[4]);
         return true;
     }
+    using base::apply_impl;
     void apply_impl(const LinOp* b, LinOp* x) const override
     {
         last_inner_iters_ = -1;
         if (mixed_as(V{}, b, x)) return;
-        ::gko::detail::require_device(exec_, "ir::apply");
-        auto csr = as<const matrix::Csr<V, int32>>(A_.get());
-        auto db = matrix::detail_fmt::dense(b); auto dx = matrix::detail_fmt::dense(x);
-        const int64_t n = size_[0], nrhs = db->cols();
-        if (db->get_stride() != static_cast<size_type>(nrhs) || dx->get_stride() != static_cast<size_type>(nrhs)) GKO_NOT_SUPPORTED("solver vectors must be contiguous (stride == #columns)");
-        array<char> ws(exec_, gkomi_krylov_workspace_bytes(n, nrhs));
-        std::vector<double> info(2 + 2 * nrhs, 0.0);
-        ::gko::detail::linop_callback cb{inner_.get(), exec_, static_cast<size_type>(n), static_cast<size_type>(nrhs)};
-        GKOMI_CALL(gkomi_ir_solve_f64_i32(nullptr, n, nrhs, csr->get_num_stored_elements(), csr->get_const_row_ptrs(), csr->get_const_col_idxs(), csr->get_const_values(),
-                                          csr->get_strategy()->get_code(), csr->get_max_row_nnz(), inner_ ? &::gko::detail::linop_callback::call : nullptr, inner_ ? &cb : nullptr,
-                                          relaxation_factor_, db->get_const_values(), dx->get_values(), settings_.max_iters, settings_.reduction_factor,
-                                          detail::baseline_code(settings_.baseline), ws.get_data(), ws.get_num_elems(), info.data()));
-        last_iters_ = static_cast<int64_t>(info[0]);
-        last_converged_ = info[1] != 0.0;
+        const auto& st = this->settings_;
+        const LinOp* inner = this->precond_.get();
+        typename base::operands f(*this, b, x);
+        auto csr = as<const matrix::Csr<V, int32>>(this->A_.get());
+        array<char> ws(this->exec_, gkomi_krylov_workspace_bytes(f.n, f.nrhs));
+        ::gko::detail::linop_callback cb{inner, this->exec_, static_cast<size_type>(f.n), static_cast<size_type>(f.nrhs)};
+        GKOMI_CALL(gkomi_ir_solve_f64_i32(nullptr, f.n, f.nrhs, csr->get_num_stored_elements(), csr->get_const_row_ptrs(), csr->get_const_col_idxs(), csr->get_const_values(),
+                                          csr->get_strategy()->get_code(), csr->get_max_row_nnz(), inner ? &::gko::detail::linop_callback::call : nullptr, inner ? &cb : nullptr,
+                                          relaxation_factor_, f.db->get_const_values(), f.dx->get_values(), st.max_iters, st.reduction_factor,
+                                          detail::baseline_code(st.baseline), ws.get_data(), ws.get_num_elems(), f.info.data()));
+        f.report();
     }
-    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
-    {
-        auto dx = matrix::detail_fmt::dense(x);
-        auto x_clone = dx->clone();
-        this->apply_impl(b, x_clone.get());
-        dx->scale(matrix::detail_fmt::dense(beta));
-        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
-    }
-    std::shared_ptr<const LinOp> A_;
-    std::shared_ptr<const LinOp> inner_;
-    stop::criterion_settings settings_;
     V relaxation_factor_;
-    mutable int64_t last_iters_{-1};
-    mutable bool last_converged_{false};
     mutable int64_t last_inner_iters_{-1};
 };
 
 template <typename V = double>
-class Gmres : public LinOp {
+class Gmres : public detail::iterative_solver<Gmres<V>> {
+    using base = detail::iterative_solver<Gmres<V>>;
 public:
     class Factory : public detail::factory_base<Gmres> {
     public:
@@ -2764,46 +2672,20 @@ public:
     };
     static Factory build() { return Factory{}; }
     size_type get_krylov_dim() const noexcept { return krylov_dim_; }
-    int64_t get_last_iteration_count() const noexcept { return last_iters_; }
-    bool has_converged() const noexcept { return last_converged_; }
 protected:
     friend class detail::factory_base<Gmres>;
-    Gmres(const Factory* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), gko::transpose(A->get_size())), A_(std::move(A)), settings_(f->settings()), krylov_dim_(f->krylov_dim_)
-    {
-        precond_ = f->precond_ ? f->precond_ : (f->precond_factory_ ? std::shared_ptr<const LinOp>(f->precond_factory_->generate_impl(A_)) : nullptr);
-    }
+    Gmres(const Factory* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A)), krylov_dim_(f->krylov_dim_) {}
+    using base::apply_impl;
     void apply_impl(const LinOp* b, LinOp* x) const override
     {
-        ::gko::detail::require_device(exec_, "gmres::apply");
-        auto db = matrix::detail_fmt::dense(b); auto dx = matrix::detail_fmt::dense(x);
-        const int64_t n = size_[0], nrhs = db->cols();
-        if (db->get_stride() != static_cast<size_type>(nrhs) || dx->get_stride() != static_cast<size_type>(nrhs)) GKO_NOT_SUPPORTED("solver vectors must be contiguous (stride == #columns)");
-        array<char> ws(exec_, gkomi_gmres_workspace_bytes(n, nrhs, krylov_dim_));
-        std::vector<double> info(2 + 2 * nrhs, 0.0);
-        ::gko::detail::precond_callback cb(precond_.get(), exec_, static_cast<size_type>(n), static_cast<size_type>(nrhs));
-        auto pfn = cb.fn;
-        void* pctx = cb.ctx;
-        // a Csr system matrix travels as its record (srow, row statistic): detail::system_callback
-        ::gko::detail::system_callback mcb(A_.get(), exec_, static_cast<size_type>(n));
-        GKOMI_CALL(gkomi_gmres_solve_op_f64(nullptr, n, nrhs, mcb.fn, mcb.ctx, pfn, pctx, db->get_const_values(), dx->get_values(), krylov_dim_,
-                                            settings_.max_iters, settings_.reduction_factor, detail::baseline_code(settings_.baseline), ws.get_data(), ws.get_num_elems(), info.data()));
-        last_iters_ = static_cast<int64_t>(info[0]);
-        last_converged_ = info[1] != 0.0;
+        const auto& st = this->settings_;
+        typename base::frame f(*this, b, x);
+        array<char> ws(this->exec_, gkomi_gmres_workspace_bytes(f.n, f.nrhs, krylov_dim_));
+        GKOMI_CALL(gkomi_gmres_solve_op_f64(nullptr, f.n, f.nrhs, f.system.fn, f.system.ctx, f.precond.fn, f.precond.ctx, f.db->get_const_values(), f.dx->get_values(), krylov_dim_,
+                                            st.max_iters, st.reduction_factor, detail::baseline_code(st.baseline), ws.get_data(), ws.get_num_elems(), f.info.data()));
+        f.report();
     }
-    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
-    {
-        auto dx = matrix::detail_fmt::dense(x);
-        auto x_clone = dx->clone();
-        this->apply_impl(b, x_clone.get());
-        dx->scale(matrix::detail_fmt::dense(beta));
-        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
-    }
-    std::shared_ptr<const LinOp> A_;
-    std::shared_ptr<const LinOp> precond_;
-    stop::criterion_settings settings_;
     size_type krylov_dim_;
-    mutable int64_t last_iters_{-1};
-    mutable bool last_converged_{false};
 };
 
 // LowerTrs / UpperTrs (include/ginkgo/core/solver/triangular.hpp)

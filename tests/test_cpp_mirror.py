@@ -132,6 +132,8 @@ def test_hot_path_tour(bins):
     assert int(kv["bicg_ilu_iters"][0]) < int(kv["bicg_jacobi_iters"][0])
     # IR stops at its iteration limit or at the loose goal; either way the residual it reports is the true one
     assert float(kv["ir_jacobi_iters"][4]) < 1.0 and (kv["ir_jacobi_iters"][2] == "1") == (float(kv["ir_jacobi_iters"][4]) < 1e-2)
+    # the one advanced apply of the solvers' base: the same solve and the same two BLAS-1 calls as by hand
+    assert float(kv["cg_advanced_diff"][0]) == 0.0 and float(kv["gmres_advanced_diff"][0]) == 0.0
     # device assembly: duplicates summed, explicit zeros dropped, Csr::read on the device
     assert kv["assembly_nnz"][0] == kv["assembly_nnz"][2] and float(kv["assembly_nnz"][4]) == 0.0
     assert kv["dimension_check"] == ["ok"]
