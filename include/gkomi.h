@@ -1026,6 +1026,53 @@ int gkomi_par_ic_compute_factor_f64_i32(gkomi_stream_t s, int64_t iterations,
                                         const int32_t* l_row_ptrs,
                                         const int32_t* l_col_idxs,
                                         double* l_vals);
+/* ---- exact ILU(0) / IC(0): factorization::Ilu, factorization::Ic ----------
+ * ilu_factorization::compute_lu (core/factorization/ilu_kernels.hpp;
+ * reference/factorization/ilu_kernels.cpp:56-97, called from
+ * core/factorization/ilu.cpp:67-124) and ic_factorization::compute
+ * (core/factorization/ic_kernels.hpp; reference/factorization/ic_kernels.cpp:53-100,
+ * called from core/factorization/ic.cpp:67-120), in place on the values of a
+ * square CSR matrix whose rows are strictly ascending in column and store their
+ * diagonal (what sort_by_column_index + add_diagonal_elements guarantee there).
+ * Both are bit-identical to the reference: per entry the same products are
+ * subtracted / added in ascending k, one rounding each, IEEE quotient and root;
+ * a zero pivot gives the reference's inf / nan.  ic compute changes only the
+ * entries with col <= row.
+ *   analyse   once per sparsity pattern, blocking, for both factorizations: the
+ *             diagonal position and the dependency level of every row (from its
+ *             entries col < row), the rows ordered by level (stable), the first
+ *             position of every level, the launches of the numeric phase.
+ *             GKOMI_EINVAL, with the workspace left invalid, if a row lacks its
+ *             diagonal or is not strictly ascending.  host_out[6] = { nlevels,
+ *             longest row, widest level, launches per numeric call, of those
+ *             single-workgroup runs over narrow levels, nnz }.
+ *   compute   any number of times on one analysed workspace (same pattern, new
+ *             values).  Per wide level one launch per row-length bin it holds
+ *             rows of (group width by row length: 8 lanes, a wave, a
+ *             workgroup), one single-workgroup launch per run of
+ *             consecutive narrow levels; no kernel waits on another workgroup.
+ *             Reads the launch list back from the workspace first (blocking).
+ *             GKOMI_EINVAL, before any launch, on a workspace without a
+ *             successful analysis of an n-row matrix.
+ * gkomi_ilu_tuning: host_out[4] = { longest row a group of 8 lanes takes,
+ * longest row a wave takes, longest row a workgroup keeps in LDS, rows of the
+ * widest level that still counts as narrow } of the library as built (unmeasured
+ * tuning constants; the tests place a case on either side of each).  host_out
+ * NULL: nothing is written. */
+size_t gkomi_ilu_analysis_workspace_bytes(int64_t n);
+void gkomi_ilu_tuning(int64_t* host_out);
+int gkomi_ilu_analyse_i32(gkomi_stream_t s, int64_t n, const int32_t* row_ptrs,
+                          const int32_t* col_idxs, void* workspace,
+                          size_t workspace_bytes, int64_t* host_out);
+int gkomi_ilu_compute_lu_f64_i32(gkomi_stream_t s, int64_t n,
+                                 const int32_t* row_ptrs,
+                                 const int32_t* col_idxs, double* vals,
+                                 const void* analysis_workspace,
+                                 size_t workspace_bytes);
+int gkomi_ic_compute_f64_i32(gkomi_stream_t s, int64_t n,
+                             const int32_t* row_ptrs, const int32_t* col_idxs,
+                             double* vals, const void* analysis_workspace,
+                             size_t workspace_bytes);
 /* ---- matrix assembly: device_matrix_data ---------- */
 /* components::{sort_row_major, sum_duplicates, remove_zeros}
  * (core/base/device_matrix_data_kernels.hpp;

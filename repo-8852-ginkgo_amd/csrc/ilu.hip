@@ -1,0 +1,583 @@
+// Exact ILU(0) and IC(0): factorization::Ilu / factorization::Ic
+// (core/factorization/ilu.cpp:67-124 -> reference/factorization/ilu_kernels.cpp:56-97 compute_lu;
+//  core/factorization/ic.cpp:67-120 -> reference/factorization/ic_kernels.cpp:53-100 compute).
+// The reference's HIP backend hands both to the vendor library (csrilu0 / csric0); this library links none.
+//
+// Dependencies: row i needs the FINISHED rows k < i for which a_ik is stored -- for ILU their U part and
+// pivot, for IC their whole lower part.  That is the lower-triangular level structure trs_levels.hip
+// analyses, run on the pattern of the whole of A.  Rows of one level are independent.
+//
+// Bits.  compute_lu forms entry (i, j) as a_ij minus l_ik u_kj over the stored k < min(i, j) of row i in
+// ascending k, one product and one difference each, then divides by u_jj below the diagonal.  The row-wise
+// IKJ form used here walks the lower entries k of row i in the same ascending order and, per k, subtracts
+// l_ik u_kj from every stored j > k of row i for which row k stores j: every entry sees the same terms in
+// the same order.  Different j of one k step are different entries (the lanes of a group take them), and the
+// group meets between two k steps.  ic compute is a chain inside the row (entry (i, j) needs every earlier
+// l_ik), so only the products of one dot are formed in parallel; the sum starts at +0.0 and the products are
+// added one after the other in ascending k.  A column of row j that row i does not store contributes +0.0:
+// a sum that starts at +0.0 is never -0.0 (x + y is -0.0 only for x = y = -0.0), so adding +0.0 leaves every
+// bit alone.  Quotient and root are the IEEE ones; the library is built with -ffp-contract=off.
+//
+// The working row lives in LDS (an "image" per group); finished rows are read from memory.
+//
+// Scheduling.  No kernel here waits on another workgroup: no flags, no spins, no device-wide meetings.
+//   (a) a level of more than `narrow_level_rows` rows is one launch per row-length bin it holds rows of (the
+//       bins below: the group width follows the row), each a capped grid that strides over the level's list
+//       of rows and takes the rows of its bin;
+//   (b) a run of consecutive levels of at most `narrow_level_rows` rows each is ONE launch of ONE
+//       workgroup that walks the levels with __syncthreads in between (a chain or thin band would
+//       otherwise cost a launch per row).
+// All boundaries are tuning constants; none has been measured.
+#include "common.hpp"
+
+#include <vector>
+
+#include "internal.hpp"
+#include "sort_scan.hpp"
+
+namespace gkomi {
+namespace {
+
+constexpr int fact_block = 256;
+// row-length bins: a row of at most bin_short entries is factorized by 8 lanes, one of at most bin_wave
+// by a wave (both with an LDS image per group), one of at most bin_lds by a workgroup with the row in
+// LDS, anything longer by a workgroup on the row in memory
+constexpr int bin_short = 32;
+constexpr int short_width = 8;
+constexpr int bin_wave = 512;
+constexpr int bin_lds = 1024;
+// the boundary between (a) and (b): a level of at most this many rows is narrow (4 rows per wave of the
+// one workgroup that walks it)
+constexpr int narrow_level_rows = 16;
+constexpr int max_level_grid = 4096;
+
+constexpr int64_t ws_magic = 0x696c7530676b6f6dll;
+
+struct analysis_header {
+    int64_t magic;  // ws_magic once the analysis has succeeded
+    int64_t n, nnz, nlevels, nsegments, longest_row, widest_level, narrow_runs, launches;
+};
+static_assert(sizeof(analysis_header) <= 256, "the header has 256 bytes");
+
+// one launch of the numeric phase
+struct segment {
+    int32_t kind;      // 0: one wide level, 1: a run of narrow levels
+    int32_t first;     // wide: first position of the level; run: first level
+    int32_t last;      // wide: one past its last position;   run: one past the last level
+    int32_t longest;   // longest row inside
+    int32_t bins;      // wide: bit b set = the level holds a row of bin b (0 short, 1 wave, 2 workgroup)
+    int32_t pad_;
+};
+
+struct analysis_layout {
+    size_t diag, level, level_sorted, rows, perm, cnt, level_start, level_longest, level_bins, segments, flags, tmp, tmp_bytes, total;
+};
+
+analysis_layout make_layout(int64_t n)
+{
+    analysis_layout l{};
+    const size_t m = static_cast<size_t>(n > 0 ? n : 1);
+    const size_t vec = align256(sizeof(int32_t) * (m + 1));
+    size_t off = 256;
+    l.diag = off; off += vec;
+    l.level = off; off += vec;
+    l.level_sorted = off; off += vec;
+    l.rows = off; off += vec;
+    l.perm = off; off += vec;
+    l.cnt = off; off += vec;
+    l.level_start = off; off += vec;
+    l.level_longest = off; off += vec;
+    l.level_bins = off; off += align256(sizeof(int32_t) * 3 * (m + 1));
+    l.segments = off; off += align256(sizeof(segment) * (m + 1));
+    l.flags = off; off += 256;
+    l.tmp_bytes = align256(radix_sort_workspace_bytes(static_cast<int64_t>(m), sizeof(uint32_t), true)) + 256;
+    l.tmp = off; off += l.tmp_bytes;
+    l.total = off;
+    return l;
+}
+
+// diag[row] = position of the diagonal; flags[0] |= 1: a row without diagonal, |= 2: a row that is not
+// strictly ascending or leaves [0, n); flags[1] = longest row
+__global__ __launch_bounds__(256) void fact_check_rows_kernel(int32_t n, const int32_t* __restrict__ row_ptrs,
+                                                             const int32_t* __restrict__ col_idxs,
+                                                             int32_t* __restrict__ diag, int32_t* __restrict__ flags)
+{
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    const int begin = row_ptrs[row], end = row_ptrs[row + 1];
+    int d = -1, bad = 0, prev = -1;
+    for (int k = begin; k < end; ++k) {
+        const int col = col_idxs[k];
+        if (col <= prev || col >= n) bad = 2;
+        if (col == row) d = k;
+        prev = col;
+    }
+    if (end < begin) bad = 2;
+    diag[row] = d;
+    if (d < 0) bad |= 1;
+    if (bad) atomicOr(flags, bad);
+    atomicMax(flags + 1, end - begin);
+}
+
+__host__ __device__ __forceinline__ int bin_of(int len) { return len <= bin_short ? 0 : (len <= bin_wave ? 1 : 2); }
+
+// level_longest[l] = longest row of level l, level_bins[3 l + b] = its rows of bin b (both zeroed by the caller)
+__global__ __launch_bounds__(256) void fact_level_longest_kernel(int32_t n, const int32_t* __restrict__ row_ptrs,
+                                                                const int32_t* __restrict__ perm,
+                                                                const int32_t* __restrict__ level_sorted,
+                                                                int32_t* __restrict__ level_longest,
+                                                                int32_t* __restrict__ level_bins)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int row = perm[p];
+    const int len = row_ptrs[row + 1] - row_ptrs[row];
+    atomicMax(level_longest + level_sorted[p], len);
+    atomicAdd(level_bins + 3 * level_sorted[p] + bin_of(len), 1);
+}
+
+// ---- how a group meets ------------------------------------------------------------------------------
+// lanes of one wave: LDS operations of a wave complete in program order; the fences keep the compiler from
+// moving an LDS access across the meeting point
+struct wave_meet {
+    __device__ __forceinline__ void operator()() const
+    {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+};
+struct block_meet {
+    __device__ __forceinline__ void operator()() const { __syncthreads(); }
+};
+
+// a value of a finished row.  Coherent (the narrow-level workgroup: the row was finished by another wave of
+// this launch): past the compute unit's vector cache, which may still hold the line from before.
+template <bool Coherent>
+__device__ __forceinline__ double finished(const double* p)
+{
+    if (Coherent) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return *p;
+}
+// the working row: an LDS image, or (InMemory) the row itself, shared by the waves of one workgroup
+template <bool InMemory>
+__device__ __forceinline__ double wld(const double* p)
+{
+    if (InMemory) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return *p;
+}
+template <bool InMemory>
+__device__ __forceinline__ void wst(double* p, double v)
+{
+    if (InMemory) {
+        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        *p = v;
+    }
+}
+
+// position of `col` among cols[lo, hi) (strictly ascending), -1 if it is not stored
+__device__ __forceinline__ int find_col(const int32_t* __restrict__ cols, int lo, int hi, int col)
+{
+    const int end = hi;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (cols[mid] < col) {
+            lo = mid + 1;
+        } else {
+            hi = mid;
+        }
+    }
+    return lo < end && cols[lo] == col ? lo : -1;
+}
+
+// compute_lu of one row by a group of W lanes (t = my lane in the group).  w: the working row (len entries).
+template <int W, bool InMemory, bool Coherent, class Meet>
+__device__ __forceinline__ void ilu_row(int t, int row, const int32_t* __restrict__ row_ptrs,
+                                        const int32_t* __restrict__ col_idxs, const int32_t* __restrict__ diag,
+                                        double* vals, double* w, Meet meet)
+{
+    const int begin = row_ptrs[row];
+    const int len = row_ptrs[row + 1] - begin;
+    const int dpos = diag[row] - begin;
+    const int32_t* cols = col_idxs + begin;
+    if (!InMemory) {
+        for (int q = t; q < len; q += W) w[q] = vals[begin + q];
+        meet();
+    }
+    for (int p = 0; p < dpos; ++p) {
+        const int k = cols[p];
+        const int dk = diag[k];
+        const double l = wld<InMemory>(w + p) / finished<Coherent>(vals + dk);
+        const int kend = row_ptrs[k + 1];
+        for (int q = dk + 1 + t; q < kend; q += W) {
+            const int r = find_col(cols, p + 1, len, col_idxs[q]);
+            if (r >= 0) {
+                const double prod = l * finished<Coherent>(vals + q);
+                wst<InMemory>(w + r, wld<InMemory>(w + r) - prod);
+            }
+        }
+        meet();
+        // nobody reads entry p of the working row any more
+        if (t == 0) vals[begin + p] = l;
+    }
+    if (!InMemory) {
+        for (int q = dpos + t; q < len; q += W) vals[begin + q] = w[q];
+    }
+}
+
+// ic compute of one row.  w: the lower part of the working row with its diagonal; products: W doubles of the group.
+template <int W, bool InMemory, bool Coherent, class Meet>
+__device__ __forceinline__ void ic_row(int t, int row, const int32_t* __restrict__ row_ptrs,
+                                       const int32_t* __restrict__ col_idxs, const int32_t* __restrict__ diag,
+                                       double* vals, double* w, double* products, Meet meet)
+{
+    const int begin = row_ptrs[row];
+    const int dpos = diag[row] - begin;
+    const int32_t* cols = col_idxs + begin;
+    if (!InMemory) {
+        for (int q = t; q <= dpos; q += W) w[q] = vals[begin + q];
+        meet();
+    }
+    for (int p = 0; p <= dpos; ++p) {
+        const int j = cols[p];
+        const bool is_diag = p == dpos;
+        const double a = wld<InMemory>(w + p);
+        // the lower entries of row j; for the diagonal they are this row's own, in the working row
+        const int jb = row_ptrs[j];
+        const int jd = is_diag ? begin + dpos : diag[j];
+        double sum = 0.0;
+        for (int base = jb; base < jd; base += W) {
+            const int q = base + t;
+            double prod = 0.0;
+            if (q < jd) {
+                if (is_diag) {
+                    const double v = wld<InMemory>(w + (q - begin));
+                    prod = v * v;
+                } else {
+                    const int r = find_col(cols, 0, p, col_idxs[q]);
+                    if (r >= 0) prod = wld<InMemory>(w + r) * finished<Coherent>(vals + q);
+                }
+            }
+            products[t] = prod;
+            meet();
+            const int m = jd - base < W ? jd - base : W;
+            for (int s = 0; s < m; ++s) sum += products[s];
+            meet();
+        }
+        const double diff = a - sum;
+        const double l = is_diag ? sqrt(diff) : diff / finished<Coherent>(vals + jd);
+        meet();
+        if (t == 0) wst<InMemory>(w + p, l);
+        meet();
+    }
+    if (!InMemory) {
+        for (int q = t; q <= dpos; q += W) vals[begin + q] = w[q];
+    }
+}
+
+// one row by a whole workgroup: in LDS when it fits, in memory otherwise.  image: bin_lds doubles.
+template <bool Ic, bool Coherent>
+__device__ __forceinline__ void block_row(int row, const int32_t* __restrict__ row_ptrs,
+                                          const int32_t* __restrict__ col_idxs, const int32_t* __restrict__ diag,
+                                          double* vals, double* image, double* products)
+{
+    const int t = threadIdx.x;
+    const int begin = row_ptrs[row];
+    const int len = row_ptrs[row + 1] - begin;
+    if (len <= bin_lds) {
+        if (Ic) {
+            ic_row<fact_block, false, Coherent>(t, row, row_ptrs, col_idxs, diag, vals, image, products, block_meet{});
+        } else {
+            ilu_row<fact_block, false, Coherent>(t, row, row_ptrs, col_idxs, diag, vals, image, block_meet{});
+        }
+    } else {
+        if (Ic) {
+            ic_row<fact_block, true, Coherent>(t, row, row_ptrs, col_idxs, diag, vals, vals + begin, products, block_meet{});
+        } else {
+            ilu_row<fact_block, true, Coherent>(t, row, row_ptrs, col_idxs, diag, vals, vals + begin, block_meet{});
+        }
+    }
+}
+
+// (a) one wide level, its rows of bin Bin (at most Cap entries): a group of W lanes per row, grid-stride over
+// perm[first, last); rows of the other bins are left to their own launch (rows of a level are independent)
+template <bool Ic, int W, int Cap, int Bin>
+__global__ __launch_bounds__(fact_block) void fact_level_kernel(const int32_t* __restrict__ row_ptrs,
+                                                               const int32_t* __restrict__ col_idxs,
+                                                               const int32_t* __restrict__ diag,
+                                                               const int32_t* __restrict__ perm, int first, int last,
+                                                               double* vals)
+{
+    constexpr int groups = fact_block / W;
+    __shared__ double image[groups * Cap];
+    __shared__ double products[fact_block];
+    const int g = threadIdx.x / W, t = threadIdx.x % W;
+    for (int pos = first + blockIdx.x * groups + g; pos < last; pos += gridDim.x * groups) {
+        const int row = perm[pos];
+        if (bin_of(row_ptrs[row + 1] - row_ptrs[row]) != Bin) continue;  // the same answer in every lane of the group
+        if (Ic) {
+            ic_row<W, false, false>(t, row, row_ptrs, col_idxs, diag, vals, image + g * Cap, products + g * W, wave_meet{});
+        } else {
+            ilu_row<W, false, false>(t, row, row_ptrs, col_idxs, diag, vals, image + g * Cap, wave_meet{});
+        }
+        wave_meet{}();  // the image is loaded again
+    }
+}
+
+// (a) the rows longer than bin_wave of one wide level: a workgroup per row
+template <bool Ic>
+__global__ __launch_bounds__(fact_block) void fact_level_block_kernel(const int32_t* __restrict__ row_ptrs,
+                                                                     const int32_t* __restrict__ col_idxs,
+                                                                     const int32_t* __restrict__ diag,
+                                                                     const int32_t* __restrict__ perm, int first,
+                                                                     int last, double* vals)
+{
+    __shared__ double image[bin_lds];
+    __shared__ double products[fact_block];
+    for (int pos = first + blockIdx.x; pos < last; pos += gridDim.x) {
+        const int row = perm[pos];
+        if (bin_of(row_ptrs[row + 1] - row_ptrs[row]) != 2) continue;  // the same answer in the whole workgroup
+        block_row<Ic, false>(row, row_ptrs, col_idxs, diag, vals, image, products);
+        __syncthreads();
+    }
+}
+
+// (b) ONE workgroup walks the narrow levels [first_level, last_level): a wave per row of at most bin_wave entries,
+// then the workgroup per longer row, __syncthreads between levels.  What a level wrote is read by the
+// next through agent-scope loads after a release fence.
+template <bool Ic>
+__global__ __launch_bounds__(fact_block) void fact_run_kernel(const int32_t* __restrict__ row_ptrs,
+                                                             const int32_t* __restrict__ col_idxs,
+                                                             const int32_t* __restrict__ diag,
+                                                             const int32_t* __restrict__ perm,
+                                                             const int32_t* __restrict__ level_start,
+                                                             const int32_t* __restrict__ level_longest,
+                                                             int first_level, int last_level, double* vals)
+{
+    constexpr int waves = fact_block / wave_size;
+    static_assert(waves * bin_wave >= bin_lds, "the images of the waves hold the image of the workgroup");
+    __shared__ double image[waves * bin_wave];
+    __shared__ double products[fact_block];
+    const int wave = threadIdx.x / wave_size, lane = threadIdx.x % wave_size;
+    for (int lvl = first_level; lvl < last_level; ++lvl) {
+        const int first = level_start[lvl], last = level_start[lvl + 1];
+        // the rows of at most bin_wave entries: a wave each
+        for (int pos = first + wave; pos < last; pos += waves) {
+            const int row = perm[pos];
+            if (bin_of(row_ptrs[row + 1] - row_ptrs[row]) == 2) continue;
+            if (Ic) {
+                ic_row<wave_size, false, true>(lane, row, row_ptrs, col_idxs, diag, vals, image + wave * bin_wave,
+                                               products + wave * wave_size, wave_meet{});
+            } else {
+                ilu_row<wave_size, false, true>(lane, row, row_ptrs, col_idxs, diag, vals, image + wave * bin_wave,
+                                                wave_meet{});
+            }
+            wave_meet{}();
+        }
+        // the longer ones, if the level has any: the workgroup, one after the other (the images are shared)
+        if (level_longest[lvl] > bin_wave) {
+            __syncthreads();
+            for (int pos = first; pos < last; ++pos) {
+                const int row = perm[pos];
+                if (bin_of(row_ptrs[row + 1] - row_ptrs[row]) != 2) continue;
+                block_row<Ic, true>(row, row_ptrs, col_idxs, diag, vals, image, products);
+                __syncthreads();
+            }
+        }
+        __threadfence();
+        __syncthreads();
+    }
+}
+
+template <bool Ic>
+int compute(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs, double* vals,
+            const void* workspace, size_t workspace_bytes)
+{
+    if (n < 0) return GKOMI_EINVAL;
+    if (n > INT32_MAX - 1024) return GKOMI_ENOTSUPPORTED;
+    const analysis_layout l = make_layout(n);
+    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
+    const char* ws = static_cast<const char*>(workspace);
+    analysis_header h{};
+    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost, stream)));
+    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+    // no analysis, a failed one (missing diagonal, unsorted row), or one of another matrix
+    if (h.magic != ws_magic || h.n != n || h.nsegments < 0 || h.nsegments > n) return GKOMI_EINVAL;
+    if (n == 0) return GKOMI_SUCCESS;
+    std::vector<segment> segs(static_cast<size_t>(h.nsegments));
+    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(segs.data(), ws + l.segments, sizeof(segment) * segs.size(),
+                                              hipMemcpyDeviceToHost, stream)));
+    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+    const int32_t* diag = reinterpret_cast<const int32_t*>(ws + l.diag);
+    const int32_t* perm = reinterpret_cast<const int32_t*>(ws + l.perm);
+    const int32_t* level_start = reinterpret_cast<const int32_t*>(ws + l.level_start);
+    const int32_t* level_longest = reinterpret_cast<const int32_t*>(ws + l.level_longest);
+    for (const segment& sg : segs) {
+        if (sg.kind == 1) {
+            hipLaunchKernelGGL(fact_run_kernel<Ic>, dim3(1), dim3(fact_block), 0, stream, row_ptrs, col_idxs, diag, perm,
+                               level_start, level_longest, sg.first, sg.last, vals);
+            continue;
+        }
+        const int64_t rows = sg.last - sg.first;
+        // one launch per bin the level holds rows of
+        if (sg.bins & 1) {
+            hipLaunchKernelGGL((fact_level_kernel<Ic, short_width, bin_short, 0>),
+                               dim3(grid_for(rows, fact_block / short_width, max_level_grid)), dim3(fact_block), 0, stream,
+                               row_ptrs, col_idxs, diag, perm, sg.first, sg.last, vals);
+        }
+        if (sg.bins & 2) {
+            hipLaunchKernelGGL((fact_level_kernel<Ic, wave_size, bin_wave, 1>),
+                               dim3(grid_for(rows, fact_block / wave_size, max_level_grid)), dim3(fact_block), 0, stream,
+                               row_ptrs, col_idxs, diag, perm, sg.first, sg.last, vals);
+        }
+        if (sg.bins & 4) {
+            hipLaunchKernelGGL(fact_level_block_kernel<Ic>, dim3(grid_for(rows, 1, max_level_grid)), dim3(fact_block), 0,
+                               stream, row_ptrs, col_idxs, diag, perm, sg.first, sg.last, vals);
+        }
+    }
+    return check_launch();
+}
+
+}  // namespace
+}  // namespace gkomi
+
+using namespace gkomi;
+
+extern "C" size_t gkomi_ilu_analysis_workspace_bytes(int64_t n)
+{
+    if (n < 0 || n > INT32_MAX - 1024) return 0;
+    return make_layout(n).total;
+}
+
+extern "C" int gkomi_ilu_analyse_i32(gkomi_stream_t s, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs,
+                                     void* workspace, size_t workspace_bytes, int64_t* host_out)
+{
+    if (n < 0 || host_out == nullptr) return GKOMI_EINVAL;
+    if (n > INT32_MAX - 1024) return GKOMI_ENOTSUPPORTED;
+    const analysis_layout l = make_layout(n);
+    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
+    hipStream_t stream = to_stream(s);
+    char* ws = static_cast<char*>(workspace);
+    for (int i = 0; i < 6; ++i) host_out[i] = 0;
+    // the workspace is not valid until the end of a successful analysis
+    GKOMI_TRY(static_cast<int>(hipMemsetAsync(ws, 0, 256, stream)));
+    analysis_header h{};
+    h.magic = ws_magic;
+    h.n = n;
+    if (n > 0) {
+        int32_t* diag = reinterpret_cast<int32_t*>(ws + l.diag);
+        int32_t* level = reinterpret_cast<int32_t*>(ws + l.level);
+        int32_t* level_sorted = reinterpret_cast<int32_t*>(ws + l.level_sorted);
+        int32_t* rows = reinterpret_cast<int32_t*>(ws + l.rows);
+        int32_t* perm = reinterpret_cast<int32_t*>(ws + l.perm);
+        int32_t* cnt = reinterpret_cast<int32_t*>(ws + l.cnt);
+        int32_t* level_start = reinterpret_cast<int32_t*>(ws + l.level_start);
+        int32_t* level_longest = reinterpret_cast<int32_t*>(ws + l.level_longest);
+        int32_t* level_bins = reinterpret_cast<int32_t*>(ws + l.level_bins);
+        int32_t* flags = reinterpret_cast<int32_t*>(ws + l.flags);
+        const int32_t n32 = static_cast<int32_t>(n);
+        const dim3 grid(static_cast<unsigned>(ceildiv(n, 256)));
+        GKOMI_TRY(static_cast<int>(hipMemsetAsync(flags, 0, 256, stream)));
+        hipLaunchKernelGGL(fact_check_rows_kernel, grid, dim3(256), 0, stream, n32, row_ptrs, col_idxs, diag, flags);
+        int32_t hf[2] = {0, 0};
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, stream)));
+        int32_t nnz = 0;
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&nnz, row_ptrs + n, sizeof(nnz), hipMemcpyDeviceToHost, stream)));
+        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+        if (hf[0] != 0) return GKOMI_EINVAL;  // a row without its diagonal, or not strictly ascending
+        h.nnz = nnz;
+        h.longest_row = hf[1];
+        GKOMI_TRY(trs_relax_lower_levels(stream, n, row_ptrs, col_idxs, level, cnt, flags));
+        GKOMI_TRY(trs_iota(stream, n, rows));
+        // stable: the rows of a level keep their order
+        GKOMI_TRY(radix_sort_u32(stream, n, reinterpret_cast<const uint32_t*>(level),
+                                 reinterpret_cast<uint32_t*>(level_sorted), reinterpret_cast<const uint32_t*>(rows),
+                                 reinterpret_cast<uint32_t*>(perm), 32, ws + l.tmp, l.tmp_bytes));
+        int32_t top = 0;
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&top, level_sorted + (n - 1), sizeof(top), hipMemcpyDeviceToHost, stream)));
+        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+        const int64_t nlevels = static_cast<int64_t>(top) + 1;
+        if (nlevels < 1 || nlevels > n) return GKOMI_EINVAL;
+        h.nlevels = nlevels;
+        GKOMI_TRY(trs_level_starts(stream, n, nlevels, level_sorted, level_start));
+        GKOMI_TRY(static_cast<int>(hipMemsetAsync(level_longest, 0, sizeof(int32_t) * nlevels, stream)));
+        GKOMI_TRY(static_cast<int>(hipMemsetAsync(level_bins, 0, sizeof(int32_t) * 3 * nlevels, stream)));
+        hipLaunchKernelGGL(fact_level_longest_kernel, grid, dim3(256), 0, stream, n32, row_ptrs, perm, level_sorted,
+                           level_longest, level_bins);
+        std::vector<int32_t> start(static_cast<size_t>(nlevels) + 1), longest(static_cast<size_t>(nlevels)),
+            bins(3 * static_cast<size_t>(nlevels));
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(bins.data(), level_bins, sizeof(int32_t) * bins.size(),
+                                                  hipMemcpyDeviceToHost, stream)));
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(start.data(), level_start, sizeof(int32_t) * start.size(),
+                                                  hipMemcpyDeviceToHost, stream)));
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(longest.data(), level_longest, sizeof(int32_t) * longest.size(),
+                                                  hipMemcpyDeviceToHost, stream)));
+        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+        // the launches of the numeric phase
+        for (int64_t lvl = 0; lvl < nlevels; ++lvl) {
+            if (start[lvl + 1] - start[lvl] > h.widest_level) h.widest_level = start[lvl + 1] - start[lvl];
+        }
+        std::vector<segment> segs;
+        for (int64_t lvl = 0; lvl < nlevels;) {
+            const int32_t width = start[lvl + 1] - start[lvl];
+            if (width > narrow_level_rows) {
+                int32_t mask = 0;
+                for (int b = 0; b < 3; ++b) {
+                    if (bins[3 * lvl + b] > 0) {
+                        mask |= 1 << b;
+                        ++h.launches;
+                    }
+                }
+                segs.push_back({0, start[lvl], start[lvl + 1], longest[lvl], mask, 0});
+                ++lvl;
+                continue;
+            }
+            int64_t end = lvl;
+            int32_t run_longest = 0;
+            for (; end < nlevels && start[end + 1] - start[end] <= narrow_level_rows; ++end) {
+                if (longest[end] > run_longest) run_longest = longest[end];
+            }
+            segs.push_back({1, static_cast<int32_t>(lvl), static_cast<int32_t>(end), run_longest, 0, 0});
+            ++h.narrow_runs;
+            ++h.launches;
+            lvl = end;
+        }
+        h.nsegments = static_cast<int64_t>(segs.size());
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(ws + l.segments, segs.data(), sizeof(segment) * segs.size(),
+                                                  hipMemcpyHostToDevice, stream)));
+        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));  // segs leaves scope
+        GKOMI_TRY(check_launch());
+    }
+    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(ws, &h, sizeof(h), hipMemcpyHostToDevice, stream)));
+    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+    host_out[0] = h.nlevels;
+    host_out[1] = h.longest_row;
+    host_out[2] = h.widest_level;
+    host_out[3] = h.launches;
+    host_out[4] = h.narrow_runs;
+    host_out[5] = h.nnz;
+    return GKOMI_SUCCESS;
+}
+
+extern "C" void gkomi_ilu_tuning(int64_t* host_out)
+{
+    if (host_out == nullptr) return;
+    host_out[0] = bin_short;
+    host_out[1] = bin_wave;
+    host_out[2] = bin_lds;
+    host_out[3] = narrow_level_rows;
+}
+
+extern "C" int gkomi_ilu_compute_lu_f64_i32(gkomi_stream_t s, int64_t n, const int32_t* row_ptrs,
+                                            const int32_t* col_idxs, double* vals, const void* analysis_workspace,
+                                            size_t workspace_bytes)
+{
+    return compute<false>(to_stream(s), n, row_ptrs, col_idxs, vals, analysis_workspace, workspace_bytes);
+}
+
+extern "C" int gkomi_ic_compute_f64_i32(gkomi_stream_t s, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs,
+                                        double* vals, const void* analysis_workspace, size_t workspace_bytes)
+{
+    return compute<true>(to_stream(s), n, row_ptrs, col_idxs, vals, analysis_workspace, workspace_bytes);
+}

@@ -331,4 +331,14 @@ struct spmv_dot_plan {
     }
 };
 
+// ---- level analysis of trs_levels.hip, shared with the exact factorizations (ilu.hip) ----------------
+// level[row] = 1 + max level of the rows col < row it stores (0 without any), cnt[row] = their number:
+// trs_relax_levels_kernel<true> to its fixed point.  Blocking; flags = 4 ints of device scratch.
+int trs_relax_lower_levels(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs,
+                           int32_t* level, int32_t* cnt, int32_t* flags);
+// rows[i] = i
+int trs_iota(hipStream_t stream, int64_t n, int32_t* rows);
+// level_start[l] = first position of level l in level order, level_start[nlevels] = n
+int trs_level_starts(hipStream_t stream, int64_t n, int64_t nlevels, const int32_t* level_sorted, int32_t* level_start);
+
 }  // namespace gkomi

@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "internal.hpp"
 #include "sort_scan.hpp"
 
 namespace gkomi {
@@ -543,25 +544,12 @@ void launch_small(hipStream_t stream, int64_t max_deps, const plan_header* hdr, 
 #undef GKOMI_SMALL
 }
 
+// the relaxation to its fixed point (blocking): level (zeroed here) and cnt of n rows, flags = 4 ints of scratch
 template <bool Lower>
-int analyse_symbolic(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs,
-                     void* workspace, size_t workspace_bytes, int64_t* host_out)
+int relax_levels(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs, int32_t* level,
+                 int32_t* cnt, int32_t* flags)
 {
-    const symbolic_layout l = make_symbolic_layout(n);
-    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
-    char* ws = static_cast<char*>(workspace);
-    int32_t* level = reinterpret_cast<int32_t*>(ws + l.level);
-    int32_t* level_sorted = reinterpret_cast<int32_t*>(ws + l.level_sorted);
-    int32_t* rows = reinterpret_cast<int32_t*>(ws + l.rows);
-    int32_t* perm = reinterpret_cast<int32_t*>(ws + l.perm);
-    int32_t* cnt = reinterpret_cast<int32_t*>(ws + l.cnt);
-    int32_t* slice_len = reinterpret_cast<int32_t*>(ws + l.slice_len);
-    int32_t* slice_off = reinterpret_cast<int32_t*>(ws + l.slice_off);
-    int32_t* flags = reinterpret_cast<int32_t*>(ws + l.flags);  // [0] changed, [1] nlevels
     const int32_t n32 = static_cast<int32_t>(n);
-    const int32_t nslices = static_cast<int32_t>(ceildiv(n, slice));
-    host_out[0] = host_out[1] = host_out[2] = host_out[3] = 0;
-    if (n == 0) return GKOMI_SUCCESS;
     int err = static_cast<int>(hipMemsetAsync(level, 0, sizeof(int32_t) * n, stream));
     if (err) return err;
     const dim3 grid(static_cast<unsigned>(ceildiv(n, 256)));
@@ -582,6 +570,31 @@ int analyse_symbolic(hipStream_t stream, int64_t n, const int32_t* row_ptrs, con
         if (err) return err;
         if (!changed) break;
     }
+    return GKOMI_SUCCESS;
+}
+
+template <bool Lower>
+int analyse_symbolic(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs,
+                     void* workspace, size_t workspace_bytes, int64_t* host_out)
+{
+    const symbolic_layout l = make_symbolic_layout(n);
+    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
+    char* ws = static_cast<char*>(workspace);
+    int32_t* level = reinterpret_cast<int32_t*>(ws + l.level);
+    int32_t* level_sorted = reinterpret_cast<int32_t*>(ws + l.level_sorted);
+    int32_t* rows = reinterpret_cast<int32_t*>(ws + l.rows);
+    int32_t* perm = reinterpret_cast<int32_t*>(ws + l.perm);
+    int32_t* cnt = reinterpret_cast<int32_t*>(ws + l.cnt);
+    int32_t* slice_len = reinterpret_cast<int32_t*>(ws + l.slice_len);
+    int32_t* slice_off = reinterpret_cast<int32_t*>(ws + l.slice_off);
+    int32_t* flags = reinterpret_cast<int32_t*>(ws + l.flags);  // [0] changed, [1] nlevels
+    const int32_t n32 = static_cast<int32_t>(n);
+    const int32_t nslices = static_cast<int32_t>(ceildiv(n, slice));
+    host_out[0] = host_out[1] = host_out[2] = host_out[3] = 0;
+    if (n == 0) return GKOMI_SUCCESS;
+    int err = relax_levels<Lower>(stream, n, row_ptrs, col_idxs, level, cnt, flags);
+    if (err) return err;
+    const dim3 grid(static_cast<unsigned>(ceildiv(n, 256)));
     hipLaunchKernelGGL(trs_iota_kernel, grid, dim3(256), 0, stream, n32, rows);
     size_t tmp_bytes = l.tmp_bytes;
     // stable: rows of one level keep their storage order (deterministic layout)
@@ -613,6 +626,28 @@ int analyse_symbolic(hipStream_t stream, int64_t n, const int32_t* row_ptrs, con
 }
 
 }  // namespace
+
+// the same helpers for the exact factorizations (ilu.hip; declared in internal.hpp)
+int trs_relax_lower_levels(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs,
+                           int32_t* level, int32_t* cnt, int32_t* flags)
+{
+    return relax_levels<true>(stream, n, row_ptrs, col_idxs, level, cnt, flags);
+}
+
+int trs_iota(hipStream_t stream, int64_t n, int32_t* rows)
+{
+    hipLaunchKernelGGL(trs_iota_kernel, dim3(static_cast<unsigned>(ceildiv(n, 256))), dim3(256), 0, stream,
+                       static_cast<int32_t>(n), rows);
+    return check_launch();
+}
+
+int trs_level_starts(hipStream_t stream, int64_t n, int64_t nlevels, const int32_t* level_sorted, int32_t* level_start)
+{
+    hipLaunchKernelGGL(trs_level_start_kernel, dim3(static_cast<unsigned>(ceildiv(n, 256))), dim3(256), 0, stream,
+                       static_cast<int32_t>(n), static_cast<int32_t>(nlevels), level_sorted, level_start);
+    return check_launch();
+}
+
 }  // namespace gkomi
 
 using namespace gkomi;

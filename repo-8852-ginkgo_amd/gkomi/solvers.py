@@ -561,3 +561,83 @@ def par_ic_generate(gk, n, row_ptrs, col_idxs, vals, iterations=0, nrhs=1):
     p = ilu_from_factors(gk, n, (lrp, lc, lv), Lt, nrhs=nrhs)
     p.L, p.Lt = (lrp, lc, lv), Lt
     return p
+
+
+class FactorizationAnalysis:
+    """gkomi_ilu_analyse_i32: diagonal positions, dependency levels and the launch list of the exact ILU(0) / IC(0)
+    of one sparsity pattern (sorted rows, diagonal stored); reusable for any number of numeric calls."""
+
+    def __init__(self, gk, n, row_ptrs, col_idxs):
+        self.gk, self.n = gk, n
+        self.nbytes = gk.ilu_analysis_workspace_bytes(n)
+        self.ws = torch.zeros(max(self.nbytes, 8), dtype=torch.uint8, device=row_ptrs.device)
+        out = (ctypes.c_int64 * 6)()
+        gk.ilu_analyse_i32(torch.cuda.current_stream().cuda_stream, n, row_ptrs, col_idxs, self.ws, self.nbytes,
+                           ctypes.addressof(out))
+        self.nlevels, self.longest_row, self.widest_level, self.launches, self.narrow_runs, self.nnz = (int(x) for x in out)
+
+    def compute_lu(self, row_ptrs, col_idxs, vals):
+        self.gk.ilu_compute_lu_f64_i32(torch.cuda.current_stream().cuda_stream, self.n, row_ptrs, col_idxs, vals,
+                                       self.ws, self.nbytes)
+
+    def ic_compute(self, row_ptrs, col_idxs, vals):
+        self.gk.ic_compute_f64_i32(torch.cuda.current_stream().cuda_stream, self.n, row_ptrs, col_idxs, vals, self.ws,
+                                   self.nbytes)
+
+
+def _sorted_with_diagonal(gk, n, row_ptrs, col_idxs, vals, skip_sorting):
+    """sort_by_column_index unless skipped, then add_diagonal_elements, on a working copy
+    (core/factorization/ilu.cpp:80-86)"""
+    ci, v = col_idxs.clone(), vals.clone()
+    if not skip_sorting:
+        sorted_flag = ctypes.c_int(0)
+        s = torch.cuda.current_stream().cuda_stream
+        ws = torch.zeros(8, dtype=torch.uint8, device=v.device)
+        gk.csr_is_sorted_by_column_index_i32(s, n, row_ptrs, ci, ws, 8, ctypes.addressof(sorted_flag))
+        if not sorted_flag.value:
+            gk.csr_sort_by_column_index_f64_i32(s, n, row_ptrs, ci, v)
+    rp, ci2, v2 = _with_diagonal(gk, n, row_ptrs, ci, v)
+    return rp, ci2, v2
+
+
+def ilu_generate(gk, n, row_ptrs, col_idxs, vals, nrhs=1, skip_sorting=False):
+    """preconditioner::Ilu over factorization::Ilu, the exact ILU(0) (core/factorization/ilu.cpp:67-124): sort,
+    add_diagonal_elements, compute_lu, initialize_l_u.  .L / .U hold the factors, .analysis the level analysis."""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = vals.device
+    rp, ci, v = _sorted_with_diagonal(gk, n, row_ptrs, col_idxs, vals, skip_sorting)
+    an = FactorizationAnalysis(gk, n, rp, ci)
+    an.compute_lu(rp, ci, v)
+    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    urp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    sb = gk.prefix_sum_workspace_bytes(n + 1)
+    sws = torch.empty(max(sb, 8), dtype=torch.uint8, device=dv)
+    gk.factorization_initialize_row_ptrs_l_u_i32(s, n, rp, ci, lrp, urp, sws, sb)
+    lnnz, unnz = int(lrp[n].item()), int(urp[n].item())
+    lc, lv = torch.zeros(lnnz, dtype=torch.int32, device=dv), torch.zeros(lnnz, dtype=torch.float64, device=dv)
+    uc, uv = torch.zeros(unnz, dtype=torch.int32, device=dv), torch.zeros(unnz, dtype=torch.float64, device=dv)
+    gk.factorization_initialize_l_u_f64_i32(s, n, rp, ci, v, lrp, lc, lv, urp, uc, uv)
+    p = ilu_from_factors(gk, n, (lrp, lc, lv), (urp, uc, uv), nrhs=nrhs)
+    p.L, p.U, p.analysis = (lrp, lc, lv), (urp, uc, uv), an
+    return p
+
+
+def ic_generate(gk, n, row_ptrs, col_idxs, vals, nrhs=1, skip_sorting=False):
+    """preconditioner::Ic over factorization::Ic, the exact IC(0) (core/factorization/ic.cpp:67-120): sort,
+    add_diagonal_elements, compute, initialize_l, L^T.  .L / .Lt hold the factors."""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = vals.device
+    rp, ci, v = _sorted_with_diagonal(gk, n, row_ptrs, col_idxs, vals, skip_sorting)
+    an = FactorizationAnalysis(gk, n, rp, ci)
+    an.ic_compute(rp, ci, v)
+    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    sb = gk.prefix_sum_workspace_bytes(n + 1)
+    sws = torch.empty(max(sb, 8), dtype=torch.uint8, device=dv)
+    gk.factorization_initialize_row_ptrs_l_i32(s, n, rp, ci, lrp, sws, sb)
+    lnnz = int(lrp[n].item())
+    lc, lv = torch.zeros(lnnz, dtype=torch.int32, device=dv), torch.zeros(lnnz, dtype=torch.float64, device=dv)
+    gk.factorization_initialize_l_f64_i32(s, n, rp, ci, v, lrp, lc, lv, 0)
+    Lt = _transpose(gk, n, lrp, lc, lv)
+    p = ilu_from_factors(gk, n, (lrp, lc, lv), Lt, nrhs=nrhs)
+    p.L, p.Lt, p.analysis = (lrp, lc, lv), Lt, an
+    return p

@@ -2885,6 +2885,144 @@ protected:
 };
 }  // namespace factorization
 
+// ---- Ilu + Ic, the exact ILU(0) / IC(0) (core/factorization/ilu.cpp:67-124, ic.cpp:67-120) ------
+namespace factorization {
+namespace detail_exact {
+// the working copy both generate chains factorize: sorted unless skipped, explicit diagonal, then
+// gkomi_ilu_analyse_i32 + the numeric phase in place
+template <typename V, typename I>
+struct working_copy {
+    size_type n{0}, nnz{0};
+    array<I> rp, ci;
+    array<V> v;
+    working_copy(std::shared_ptr<const Executor> exec, const LinOp* A, bool skip_sorting, bool ic, const char* who)
+    {
+        static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "the exact factorizations are <double, int32>");
+        detail::require_device(exec, who);
+        auto src = as<const matrix::Csr<V, I>>(A);
+        n = src->get_size()[0];
+        if (n != src->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, std::string(who) + " needs a square matrix");
+        std::unique_ptr<matrix::Csr<V, I>> sorted;
+        if (!skip_sorting && !src->is_sorted_by_column_index()) {
+            matrix_data<V, I> d;
+            src->write(d);
+            sorted = matrix::Csr<V, I>::create(exec);
+            sorted->read(d);
+            sorted->sort_by_column_index();
+            src = sorted.get();
+        }
+        rp = array<I>(exec, n + 1);
+        exec->copy(n + 1, src->get_const_row_ptrs(), rp.get_data());
+        nnz = src->get_num_stored_elements();
+        array<char> fws(exec, gkomi_factorization_workspace_bytes(n));
+        int64_t missing = 0;
+        GKOMI_CALL(gkomi_factorization_count_missing_diagonal_i32(nullptr, n, n, rp.get_const_data(), src->get_const_col_idxs(), fws.get_data(), fws.get_num_elems(), &missing));
+        ci = array<I>(exec, nnz + missing);
+        v = array<V>(exec, nnz + missing);
+        if (missing) {
+            GKOMI_CALL(gkomi_factorization_add_diagonal_elements_f64_i32(nullptr, n, n, rp.get_data(), src->get_const_col_idxs(), src->get_const_values(), ci.get_data(), v.get_data(), fws.get_const_data()));
+        } else {
+            exec->copy(nnz, src->get_const_col_idxs(), ci.get_data());
+            exec->copy(nnz, src->get_const_values(), v.get_data());
+        }
+        nnz += missing;
+        array<char> aws(exec, gkomi_ilu_analysis_workspace_bytes(n));
+        int64_t info[6] = {};
+        GKOMI_CALL(gkomi_ilu_analyse_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), aws.get_data(), aws.get_num_elems(), info));
+        if (ic) {
+            GKOMI_CALL(gkomi_ic_compute_f64_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), v.get_data(), aws.get_const_data(), aws.get_num_elems()));
+        } else {
+            GKOMI_CALL(gkomi_ilu_compute_lu_f64_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), v.get_data(), aws.get_const_data(), aws.get_num_elems()));
+        }
+        exec->synchronize();  // the analysis workspace leaves scope
+    }
+};
+}  // namespace detail_exact
+
+template <typename V = double, typename I = int32>
+class Ilu {
+public:
+    using matrix_type = matrix::Csr<V, I>;
+    class Factory {
+    public:
+        Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
+        Factory& with_l_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { l_strategy_ = std::move(s); return *this; }
+        Factory& with_u_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { u_strategy_ = std::move(s); return *this; }
+        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
+        std::unique_ptr<Ilu> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Ilu>(new Ilu(*this, std::move(A))); }
+        std::shared_ptr<const Executor> exec_;
+        bool skip_sorting_{false};
+        std::shared_ptr<typename matrix_type::strategy_type> l_strategy_, u_strategy_;
+    };
+    static Factory build() { return Factory{}; }
+    std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
+    std::shared_ptr<const matrix_type> get_u_factor() const { return u_; }
+protected:
+    Ilu(const Factory& f, std::shared_ptr<const LinOp> A)
+    {
+        const auto& exec = f.exec_;
+        detail_exact::working_copy<V, I> w(exec, A.get(), f.skip_sorting_, false, "ilu_factorization");
+        const size_type n = w.n;
+        array<I> lrp(exec, n + 1), urp(exec, n + 1);
+        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
+        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_u_i32(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), lrp.get_data(), urp.get_data(), sws.get_data(), sws.get_num_elems()));
+        const size_type lnnz = exec->copy_val_to_host(lrp.get_const_data() + n), unnz = exec->copy_val_to_host(urp.get_const_data() + n);
+        array<I> lc(exec, lnnz), uc(exec, unnz);
+        array<V> lv(exec, lnnz), uv(exec, unnz);
+        GKOMI_CALL(gkomi_factorization_initialize_l_u_f64_i32(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), w.v.get_const_data(), lrp.get_const_data(), lc.get_data(), lv.get_data(), urp.get_const_data(), uc.get_data(), uv.get_data()));
+        auto l = matrix_type::create(exec); auto u = matrix_type::create(exec);
+        l->adopt(dim<2>(n, n), std::move(lrp), std::move(lc), std::move(lv));
+        u->adopt(dim<2>(n, n), std::move(urp), std::move(uc), std::move(uv));
+        if (f.l_strategy_) l->set_strategy(f.l_strategy_);
+        if (f.u_strategy_) u->set_strategy(f.u_strategy_);
+        l_ = std::move(l); u_ = std::move(u);
+    }
+    std::shared_ptr<matrix_type> l_, u_;
+};
+
+template <typename V = double, typename I = int32>
+class Ic {
+public:
+    using matrix_type = matrix::Csr<V, I>;
+    class Factory {
+    public:
+        Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
+        Factory& with_both_factors(bool both) { both_factors_ = both; return *this; }
+        Factory& with_l_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { l_strategy_ = std::move(s); return *this; }
+        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
+        std::unique_ptr<Ic> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Ic>(new Ic(*this, std::move(A))); }
+        std::shared_ptr<const Executor> exec_;
+        bool skip_sorting_{false}, both_factors_{true};
+        std::shared_ptr<typename matrix_type::strategy_type> l_strategy_;
+    };
+    static Factory build() { return Factory{}; }
+    std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
+    // nullptr when generated with_both_factors(false)
+    std::shared_ptr<const matrix_type> get_lt_factor() const { return lt_; }
+protected:
+    Ic(const Factory& f, std::shared_ptr<const LinOp> A)
+    {
+        const auto& exec = f.exec_;
+        detail_exact::working_copy<V, I> w(exec, A.get(), f.skip_sorting_, true, "ic_factorization");
+        const size_type n = w.n;
+        array<I> lrp(exec, n + 1);
+        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
+        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_i32(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), lrp.get_data(), sws.get_data(), sws.get_num_elems()));
+        const size_type lnnz = exec->copy_val_to_host(lrp.get_const_data() + n);
+        array<I> lc(exec, lnnz);
+        array<V> lv(exec, lnnz);
+        GKOMI_CALL(gkomi_factorization_initialize_l_f64_i32(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), w.v.get_const_data(), lrp.get_const_data(), lc.get_data(), lv.get_data(), 0));
+        auto l = matrix_type::create(exec);
+        l->adopt(dim<2>(n, n), std::move(lrp), std::move(lc), std::move(lv));
+        if (f.l_strategy_) l->set_strategy(f.l_strategy_);
+        if (f.both_factors_) lt_ = l->transpose();
+        l_ = std::move(l);
+    }
+    std::shared_ptr<matrix_type> l_, lt_;
+};
+}  // namespace factorization
+
+
 namespace preconditioner {
 template <typename V = double, typename I = int32>
 class Ilu : public LinOp, public Transposable, public ::gko::detail::native_preconditioner {
@@ -2935,9 +3073,16 @@ public:
         Factory() : LinOpFactory(nullptr) {}
         Factory& with_factorization_iterations(size_type n) { iterations_ = n; return *this; }
         std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
-        std::unique_ptr<Ilu> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Ilu>(new Ilu(this->exec_, iterations_, std::move(A))); }
+        // the exact ILU(0) instead of the default ParIlu sweeps
+        Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::Ilu<V, I>::Factory> f) { exact_ = std::move(f); return *this; }
+        std::unique_ptr<Ilu> generate(std::shared_ptr<const LinOp> A) const
+        {
+            if (exact_) return std::unique_ptr<Ilu>(new Ilu(this->exec_, *exact_, std::move(A)));
+            return std::unique_ptr<Ilu>(new Ilu(this->exec_, iterations_, std::move(A)));
+        }
         std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
         size_type iterations_{0};
+        std::shared_ptr<const typename ::gko::factorization::Ilu<V, I>::Factory> exact_;
     };
     static Factory build() { return Factory{}; }
     std::shared_ptr<const LinOp> get_l_solver() const { return l_solver_; }
@@ -2958,6 +3103,14 @@ protected:
     Ilu(std::shared_ptr<const Executor> exec, size_type iterations, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
     {
         auto fact = factorization::ParIlu<V, I>::build().with_iterations(iterations).on(exec)->generate(std::move(A));
+        l_factor_ = fact->get_l_factor();
+        u_factor_ = fact->get_u_factor();
+        l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(l_factor_);
+        u_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(u_factor_);
+    }
+    Ilu(std::shared_ptr<const Executor> exec, const typename ::gko::factorization::Ilu<V, I>::Factory& exact, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
+    {
+        auto fact = (exact.exec_ ? exact : *exact.on(exec)).generate(std::move(A));
         l_factor_ = fact->get_l_factor();
         u_factor_ = fact->get_u_factor();
         l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(l_factor_);
@@ -3058,9 +3211,16 @@ public:
         Factory() : LinOpFactory(nullptr) {}
         Factory& with_factorization_iterations(size_type n) { iterations_ = n; return *this; }
         std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
-        std::unique_ptr<Ic> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Ic>(new Ic(this->exec_, iterations_, std::move(A))); }
+        // the exact IC(0) instead of the default ParIc sweeps
+        Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::Ic<V, I>::Factory> f) { exact_ = std::move(f); return *this; }
+        std::unique_ptr<Ic> generate(std::shared_ptr<const LinOp> A) const
+        {
+            if (exact_) return std::unique_ptr<Ic>(new Ic(this->exec_, *exact_, std::move(A)));
+            return std::unique_ptr<Ic>(new Ic(this->exec_, iterations_, std::move(A)));
+        }
         std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
         size_type iterations_{0};
+        std::shared_ptr<const typename ::gko::factorization::Ic<V, I>::Factory> exact_;
     };
     static Factory build() { return Factory{}; }
     std::shared_ptr<const LinOp> get_l_solver() const { return l_solver_; }
@@ -3070,6 +3230,14 @@ protected:
     Ic(std::shared_ptr<const Executor> exec, size_type iterations, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
     {
         auto fact = factorization::ParIc<V, I>::build().with_iterations(iterations).on(exec)->generate(std::move(A));
+        l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(fact->get_l_factor());
+        lh_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(fact->get_lt_factor());
+    }
+    Ic(std::shared_ptr<const Executor> exec, const typename ::gko::factorization::Ic<V, I>::Factory& exact, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
+    {
+        auto both = exact;
+        both.with_both_factors(true);  // the preconditioner needs L^T whatever the factory says
+        auto fact = (both.exec_ ? both : *both.on(exec)).generate(std::move(A));
         l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(fact->get_l_factor());
         lh_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(fact->get_lt_factor());
     }
