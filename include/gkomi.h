@@ -1073,6 +1073,110 @@ int gkomi_ic_compute_f64_i32(gkomi_stream_t s, int64_t n,
                              const int32_t* row_ptrs, const int32_t* col_idxs,
                              double* vals, const void* analysis_workspace,
                              size_t workspace_bytes);
+/* ---- sparse direct solver: symbolic Cholesky, Lu, solver::Direct -----------
+ * experimental::factorization::Lu (core/factorization/lu.cpp:85-145),
+ * symbolic_cholesky (core/factorization/symbolic.cpp:66-93), elimination_forest
+ * (core/factorization/elimination_forest.cpp:44-207); experimental::solver::Direct
+ * (core/solver/direct.cpp:131-227) then applies the combined factor with
+ * gkomi_lower_trs_solve_f64_i32 (unit_diag = 1) and gkomi_upper_trs_solve_f64_i32,
+ * which ignore the other triangle.  <double, int32>.  Every entry rejects bad
+ * arguments before any HIP call.
+ *
+ * compute_elim_forest (core/factorization/elimination_forest.cpp:183-207, loop for
+ * loop :44-152): host code there and here.  Outputs: parents[n], child_ptrs[n + 2],
+ * children[n], postorder[n], inv_postorder[n], postorder_parents[n]; the
+ * pseudo-root of every tree is n.  Only entries col < row are read; rows need not
+ * be sorted nor store a diagonal.  The _host entry takes host arrays and needs no
+ * device; the other one takes device arrays, copies the pattern to the host,
+ * computes, writes device arrays, and blocks.  GKOMI_EINVAL for decreasing
+ * row_ptrs or a negative column. */
+int gkomi_elimination_forest_host_i32(int64_t n, const int32_t* host_row_ptrs,
+                                      const int32_t* host_col_idxs,
+                                      int32_t* parents, int32_t* child_ptrs,
+                                      int32_t* children, int32_t* postorder,
+                                      int32_t* inv_postorder,
+                                      int32_t* postorder_parents);
+int gkomi_elimination_forest_i32(gkomi_stream_t s, int64_t n,
+                                 const int32_t* row_ptrs,
+                                 const int32_t* col_idxs, int32_t* parents,
+                                 int32_t* child_ptrs, int32_t* children,
+                                 int32_t* postorder, int32_t* inv_postorder,
+                                 int32_t* postorder_parents);
+/* cholesky::cholesky_symbolic_count / cholesky_symbolic_factorize
+ * (core/factorization/cholesky_kernels.hpp;
+ * common/cuda_hip/factorization/cholesky_kernels.hpp.inc:34-149, results as the
+ * reference executor's, reference/factorization/cholesky_kernels.cpp:58-128): the
+ * pattern of the Cholesky factor L of a matrix with symmetric pattern, from its
+ * entries col < row and its elimination forest.  A row of A need not store its
+ * diagonal and need not be sorted.
+ *   count      row_nnz[0, n) = entries of every row of L with its diagonal, and
+ *              *host_factor_nnz = their sum in 64 bits (blocking).  A sum beyond
+ *              INT32_MAX is GKOMI_ENOTSUPPORTED (the caller's prefix sum,
+ *              gkomi_prefix_sum_i32 over n + 1 entries, is 32 bits wide).
+ *   factorize  out_cols[out_row_ptrs[row], out_row_ptrs[row + 1]) = the columns
+ *              of row `row` of L, the diagonal last, the others in no specified
+ *              order (symbolic_cholesky sorts next).  Writes exactly that range.
+ *              Blocking.
+ * Both: workspace gkomi_cholesky_symbolic_workspace_bytes(n, nnz) bytes, nothing
+ * kept in it between the calls.  GKOMI_EINVAL if the forest arrays are not a
+ * forest's (an index out of range, a postorder parent that is not larger than its
+ * node) or if out_row_ptrs is not the prefix sum of row_nnz; no access leaves
+ * the arrays in either case. */
+size_t gkomi_cholesky_symbolic_workspace_bytes(int64_t n, int64_t nnz);
+int gkomi_cholesky_symbolic_count_i32(gkomi_stream_t s, int64_t n, int64_t nnz,
+                                      const int32_t* row_ptrs,
+                                      const int32_t* col_idxs,
+                                      const int32_t* inv_postorder,
+                                      const int32_t* postorder_parents,
+                                      int32_t* row_nnz, void* workspace,
+                                      size_t workspace_bytes,
+                                      int64_t* host_factor_nnz);
+int gkomi_cholesky_symbolic_factorize_i32(
+    gkomi_stream_t s, int64_t n, int64_t nnz, const int32_t* row_ptrs,
+    const int32_t* col_idxs, const int32_t* postorder,
+    const int32_t* inv_postorder, const int32_t* postorder_parents,
+    const int32_t* out_row_ptrs, int32_t* out_cols, void* workspace,
+    size_t workspace_bytes);
+/* lu_factorization::initialize (core/factorization/lu_kernels.hpp;
+ * common/cuda_hip/factorization/lu_kernels.hpp.inc:36-78,
+ * reference/factorization/lu_kernels.cpp:58-90): the factor's values zeroed, the
+ * values of A scattered into the factor's pattern (rows strictly ascending; the
+ * column is found by binary search, the reference's lookup structures of
+ * csr::build_lookup are not built), diag_idxs[row] = position of the diagonal.
+ * Where an entry of A has no place in the factor's row the reference's
+ * lookup_unsafe is undefined; here the entry is skipped and the call returns
+ * GKOMI_EINVAL, as it does for a factor row without diagonal (diag_idxs -1).
+ * Blocks on a 4-byte flag: workspace_bytes >= 4.  A row of A that repeats a
+ * column keeps one of its values, which one is not specified. */
+int gkomi_lu_initialize_f64_i32(gkomi_stream_t s, int64_t n,
+                                const int32_t* a_row_ptrs,
+                                const int32_t* a_col_idxs, const double* a_vals,
+                                int64_t factor_nnz, const int32_t* f_row_ptrs,
+                                const int32_t* f_col_idxs, double* f_vals,
+                                int32_t* diag_idxs, void* workspace,
+                                size_t workspace_bytes);
+/* lu_factorization::factorize (core/factorization/lu_kernels.hpp;
+ * reference/factorization/lu_kernels.cpp:96-126) on an analysed workspace of
+ * gkomi_ilu_analyse_i32 for the factor's pattern: the function behind
+ * gkomi_ilu_compute_lu_f64_i32, no second kernel.  Why the bits are the
+ * reference's: factorize walks the lower entries k of a row in ascending order,
+ * forms l = a_ik / u_kk and subtracts l * u_kj from the entry (i, j) of every
+ * j > k that row k stores -- the row-wise form of compute_lu in csrc/ilu.hip, term
+ * for term and in the same order; compute_lu skips a j that row i does not
+ * store, and on a pattern closed under fill (symbolic_cholesky's, or any the
+ * caller guarantees) there is none to skip.  The reference's HIP kernel
+ * (lu_kernels.hpp.inc:82-154) spin-waits on flags of other workgroups and is not
+ * ported: the level schedule waits on no other workgroup. */
+int gkomi_lu_factorize_f64_i32(gkomi_stream_t s, int64_t n,
+                               const int32_t* f_row_ptrs,
+                               const int32_t* f_col_idxs, double* f_vals,
+                               const void* analysis_workspace,
+                               size_t workspace_bytes);
+/* Lu::generate_impl's choice of the symbolic phase (core/factorization/lu.cpp:94-99):
+ * GKOMI_ENOTSUPPORTED without a symbolic factorization and without
+ * symmetric_sparsity, GKOMI_SUCCESS otherwise. */
+int gkomi_lu_symbolic_supported(int has_symbolic, int symmetric_sparsity);
+
 /* ---- matrix assembly: device_matrix_data ---------- */
 /* components::{sort_row_major, sum_duplicates, remove_zeros}
  * (core/base/device_matrix_data_kernels.hpp;

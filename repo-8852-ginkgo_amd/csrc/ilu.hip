@@ -176,21 +176,6 @@ __device__ __forceinline__ void wst(double* p, double v)
     }
 }
 
-// position of `col` among cols[lo, hi) (strictly ascending), -1 if it is not stored
-__device__ __forceinline__ int find_col(const int32_t* __restrict__ cols, int lo, int hi, int col)
-{
-    const int end = hi;
-    while (lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        if (cols[mid] < col) {
-            lo = mid + 1;
-        } else {
-            hi = mid;
-        }
-    }
-    return lo < end && cols[lo] == col ? lo : -1;
-}
-
 // compute_lu of one row by a group of W lanes (t = my lane in the group).  w: the working row (len entries).
 template <int W, bool InMemory, bool Coherent, class Meet>
 __device__ __forceinline__ void ilu_row(int t, int row, const int32_t* __restrict__ row_ptrs,
@@ -440,6 +425,14 @@ int compute(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_
 }
 
 }  // namespace
+
+// the numeric phase of lu_factorization::factorize (lu.hip) is compute_lu on a pattern closed under fill
+int ilu_compute_lu(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs, double* vals,
+                   const void* analysis_workspace, size_t workspace_bytes)
+{
+    return compute<false>(stream, n, row_ptrs, col_idxs, vals, analysis_workspace, workspace_bytes);
+}
+
 }  // namespace gkomi
 
 using namespace gkomi;
@@ -573,7 +566,7 @@ extern "C" int gkomi_ilu_compute_lu_f64_i32(gkomi_stream_t s, int64_t n, const i
                                             const int32_t* col_idxs, double* vals, const void* analysis_workspace,
                                             size_t workspace_bytes)
 {
-    return compute<false>(to_stream(s), n, row_ptrs, col_idxs, vals, analysis_workspace, workspace_bytes);
+    return ilu_compute_lu(to_stream(s), n, row_ptrs, col_idxs, vals, analysis_workspace, workspace_bytes);
 }
 
 extern "C" int gkomi_ic_compute_f64_i32(gkomi_stream_t s, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs,

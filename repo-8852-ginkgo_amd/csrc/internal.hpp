@@ -341,4 +341,26 @@ int trs_iota(hipStream_t stream, int64_t n, int32_t* rows);
 // level_start[l] = first position of level l in level order, level_start[nlevels] = n
 int trs_level_starts(hipStream_t stream, int64_t n, int64_t nlevels, const int32_t* level_sorted, int32_t* level_start);
 
+
+// ---- shared by the exact factorizations (ilu.hip) and the direct solver's setup (lu.hip) ---------------
+// compute_lu on an analysed workspace of gkomi_ilu_analyse_i32: what gkomi_ilu_compute_lu_f64_i32 runs
+int ilu_compute_lu(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs, double* vals,
+                   const void* analysis_workspace, size_t workspace_bytes);
+#ifdef __HIPCC__
+// position of `col` among cols[lo, hi) (strictly ascending), -1 if it is not stored
+__device__ __forceinline__ int find_col(const int32_t* __restrict__ cols, int lo, int hi, int col)
+{
+    const int end = hi;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (cols[mid] < col) {
+            lo = mid + 1;
+        } else {
+            hi = mid;
+        }
+    }
+    return lo < end && cols[lo] == col ? lo : -1;
+}
+#endif
+
 }  // namespace gkomi

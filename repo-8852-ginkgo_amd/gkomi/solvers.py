@@ -641,3 +641,152 @@ def ic_generate(gk, n, row_ptrs, col_idxs, vals, nrhs=1, skip_sorting=False):
     p = ilu_from_factors(gk, n, (lrp, lc, lv), Lt, nrhs=nrhs)
     p.L, p.Lt, p.analysis = (lrp, lc, lv), Lt, an
     return p
+
+
+# ---- sparse direct solver: symbolic Cholesky, Lu, Direct ------------------------------------------------
+
+FOREST_FIELDS = ("parents", "child_ptrs", "children", "postorder", "inv_postorder", "postorder_parents")
+
+
+def elimination_forest(gk, n, row_ptrs, col_idxs):
+    """factorization::compute_elim_forest (core/factorization/elimination_forest.cpp:183-207) of a device CSR pattern:
+    dict of the six int32 device arrays (child_ptrs has n + 2 entries, the pseudo-root is n).  Host work, blocking."""
+    dv = row_ptrs.device
+    out = {k: torch.zeros(n + 2 if k == "child_ptrs" else max(n, 1), dtype=torch.int32, device=dv) for k in FOREST_FIELDS}
+    gk.elimination_forest_i32(torch.cuda.current_stream().cuda_stream, n, row_ptrs, col_idxs,
+                              *(out[k] for k in FOREST_FIELDS))
+    return {k: (v if k == "child_ptrs" else v[:n]) for k, v in out.items()}
+
+
+def symbolic_cholesky(gk, n, row_ptrs, col_idxs, forest=None):
+    """factorization::symbolic_cholesky (core/factorization/symbolic.cpp:66-93): count, prefix sum, factorize, sort,
+    transpose, spgeam.  Returns (L, combined), each (row_ptrs, col_idxs, vals): the sorted pattern of the Cholesky
+    factor and the pattern of L + L^T; the values these steps drag along are zeros."""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = row_ptrs.device
+    nnz = int(col_idxs.numel())
+    if forest is None:
+        forest = elimination_forest(gk, n, row_ptrs, col_idxs)
+    nb = gk.cholesky_symbolic_workspace_bytes(n, nnz)
+    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dv)
+    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    factor_nnz = ctypes.c_int64(0)
+    gk.cholesky_symbolic_count_i32(s, n, nnz, row_ptrs, col_idxs, forest["inv_postorder"], forest["postorder_parents"],
+                                   lrp, ws, nb, ctypes.addressof(factor_nnz))
+    sb = gk.prefix_sum_workspace_bytes(n + 1)
+    sws = torch.empty(max(sb, 8), dtype=torch.uint8, device=dv)
+    gk.prefix_sum_i32(s, lrp, n + 1, sws, sb)
+    lnnz = int(factor_nnz.value)
+    lc = torch.zeros(lnnz, dtype=torch.int32, device=dv)
+    lv = torch.zeros(lnnz, dtype=torch.float64, device=dv)
+    gk.cholesky_symbolic_factorize_i32(s, n, nnz, row_ptrs, col_idxs, forest["postorder"], forest["inv_postorder"],
+                                       forest["postorder_parents"], lrp, lc, ws, nb)
+    gk.csr_sort_by_column_index_f64_i32(s, n, lrp, lc, lv)
+    trp, tc, tv = _transpose(gk, n, lrp, lc, lv)
+    # L^T->apply(one, Identity, one, L): L becomes 1 * L^T + 1 * L
+    one = torch.ones(1, dtype=torch.float64, device=dv)
+    gb = gk.csr_spgeam_workspace_bytes(n)
+    gws = torch.empty(max(gb, 8), dtype=torch.uint8, device=dv)
+    crp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    cnnz = ctypes.c_int64(0)
+
+    def spgeam(cc, cv):
+        gk.csr_spgeam_f64_i32(s, n, n, one, lnnz, trp, tc, tv, one, n, n, lnnz, lrp, lc, lv, crp, cc, cv,
+                              ctypes.addressof(cnnz), gws, gb)
+    spgeam(None, None)
+    cc = torch.zeros(int(cnnz.value), dtype=torch.int32, device=dv)
+    cv = torch.zeros(int(cnnz.value), dtype=torch.float64, device=dv)
+    if cnnz.value:
+        spgeam(cc, cv)
+    return (lrp, lc, lv), (crp, cc, cv)
+
+
+class LuFactorization:
+    """experimental::factorization::Factorization in its combined_lu storage (what Lu::generate returns,
+    core/factorization/lu.cpp:144): .combined = (row_ptrs, col_idxs, vals) holds L below the diagonal (its unit
+    diagonal is not stored) and U on and above it, .diag_idxs the position of every diagonal, .analysis the
+    FactorizationAnalysis of the pattern."""
+
+    def __init__(self, gk, n, a_row_ptrs, a_col_idxs, pattern):
+        self.gk, self.n = gk, int(n)
+        self.a_row_ptrs, self.a_col_idxs = a_row_ptrs, a_col_idxs
+        frp, fc = pattern
+        dv = frp.device
+        self.combined = (frp, fc, torch.zeros(int(fc.numel()), dtype=torch.float64, device=dv))
+        self.diag_idxs = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dv)[:self.n]
+        self._flag = torch.zeros(8, dtype=torch.uint8, device=dv)
+        # rejects rows that are not strictly ascending or lack their diagonal before anything searches them
+        self.analysis = FactorizationAnalysis(gk, self.n, frp, fc)
+
+    def refactorize(self, vals):
+        """new values of A on the same pattern: lu_factorization::initialize, then factorize on the kept analysis"""
+        s = torch.cuda.current_stream().cuda_stream
+        frp, fc, fv = self.combined
+        self.gk.lu_initialize_f64_i32(s, self.n, self.a_row_ptrs, self.a_col_idxs, vals, int(fc.numel()), frp, fc, fv,
+                                      self.diag_idxs, self._flag, 8)
+        self.gk.lu_factorize_f64_i32(s, self.n, frp, fc, fv, self.analysis.ws, self.analysis.nbytes)
+        return self
+
+
+def lu_generate(gk, n, row_ptrs, col_idxs, vals, symbolic=None, symmetric_sparsity=False):
+    """experimental::factorization::Lu::generate (core/factorization/lu.cpp:85-145).  symbolic: (row_ptrs, col_idxs)
+    of the factor's pattern (sorted rows, diagonal stored, closed under fill), copied; without one,
+    symmetric_sparsity=True takes symbolic_cholesky of the matrix and anything else raises
+    GkomiError(GKOMI_ENOTSUPPORTED) like lu.cpp:94-99."""
+    gk.lu_symbolic_supported(int(symbolic is not None), int(bool(symmetric_sparsity)))
+    if symbolic is not None:
+        pattern = (symbolic[0].clone(), symbolic[1].clone())
+    else:
+        pattern = symbolic_cholesky(gk, n, row_ptrs, col_idxs)[1][:2]
+    return LuFactorization(gk, n, row_ptrs, col_idxs, pattern).refactorize(vals)
+
+
+class Direct:
+    """experimental::solver::Direct over a combined_lu factorization (core/solver/direct.cpp:131-227):
+    LowerTrs(unit_diagonal) then UpperTrs on the combined matrix through one intermediate vector.  Both solves are the
+    analysis-free kernels (csrc/trs.hip), which skip the entries of the other triangle; the level plan and the brick
+    plan are not handed a two-sided matrix."""
+
+    def __init__(self, gk, lu, nrhs=1):
+        self.gk, self.lu, self.n, self.nrhs = gk, lu, lu.n, int(nrhs)
+        dv = lu.combined[2].device
+        self.intermediate = torch.zeros((self.n, self.nrhs), dtype=torch.float64, device=dv)
+        self.trs_bytes = gk.trs_workspace_bytes()
+        self.trs_workspace = torch.zeros(self.trs_bytes, dtype=torch.uint8, device=dv)
+
+    def _solve(self, b, x):
+        s = torch.cuda.current_stream().cuda_stream
+        rp, ci, v = self.lu.combined
+        y = self.intermediate
+        self.gk.lower_trs_solve_f64_i32(s, self.n, self.nrhs, rp, ci, v, 1, b, b.stride(0), y, y.stride(0),
+                                        self.trs_workspace, self.trs_bytes)
+        self.gk.upper_trs_solve_f64_i32(s, self.n, self.nrhs, rp, ci, v, 0, y, y.stride(0), x, x.stride(0),
+                                        self.trs_workspace, self.trs_bytes)
+
+    def apply(self, *args):
+        """apply(b, x): x = A^-1 b.  apply(alpha, b, beta, x): x = alpha A^-1 b + beta x, as the upper solver's advanced
+        apply composes it (scale, then add_scaled).  b, x: n x nrhs device tensors, row stride >= nrhs."""
+        if len(args) == 2:
+            b, x = args
+            assert b.shape == (self.n, self.nrhs) and x.shape == (self.n, self.nrhs)
+            if self.n > 0:
+                self._solve(b, x)
+            return x
+        alpha, b, beta, x = args
+        assert b.shape == (self.n, self.nrhs) and x.shape == (self.n, self.nrhs)
+        if self.n == 0:
+            return x
+        s = torch.cuda.current_stream().cuda_stream
+        dv = x.device
+        al = alpha if torch.is_tensor(alpha) else torch.tensor([float(alpha)], dtype=torch.float64, device=dv)
+        be = beta if torch.is_tensor(beta) else torch.tensor([float(beta)], dtype=torch.float64, device=dv)
+        plain = torch.zeros((self.n, self.nrhs), dtype=torch.float64, device=dv)
+        self._solve(b, plain)
+        self.gk.dense_scale_f64(s, self.n, self.nrhs, be, 1, x, x.stride(0))
+        self.gk.dense_add_scaled_f64(s, self.n, self.nrhs, al, 1, plain, plain.stride(0), x, x.stride(0))
+        return x
+
+    def overrun(self):
+        flag = ctypes.c_int(0)
+        self.gk.trs_check_overrun(torch.cuda.current_stream().cuda_stream, self.trs_workspace, ctypes.addressof(flag))
+        return bool(flag.value)

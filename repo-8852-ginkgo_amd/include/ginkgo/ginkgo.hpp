@@ -3260,6 +3260,276 @@ protected:
 };
 }  // namespace preconditioner
 
+// ---- the sparse direct solver: elimination forest, symbolic Cholesky, Lu, Direct --------------------
+// (core/factorization/elimination_forest.hpp, symbolic.cpp:66-93, lu.cpp:85-145, core/solver/direct.cpp:131-227)
+namespace factorization {
+// core/factorization/elimination_forest.hpp: the pseudo-root of every tree is `size`; child_ptrs has size + 2 entries
+template <typename I = int32>
+struct elimination_forest {
+    elimination_forest(std::shared_ptr<const Executor> exec, I size)
+        : parents(exec, size), child_ptrs(exec, size + 2), children(exec, size), postorder(exec, size), inv_postorder(exec, size), postorder_parents(exec, size)
+    {}
+    array<I> parents, child_ptrs, children, postorder, inv_postorder, postorder_parents;
+};
+
+// compute_elim_forest (elimination_forest.cpp:183-207): host work on a copy of the pattern; the arrays live where the matrix does
+template <typename V, typename I>
+elimination_forest<I> compute_elim_forest(const matrix::Csr<V, I>* mtx)
+{
+    static_assert(std::is_same<I, int32>::value, "compute_elim_forest: int32 indices");
+    auto exec = mtx->get_executor();
+    const auto n = static_cast<I>(mtx->get_size()[0]);
+    elimination_forest<I> f(exec, n);
+    auto fn = exec->is_device() ? nullptr : gkomi_elimination_forest_host_i32;
+    if (fn != nullptr) {
+        GKOMI_CALL(fn(n, mtx->get_const_row_ptrs(), mtx->get_const_col_idxs(), f.parents.get_data(), f.child_ptrs.get_data(), f.children.get_data(), f.postorder.get_data(),
+                      f.inv_postorder.get_data(), f.postorder_parents.get_data()));
+    } else {
+        GKOMI_CALL(gkomi_elimination_forest_i32(nullptr, n, mtx->get_const_row_ptrs(), mtx->get_const_col_idxs(), f.parents.get_data(), f.child_ptrs.get_data(), f.children.get_data(),
+                                                f.postorder.get_data(), f.inv_postorder.get_data(), f.postorder_parents.get_data()));
+    }
+    return f;
+}
+
+// symbolic_cholesky (symbolic.cpp:66-93): the pattern of L + L^T with zero values, rows sorted
+template <typename V, typename I>
+std::unique_ptr<matrix::Csr<V, I>> symbolic_cholesky(const matrix::Csr<V, I>* mtx)
+{
+    static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "symbolic_cholesky is <double, int32>");
+    using matrix_type = matrix::Csr<V, I>;
+    auto exec = mtx->get_executor();
+    ::gko::detail::require_device(exec, "cholesky::cholesky_symbolic_count");
+    const size_type n = mtx->get_size()[0];
+    const size_type nnz = mtx->get_num_stored_elements();
+    const auto forest = compute_elim_forest(mtx);
+    array<I> row_ptrs(exec, n + 1);
+    row_ptrs.fill(0);
+    array<char> ws(exec, gkomi_cholesky_symbolic_workspace_bytes(n, nnz) + 8);
+    int64_t factor_nnz = 0;
+    GKOMI_CALL(gkomi_cholesky_symbolic_count_i32(nullptr, n, nnz, mtx->get_const_row_ptrs(), mtx->get_const_col_idxs(), forest.inv_postorder.get_const_data(),
+                                                 forest.postorder_parents.get_const_data(), row_ptrs.get_data(), ws.get_data(), ws.get_num_elems(), &factor_nnz));
+    array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
+    GKOMI_CALL(gkomi_prefix_sum_i32(nullptr, row_ptrs.get_data(), n + 1, sws.get_data(), sws.get_num_elems()));
+    array<I> cols(exec, static_cast<size_type>(factor_nnz));
+    array<V> vals(exec, static_cast<size_type>(factor_nnz));
+    vals.fill(V{});
+    GKOMI_CALL(gkomi_cholesky_symbolic_factorize_i32(nullptr, n, nnz, mtx->get_const_row_ptrs(), mtx->get_const_col_idxs(), forest.postorder.get_const_data(),
+                                                     forest.inv_postorder.get_const_data(), forest.postorder_parents.get_const_data(), row_ptrs.get_const_data(), cols.get_data(),
+                                                     ws.get_data(), ws.get_num_elems()));
+    GKOMI_CALL(gkomi_synchronize(nullptr));  // the workspaces leave scope
+    auto factor = matrix_type::create(exec);
+    factor->adopt(mtx->get_size(), std::move(row_ptrs), std::move(cols), std::move(vals));
+    factor->sort_by_column_index();
+    auto lt_factor = factor->transpose();
+    auto scalar = matrix::Dense<V>::create(exec, dim<2>(1, 1));
+    scalar->fill(V{1});
+    auto id = matrix::Identity<V>::create(exec, n);
+    lt_factor->apply(scalar.get(), id.get(), scalar.get(), factor.get());
+    return factor;
+}
+}  // namespace factorization
+
+namespace experimental {
+namespace factorization {
+// include/ginkgo/core/factorization/factorization.hpp: the storage types this backend produces
+enum class storage_type { empty, composition, combined_lu };
+
+template <typename V = double, typename I = int32>
+class Factorization : public LinOp {
+public:
+    using matrix_type = matrix::Csr<V, I>;
+    // L (strictly lower, unit diagonal not stored) and U in one matrix, as Lu::generate leaves them
+    static std::unique_ptr<Factorization> create_from_combined_lu(std::unique_ptr<matrix_type> combined)
+    {
+        auto f = std::unique_ptr<Factorization>(new Factorization(combined->get_executor(), combined->get_size(), storage_type::combined_lu));
+        f->combined_ = std::move(combined);
+        return f;
+    }
+    static std::unique_ptr<Factorization> create_from_composition(std::shared_ptr<const matrix_type> l, std::shared_ptr<const matrix_type> u)
+    {
+        auto f = std::unique_ptr<Factorization>(new Factorization(l->get_executor(), l->get_size(), storage_type::composition));
+        f->lower_ = std::move(l);
+        f->upper_ = std::move(u);
+        return f;
+    }
+    storage_type get_storage_type() const noexcept { return type_; }
+    std::shared_ptr<const matrix_type> get_combined() const { return type_ == storage_type::combined_lu ? combined_ : nullptr; }
+    std::shared_ptr<const matrix_type> get_lower_factor() const { return type_ == storage_type::composition ? lower_ : nullptr; }
+    std::shared_ptr<const matrix_type> get_upper_factor() const { return type_ == storage_type::composition ? upper_ : nullptr; }
+    // the composition L U: L with its unit diagonal stored, U with the diagonal, through factorization::initialize_l_u
+    std::unique_ptr<Factorization> unpack() const
+    {
+        if (type_ == storage_type::composition) return create_from_composition(lower_, upper_);
+        if (type_ == storage_type::empty) GKO_NOT_SUPPORTED("Factorization::unpack of an empty factorization");
+        static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "Factorization is <double, int32>");
+        const auto& exec = exec_;
+        ::gko::detail::require_device(exec, "factorization::initialize_l_u");
+        const size_type n = size_[0];
+        array<I> lrp(exec, n + 1), urp(exec, n + 1);
+        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
+        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_u_i32(nullptr, n, combined_->get_const_row_ptrs(), combined_->get_const_col_idxs(), lrp.get_data(), urp.get_data(),
+                                                                   sws.get_data(), sws.get_num_elems()));
+        const size_type lnnz = exec->copy_val_to_host(lrp.get_const_data() + n), unnz = exec->copy_val_to_host(urp.get_const_data() + n);
+        array<I> lc(exec, lnnz), uc(exec, unnz);
+        array<V> lv(exec, lnnz), uv(exec, unnz);
+        GKOMI_CALL(gkomi_factorization_initialize_l_u_f64_i32(nullptr, n, combined_->get_const_row_ptrs(), combined_->get_const_col_idxs(), combined_->get_const_values(),
+                                                              lrp.get_const_data(), lc.get_data(), lv.get_data(), urp.get_const_data(), uc.get_data(), uv.get_data()));
+        GKOMI_CALL(gkomi_synchronize(nullptr));
+        auto l = matrix_type::create(exec); auto u = matrix_type::create(exec);
+        l->adopt(size_, std::move(lrp), std::move(lc), std::move(lv));
+        u->adopt(size_, std::move(urp), std::move(uc), std::move(uv));
+        return create_from_composition(std::move(l), std::move(u));
+    }
+protected:
+    Factorization(std::shared_ptr<const Executor> exec, const dim<2>& size, storage_type type) : LinOp(std::move(exec), size), type_(type) {}
+    // x = L U b
+    void apply_impl(const LinOp* b, LinOp* x) const override
+    {
+        auto f = type_ == storage_type::composition ? nullptr : unpack();
+        const auto& l = f ? f->lower_ : lower_;
+        const auto& u = f ? f->upper_ : upper_;
+        auto mid = matrix::Dense<V>::create(exec_, b->get_size());
+        u->apply(b, mid.get());
+        l->apply(mid.get(), x);
+    }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
+    {
+        auto f = type_ == storage_type::composition ? nullptr : unpack();
+        const auto& l = f ? f->lower_ : lower_;
+        const auto& u = f ? f->upper_ : upper_;
+        auto mid = matrix::Dense<V>::create(exec_, b->get_size());
+        u->apply(b, mid.get());
+        l->apply(alpha, mid.get(), beta, x);
+    }
+    storage_type type_;
+    std::shared_ptr<const matrix_type> combined_, lower_, upper_;
+};
+
+// experimental::factorization::Lu (core/factorization/lu.cpp:85-145)
+template <typename V = double, typename I = int32>
+class Lu {
+public:
+    using matrix_type = matrix::Csr<V, I>;
+    using factorization_type = Factorization<V, I>;
+    class Factory : public LinOpFactory {
+    public:
+        Factory() : LinOpFactory(nullptr) {}
+        // the pattern of the factors (sorted rows, diagonal stored, closed under fill); copied at generate
+        Factory& with_symbolic_factorization(std::shared_ptr<const matrix_type> s) { symbolic_ = std::move(s); return *this; }
+        // without a symbolic factorization: take symbolic_cholesky of the matrix (its pattern must be symmetric)
+        Factory& with_symmetric_sparsity(bool s) { symmetric_sparsity_ = s; return *this; }
+        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
+        std::unique_ptr<factorization_type> generate(std::shared_ptr<const LinOp> A) const
+        {
+            static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "Lu is <double, int32>");
+            const auto& exec = this->exec_;
+            ::gko::detail::require_device(exec, "lu_factorization::factorize");
+            auto mtx = as<const matrix_type>(A.get());
+            if (mtx->get_size()[0] != mtx->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, "Lu needs a square matrix");
+            const size_type n = mtx->get_size()[0];
+            if (gkomi_lu_symbolic_supported(symbolic_ ? 1 : 0, symmetric_sparsity_ ? 1 : 0) != GKOMI_SUCCESS) {
+                GKO_NOT_SUPPORTED("Lu::generate without a symbolic factorization needs with_symmetric_sparsity(true)");
+            }
+            std::unique_ptr<matrix_type> factors;
+            if (!symbolic_) {
+                factors = ::gko::factorization::symbolic_cholesky(mtx);
+            } else {
+                const size_type factor_nnz = symbolic_->get_num_stored_elements();
+                array<I> rp(exec, n + 1), ci(exec, factor_nnz);
+                array<V> v(exec, factor_nnz);
+                exec->copy_from(symbolic_->get_executor().get(), factor_nnz, symbolic_->get_const_col_idxs(), ci.get_data());
+                exec->copy_from(symbolic_->get_executor().get(), n + 1, symbolic_->get_const_row_ptrs(), rp.get_data());
+                factors = matrix_type::create(exec);
+                factors->adopt(mtx->get_size(), std::move(rp), std::move(ci), std::move(v));
+            }
+            const size_type factor_nnz = factors->get_num_stored_elements();
+            // the level analysis first: it rejects rows that are not strictly ascending or lack their diagonal
+            array<char> aws(exec, gkomi_ilu_analysis_workspace_bytes(n) + 8);
+            int64_t info[6] = {};
+            GKOMI_CALL(gkomi_ilu_analyse_i32(nullptr, n, factors->get_const_row_ptrs(), factors->get_const_col_idxs(), aws.get_data(), aws.get_num_elems(), info));
+            array<I> diag_idxs(exec, n);
+            array<char> flag(exec, 8);
+            GKOMI_CALL(gkomi_lu_initialize_f64_i32(nullptr, n, mtx->get_const_row_ptrs(), mtx->get_const_col_idxs(), mtx->get_const_values(), factor_nnz,
+                                                   factors->get_const_row_ptrs(), factors->get_const_col_idxs(), factors->get_values(), diag_idxs.get_data(), flag.get_data(),
+                                                   flag.get_num_elems()));
+            GKOMI_CALL(gkomi_lu_factorize_f64_i32(nullptr, n, factors->get_const_row_ptrs(), factors->get_const_col_idxs(), factors->get_values(), aws.get_const_data(),
+                                                  aws.get_num_elems()));
+            GKOMI_CALL(gkomi_synchronize(nullptr));  // the analysis leaves scope
+            return factorization_type::create_from_combined_lu(std::move(factors));
+        }
+        std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
+        std::shared_ptr<const matrix_type> symbolic_;
+        bool symmetric_sparsity_{false};
+    };
+    static Factory build() { return Factory{}; }
+};
+}  // namespace factorization
+
+namespace solver {
+// experimental::solver::Direct (core/solver/direct.cpp:131-227): LowerTrs(unit_diagonal) then UpperTrs through one
+// intermediate vector.  A combined factorization is unpacked first (Factorization::unpack): LowerTrs / UpperTrs::generate
+// may pick the level plan or the brick plan, whose analyses are written for one-sided factors.  L then stores its unit
+// diagonal, which a unit-diagonal solve does not read: the same bits as the solve on the combined matrix.
+template <typename V = double, typename I = int32>
+class Direct : public LinOp, public Transposable {
+public:
+    using factorization_type = ::gko::experimental::factorization::Factorization<V, I>;
+    class Factory : public LinOpFactory {
+    public:
+        Factory() : LinOpFactory(nullptr) {}
+        Factory& with_factorization(std::shared_ptr<const LinOpFactory> f) { factorization_ = std::move(f); return *this; }
+        Factory& with_num_rhs(size_type n) { num_rhs_ = n; return *this; }
+        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
+        std::unique_ptr<Direct> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Direct>(new Direct(this, std::move(A))); }
+        std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
+        std::shared_ptr<const LinOpFactory> factorization_;
+        size_type num_rhs_{1};
+    };
+    static Factory build() { return Factory{}; }
+    // the factorization (the reference's EnableSolverBase<Direct, Factorization>)
+    std::shared_ptr<const factorization_type> get_system_matrix() const { return factors_; }
+    std::unique_ptr<LinOp> transpose() const override { GKO_NOT_IMPLEMENTED; }
+    std::unique_ptr<LinOp> conj_transpose() const override { GKO_NOT_IMPLEMENTED; }
+protected:
+    // a Factorization as the system matrix is taken as it is (direct.cpp:114-127)
+    static std::shared_ptr<const factorization_type> generate_factorization(const Factory* f, std::shared_ptr<const LinOp> A)
+    {
+        if (auto given = std::dynamic_pointer_cast<const factorization_type>(A)) return given;
+        if (!f->factorization_) GKO_NOT_SUPPORTED("Direct needs with_factorization(...) unless its system matrix is a Factorization");
+        std::shared_ptr<LinOp> made = f->factorization_->generate_impl(std::move(A));
+        auto fact = std::dynamic_pointer_cast<const factorization_type>(made);
+        if (!fact) GKO_NOT_SUPPORTED("the factorization factory of Direct must produce a Factorization");
+        return fact;
+    }
+    Direct(const Factory* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), A->get_size()), factors_(generate_factorization(f, A))
+    {
+        using ::gko::experimental::factorization::storage_type;
+        if (factors_->get_storage_type() == storage_type::empty) return;
+        const bool combined = factors_->get_storage_type() == storage_type::combined_lu;
+        std::shared_ptr<const factorization_type> split = combined ? std::shared_ptr<const factorization_type>(factors_->unpack()) : factors_;
+        lower_solver_ = ::gko::solver::LowerTrs<V, I>::build().with_num_rhs(f->num_rhs_).with_unit_diagonal(combined).on(exec_)->generate(split->get_lower_factor());
+        upper_solver_ = ::gko::solver::UpperTrs<V, I>::build().with_num_rhs(f->num_rhs_).with_unit_diagonal(false).on(exec_)->generate(split->get_upper_factor());
+    }
+    void apply_impl(const LinOp* b, LinOp* x) const override
+    {
+        if (!lower_solver_ || !upper_solver_) return;
+        auto intermediate = matrix::Dense<V>::create(exec_, b->get_size());
+        lower_solver_->apply(b, intermediate.get());
+        upper_solver_->apply(intermediate.get(), x);
+    }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
+    {
+        if (!lower_solver_ || !upper_solver_) return;
+        auto intermediate = matrix::Dense<V>::create(exec_, b->get_size());
+        lower_solver_->apply(b, intermediate.get());
+        upper_solver_->apply(alpha, intermediate.get(), beta, x);
+    }
+    std::shared_ptr<const factorization_type> factors_;
+    std::shared_ptr<const LinOp> lower_solver_, upper_solver_;
+};
+}  // namespace solver
+}  // namespace experimental
+
 }  // namespace gko
 
 #include "distributed.hpp"
