@@ -7,12 +7,14 @@
  * bench.py's cpu_baseline leg may load this library; the product path
  * (repo-8852-ginkgo_amd/) never does.
  *
- * Pinning: the reference needs cmake-generated code (ginkgo/config.hpp from
- * include/ginkgo/config.hpp.in) and is therefore not built here.  The oracle
- * is pinned against the known-answer vectors of the reference's own tests
- * (reference/test/...), transcribed as data into tests/golden/ JSON files, against the reference's
- * matrices/test/ MatrixMarket data and examples/simple-solver/doc/results.dox -- see
- * tests/test_oracle_golden.py.
+ * Pinning: oracle/ref.mk compiles the reference itself into oracle/_ref/
+ * (never committed) with ref_driver.cpp, our program over its public API, on
+ * top; tests/test_ref_oracle_parity*.py compare every function here with the
+ * reference's own ReferenceExecutor bit for bit, and
+ * tests/test_ref_oracle_table.py checks that none is left out.  The
+ * known-answer vectors of the reference's tests (tests/golden/ JSON files),
+ * its matrices/test/ MatrixMarket data and examples/simple-solver/doc/results.dox
+ * stay as the second pin -- see tests/test_oracle_golden.py.
  *
  * Floating point: compiled with -ffp-contract=off, matching the reference
  * built for baseline x86-64 (no FMA): `c += val * b` is a rounded product

@@ -115,7 +115,9 @@ def compute_omega(nrhs, kappa, tht, residual_norm, omega, stop):
 
 
 def csr_apply(oracle, n, rp, ci, v):
-    """x (n x nrhs) -> A x: oracle.ref_csr_spmv in float64, the same row sums in numpy for any other dtype"""
+    """x (n x nrhs) -> A x: oracle.ref_csr_spmv in float64, the same row sums in numpy for any other dtype.
+    apply.residual(b, x) is b - A x the way core/solver/idr.cpp:172-174 forms it: a copy of b, then the advanced
+    apply(-1, x, 1, residual), which starts each row sum at 1 * b and adds (-1 * value) * x term by term."""
     def apply(x):
         if x.dtype == np.float64:
             xin = np.ascontiguousarray(x)
@@ -124,6 +126,21 @@ def csr_apply(oracle, n, rp, ci, v):
             return out
         prod = v.astype(x.dtype)[:, None] * x[ci]
         return np.add.reduceat(prod, rp[:-1], axis=0)
+
+    def residual(b, x):
+        if x.dtype == np.float64:
+            xin = np.ascontiguousarray(x)
+            out = np.array(b, np.float64, order="C")
+            oracle.ref_csr_advanced_spmv(n, x.shape[1], -1.0, rp, ci, v, xin, x.shape[1], 1.0, out, x.shape[1])
+            return out
+        out = b.astype(x.dtype) * x.dtype.type(1)
+        lens = np.diff(rp)
+        for j in range(int(lens.max()) if n else 0):
+            rows = np.flatnonzero(lens > j)
+            at = rp[rows] + j
+            out[rows] += (-v[at]).astype(x.dtype)[:, None] * x[ci[at]]
+        return out
+    apply.residual = residual
     return apply
 
 
@@ -148,7 +165,7 @@ def solve(apply, b, p, subspace_dim=2, kappa=0.7, max_iters=1000, reduction=1e-1
     stop = np.zeros(nrhs, np.uint8)
     initialize(nrhs, m, p, stop)
     omega = np.ones(nrhs, dt)
-    residual = b - apply(x)
+    residual = apply.residual(b, x) if hasattr(apply, "residual") else b - apply(x)         # :172-174
     norm = lambda w: np.sqrt(np.array([seq_dot(w[:, i], w[:, i]) for i in range(nrhs)], dt))
     goal = reduction * norm(b)
     residual_norm = norm(residual)                               # :175
