@@ -1073,6 +1073,109 @@ int gkomi_ic_compute_f64_i32(gkomi_stream_t s, int64_t n,
                              const int32_t* row_ptrs, const int32_t* col_idxs,
                              double* vals, const void* analysis_workspace,
                              size_t workspace_bytes);
+/* ---- ParILUT: factorization::ParIlut (core/factorization/par_ilut.cpp:190-344)
+ * The kernels of core/factorization/par_ilut_kernels.hpp with the results of the
+ * REFERENCE executor (reference/factorization/par_ilut_kernels.cpp), bit for bit;
+ * <double, int32>.  The caller owns every allocation; an entry that produces a
+ * matrix is called twice, first to count (output index / value arrays NULL: the
+ * row pointers and the totals are written, blocking), then to fill.  Every entry
+ * rejects bad arguments before any HIP call.
+ *
+ * threshold_select (:73-90): *host_threshold = the |value| of rank `rank`
+ * (0-based) among vals[0, nnz) -- magnitudes as 63-bit keys through the library's
+ * radix sort, element `rank` read back.  Blocking.  rank outside [0, nnz) is
+ * GKOMI_EINVAL.  Workspace gkomi_par_ilut_select_workspace_bytes(nnz). */
+size_t gkomi_par_ilut_select_workspace_bytes(int64_t nnz);
+int gkomi_par_ilut_threshold_select_f64(gkomi_stream_t s, int64_t nnz,
+                                        const double* vals, int64_t rank,
+                                        void* workspace, size_t workspace_bytes,
+                                        double* host_threshold);
+/* The threshold of threshold_filter_approx (:206-247) with exactly the reference
+ * executor's sampling: sample i = |vals[(int32)(i * (double(nnz) / 1024))]| for
+ * i < 1024, sorted; splitter i = sample[(i + 1) * 4] for i < 255; a histogram of
+ * all magnitudes by upper_bound over the splitters (integer counts: exact in any
+ * order); the bucket of `rank` by upper_bound on the prefix sums; the threshold is
+ * splitter[bucket - 1], 0 for bucket 0.  Blocking.  The filter itself is
+ * gkomi_par_ilut_threshold_filter_f64_i32 with that threshold.  nnz == 0 gives 0;
+ * otherwise rank outside [0, nnz) is GKOMI_EINVAL.  Workspace
+ * gkomi_par_ilut_approx_workspace_bytes(). */
+size_t gkomi_par_ilut_approx_workspace_bytes(void);
+int gkomi_par_ilut_threshold_approx_f64(gkomi_stream_t s, int64_t nnz,
+                                        const double* vals, int64_t rank,
+                                        void* workspace, size_t workspace_bytes,
+                                        double* host_threshold);
+/* threshold_filter (:103-182): keeps an entry iff |v| >= threshold || col == row
+ * (a NaN compares false: it stays only on the diagonal), order kept.  Count call
+ * (new_col_idxs == new_vals == new_row_idxs == NULL): new_row_ptrs[n + 1] and
+ * *host_new_nnz, blocking.  Fill call with the new_row_ptrs and *host_new_nnz of
+ * the count call; new_row_idxs (may be NULL) receives the COO row index of every
+ * kept entry.  Workspace gkomi_par_ilut_filter_workspace_bytes(n), count call only. */
+size_t gkomi_par_ilut_filter_workspace_bytes(int64_t n);
+int gkomi_par_ilut_threshold_filter_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* row_ptrs,
+    const int32_t* col_idxs, const double* vals, double threshold,
+    int32_t* new_row_ptrs, int32_t* new_col_idxs, double* new_vals,
+    int32_t* new_row_idxs, int64_t* host_new_nnz, void* workspace,
+    size_t workspace_bytes);
+/* add_candidates (:355-464 over reference/components/csr_spgeam.hpp:58-104): the
+ * merge of row i of A and of LU (both sorted), one lane per row; the running match
+ * against old L without its diagonal, then against old U; a value is the existing
+ * one, or (a - lu) / u(col, col) below the diagonal, a - lu on and above it; L's
+ * diagonal is 1; u(col, col) is u_vals[u_row_ptrs[col]], the first entry of U's
+ * row.  Count call (the four new index / value arrays NULL): l_new_row_ptrs,
+ * u_new_row_ptrs (n + 1 each) and both totals, blocking; l_* / u_* are not read.
+ * Fill call with those.  Workspace gkomi_par_ilut_add_candidates_workspace_bytes(n),
+ * count call only. */
+size_t gkomi_par_ilut_add_candidates_workspace_bytes(int64_t n);
+int gkomi_par_ilut_add_candidates_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* lu_row_ptrs,
+    const int32_t* lu_col_idxs, const double* lu_vals,
+    const int32_t* a_row_ptrs, const int32_t* a_col_idxs, const double* a_vals,
+    const int32_t* l_row_ptrs, const int32_t* l_col_idxs, const double* l_vals,
+    const int32_t* u_row_ptrs, const int32_t* u_col_idxs, const double* u_vals,
+    int32_t* l_new_row_ptrs, int32_t* l_new_col_idxs, double* l_new_vals,
+    int32_t* u_new_row_ptrs, int32_t* u_new_col_idxs, double* u_new_vals,
+    int64_t* host_l_new_nnz, int64_t* host_u_new_nnz, void* workspace,
+    size_t workspace_bytes);
+/* compute_l_u_factors (:264-341).  The reference executor's sweep is sequential
+ * and in place: entry (row, col) reads only values rewritten earlier in the same
+ * sweep, so its result is determined by the pattern and reproduced here by a
+ * level schedule (row i after the rows k for which l(i, k) is stored), per entry
+ * the same products in ascending k, one rounding per product and per sum, one
+ * difference, one IEEE quotient; a value that is not finite leaves the old one.
+ *   analyse  once per pair of patterns (rows of L strictly ascending and ending
+ *            in their diagonal, rows of U strictly ascending and starting with
+ *            it; anything else is GKOMI_EINVAL and leaves the workspace
+ *            invalid): gkomi_ilu_analyse_i32 on the strictly lower part of L plus
+ *            U, whose row i is the working row of the sweep.  Blocking.
+ *            host_out[6] as there.
+ *   compute  on an analysed workspace, any number of times.  A sorted (rows
+ *            ascending).  ut_*: the CSC copy of U (CSR of U^T), all three or all
+ *            NULL; its values are brought up to date from u_vals after the sweep.
+ *            One launch per wide level and row-length bin, one single-workgroup
+ *            launch per run of narrow levels; no kernel waits on another
+ *            workgroup.  The running sums of a row too long for LDS live in a
+ *            scratch part of the workspace, which the analysis does not read:
+ *            one compute at a time per workspace.
+ * gkomi_par_ilut_tuning: host_out[4] = { longest working row a group of 8 lanes
+ * takes, longest a wave takes, longest a workgroup keeps in LDS, rows of the
+ * widest level that still counts as narrow } (unmeasured tuning constants). */
+size_t gkomi_par_ilut_sweep_workspace_bytes(int64_t n, int64_t l_nnz,
+                                            int64_t u_nnz);
+void gkomi_par_ilut_tuning(int64_t* host_out);
+int gkomi_par_ilut_analyse_i32(gkomi_stream_t s, int64_t n, int64_t l_nnz,
+                               const int32_t* l_row_ptrs,
+                               const int32_t* l_col_idxs, int64_t u_nnz,
+                               const int32_t* u_row_ptrs,
+                               const int32_t* u_col_idxs, void* workspace,
+                               size_t workspace_bytes, int64_t* host_out);
+int gkomi_par_ilut_compute_l_u_factors_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* a_row_ptrs,
+    const int32_t* a_col_idxs, const double* a_vals, int64_t l_nnz,
+    const int32_t* l_row_ptrs, const int32_t* l_col_idxs, double* l_vals,
+    int64_t u_nnz, const int32_t* u_row_ptrs, const int32_t* u_col_idxs,
+    double* u_vals, const int32_t* ut_row_ptrs, const int32_t* ut_col_idxs,
+    double* ut_vals, const void* analysis_workspace, size_t workspace_bytes);
 /* ---- sparse direct solver: symbolic Cholesky, Lu, solver::Direct -----------
  * experimental::factorization::Lu (core/factorization/lu.cpp:85-145),
  * symbolic_cholesky (core/factorization/symbolic.cpp:66-93), elimination_forest

@@ -22,7 +22,7 @@
 //
 // Scheduling.  No kernel here waits on another workgroup: no flags, no spins, no device-wide meetings.
 //   (a) a level of more than `narrow_level_rows` rows is one launch per row-length bin it holds rows of (the
-//       bins below: the group width follows the row), each a capped grid that strides over the level's list
+//       bins of fact_levels.hpp: the group width follows the row), each a capped grid that strides over the level's list
 //       of rows and takes the rows of its bin;
 //   (b) a run of consecutive levels of at most `narrow_level_rows` rows each is ONE launch of ONE
 //       workgroup that walks the levels with __syncthreads in between (a chain or thin band would
@@ -32,69 +32,15 @@
 
 #include <vector>
 
+#include "fact_levels.hpp"
 #include "internal.hpp"
 #include "sort_scan.hpp"
 
 namespace gkomi {
 namespace {
 
-constexpr int fact_block = 256;
-// row-length bins: a row of at most bin_short entries is factorized by 8 lanes, one of at most bin_wave
-// by a wave (both with an LDS image per group), one of at most bin_lds by a workgroup with the row in
-// LDS, anything longer by a workgroup on the row in memory
-constexpr int bin_short = 32;
-constexpr int short_width = 8;
-constexpr int bin_wave = 512;
-constexpr int bin_lds = 1024;
-// the boundary between (a) and (b): a level of at most this many rows is narrow (4 rows per wave of the
-// one workgroup that walks it)
-constexpr int narrow_level_rows = 16;
-constexpr int max_level_grid = 4096;
-
-constexpr int64_t ws_magic = 0x696c7530676b6f6dll;
-
-struct analysis_header {
-    int64_t magic;  // ws_magic once the analysis has succeeded
-    int64_t n, nnz, nlevels, nsegments, longest_row, widest_level, narrow_runs, launches;
-};
-static_assert(sizeof(analysis_header) <= 256, "the header has 256 bytes");
-
-// one launch of the numeric phase
-struct segment {
-    int32_t kind;      // 0: one wide level, 1: a run of narrow levels
-    int32_t first;     // wide: first position of the level; run: first level
-    int32_t last;      // wide: one past its last position;   run: one past the last level
-    int32_t longest;   // longest row inside
-    int32_t bins;      // wide: bit b set = the level holds a row of bin b (0 short, 1 wave, 2 workgroup)
-    int32_t pad_;
-};
-
-struct analysis_layout {
-    size_t diag, level, level_sorted, rows, perm, cnt, level_start, level_longest, level_bins, segments, flags, tmp, tmp_bytes, total;
-};
-
-analysis_layout make_layout(int64_t n)
-{
-    analysis_layout l{};
-    const size_t m = static_cast<size_t>(n > 0 ? n : 1);
-    const size_t vec = align256(sizeof(int32_t) * (m + 1));
-    size_t off = 256;
-    l.diag = off; off += vec;
-    l.level = off; off += vec;
-    l.level_sorted = off; off += vec;
-    l.rows = off; off += vec;
-    l.perm = off; off += vec;
-    l.cnt = off; off += vec;
-    l.level_start = off; off += vec;
-    l.level_longest = off; off += vec;
-    l.level_bins = off; off += align256(sizeof(int32_t) * 3 * (m + 1));
-    l.segments = off; off += align256(sizeof(segment) * (m + 1));
-    l.flags = off; off += 256;
-    l.tmp_bytes = align256(radix_sort_workspace_bytes(static_cast<int64_t>(m), sizeof(uint32_t), true)) + 256;
-    l.tmp = off; off += l.tmp_bytes;
-    l.total = off;
-    return l;
-}
+// the bins, the analysed workspace and the meetings are shared with the ParILUT sweep (fact_levels.hpp)
+using namespace fact;
 
 // diag[row] = position of the diagonal; flags[0] |= 1: a row without diagonal, |= 2: a row that is not
 // strictly ascending or leaves [0, n); flags[1] = longest row
@@ -119,8 +65,6 @@ __global__ __launch_bounds__(256) void fact_check_rows_kernel(int32_t n, const i
     atomicMax(flags + 1, end - begin);
 }
 
-__host__ __device__ __forceinline__ int bin_of(int len) { return len <= bin_short ? 0 : (len <= bin_wave ? 1 : 2); }
-
 // level_longest[l] = longest row of level l, level_bins[3 l + b] = its rows of bin b (both zeroed by the caller)
 __global__ __launch_bounds__(256) void fact_level_longest_kernel(int32_t n, const int32_t* __restrict__ row_ptrs,
                                                                 const int32_t* __restrict__ perm,
@@ -134,46 +78,6 @@ __global__ __launch_bounds__(256) void fact_level_longest_kernel(int32_t n, cons
     const int len = row_ptrs[row + 1] - row_ptrs[row];
     atomicMax(level_longest + level_sorted[p], len);
     atomicAdd(level_bins + 3 * level_sorted[p] + bin_of(len), 1);
-}
-
-// ---- how a group meets ------------------------------------------------------------------------------
-// lanes of one wave: LDS operations of a wave complete in program order; the fences keep the compiler from
-// moving an LDS access across the meeting point
-struct wave_meet {
-    __device__ __forceinline__ void operator()() const
-    {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-};
-struct block_meet {
-    __device__ __forceinline__ void operator()() const { __syncthreads(); }
-};
-
-// a value of a finished row.  Coherent (the narrow-level workgroup: the row was finished by another wave of
-// this launch): past the compute unit's vector cache, which may still hold the line from before.
-template <bool Coherent>
-__device__ __forceinline__ double finished(const double* p)
-{
-    if (Coherent) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
-}
-// the working row: an LDS image, or (InMemory) the row itself, shared by the waves of one workgroup
-template <bool InMemory>
-__device__ __forceinline__ double wld(const double* p)
-{
-    if (InMemory) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
-}
-template <bool InMemory>
-__device__ __forceinline__ void wst(double* p, double v)
-{
-    if (InMemory) {
-        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        *p = v;
-    }
 }
 
 // compute_lu of one row by a group of W lanes (t = my lane in the group).  w: the working row (len entries).

@@ -563,6 +563,175 @@ def par_ic_generate(gk, n, row_ptrs, col_idxs, vals, iterations=0, nrhs=1):
     return p
 
 
+# ---- ParILUT (core/factorization/par_ilut.cpp:190-344) -----------------------------------------------------
+
+def _bytes(nbytes, dv):
+    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dv)
+
+
+def _empty_csr(n, nnz, dv):
+    return torch.zeros(nnz, dtype=torch.int32, device=dv), torch.zeros(nnz, dtype=torch.float64, device=dv)
+
+
+def par_ilut_spgemm(gk, n, a, b):
+    """csr::spgemm of two n x n matrices (row_ptrs, col_idxs, vals)"""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = a[2].device
+    nb = gk.csr_spgemm_workspace_bytes(n, n)
+    ws = _bytes(nb, dv)
+    crp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    cnnz = ctypes.c_int64(0)
+
+    def call(cc, cv):
+        gk.csr_spgemm_f64_i32(s, n, n, int(a[2].numel()), a[0], a[1], a[2], n, n, int(b[2].numel()), b[0], b[1], b[2],
+                              None, None, 0, 0, 0, None, None, None, crp, cc, cv, ctypes.addressof(cnnz), ws, nb)
+    call(None, None)
+    cc, cv = _empty_csr(n, int(cnnz.value), dv)
+    if cnnz.value:
+        call(cc, cv)
+    return crp, cc, cv
+
+
+def par_ilut_add_candidates(gk, n, lu, a, l, u):
+    """par_ilut_factorization::add_candidates -> (L', U')"""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = a[2].device
+    nb = gk.par_ilut_add_candidates_workspace_bytes(n)
+    ws = _bytes(nb, dv)
+    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    urp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    lnnz, unnz = ctypes.c_int64(0), ctypes.c_int64(0)
+
+    def call(lc, lv, uc, uv):
+        gk.par_ilut_add_candidates_f64_i32(s, n, *lu, *a, *l, *u, lrp, lc, lv, urp, uc, uv, ctypes.addressof(lnnz),
+                                           ctypes.addressof(unnz), ws, nb)
+    call(None, None, None, None)
+    lc, lv = _empty_csr(n, int(lnnz.value), dv)
+    uc, uv = _empty_csr(n, int(unnz.value), dv)
+    if n:
+        call(lc, lv, uc, uv)
+    return (lrp, lc, lv), (urp, uc, uv)
+
+
+def par_ilut_threshold_select(gk, vals, rank):
+    """par_ilut_factorization::threshold_select: the magnitude of rank `rank` among vals"""
+    nnz = int(vals.numel())
+    nb = gk.par_ilut_select_workspace_bytes(nnz)
+    ws = _bytes(nb, vals.device)
+    out = ctypes.c_double(0.0)
+    gk.par_ilut_threshold_select_f64(torch.cuda.current_stream().cuda_stream, nnz, vals, rank, ws, nb, ctypes.addressof(out))
+    return out.value
+
+
+def par_ilut_threshold_approx(gk, vals, rank):
+    """the threshold of par_ilut_factorization::threshold_filter_approx"""
+    nnz = int(vals.numel())
+    nb = gk.par_ilut_approx_workspace_bytes()
+    ws = _bytes(nb, vals.device)
+    out = ctypes.c_double(0.0)
+    gk.par_ilut_threshold_approx_f64(torch.cuda.current_stream().cuda_stream, nnz, vals, rank, ws, nb, ctypes.addressof(out))
+    return out.value
+
+
+def par_ilut_threshold_filter(gk, n, m, threshold, with_coo=False):
+    """par_ilut_factorization::threshold_filter -> (row_ptrs, col_idxs, vals) [, COO row indices]"""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = m[2].device
+    nb = gk.par_ilut_filter_workspace_bytes(n)
+    ws = _bytes(nb, dv)
+    nrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    nnz = ctypes.c_int64(0)
+    gk.par_ilut_threshold_filter_f64_i32(s, n, *m, threshold, nrp, None, None, None, ctypes.addressof(nnz), ws, nb)
+    nc, nv = _empty_csr(n, int(nnz.value), dv)
+    rows = torch.zeros(int(nnz.value), dtype=torch.int32, device=dv) if with_coo else None
+    if nnz.value:
+        gk.par_ilut_threshold_filter_f64_i32(s, n, *m, threshold, nrp, nc, nv, rows, ctypes.addressof(nnz), ws, nb)
+    return ((nrp, nc, nv), rows) if with_coo else (nrp, nc, nv)
+
+
+class ParIlutSweep:
+    """gkomi_par_ilut_analyse_i32 of one pair of patterns (L', U'); .compute runs the exact sweep
+    (par_ilut_factorization::compute_l_u_factors with the reference executor's result) in place."""
+
+    def __init__(self, gk, n, l, u):
+        self.gk, self.n, self.l, self.u = gk, n, l, u
+        self.l_nnz, self.u_nnz = int(l[2].numel()), int(u[2].numel())
+        self.nbytes = gk.par_ilut_sweep_workspace_bytes(n, self.l_nnz, self.u_nnz)
+        self.ws = torch.zeros(max(self.nbytes, 8), dtype=torch.uint8, device=l[2].device)
+        out = (ctypes.c_int64 * 6)()
+        gk.par_ilut_analyse_i32(torch.cuda.current_stream().cuda_stream, n, self.l_nnz, l[0], l[1], self.u_nnz, u[0], u[1],
+                                self.ws, self.nbytes, ctypes.addressof(out))
+        self.nlevels, self.longest_row, self.widest_level, self.launches, self.narrow_runs, self.nnz = (int(x) for x in out)
+
+    def compute(self, a, u_csc=None):
+        """u_csc: the CSC copy of U, whose values are brought up to date"""
+        ut = u_csc if u_csc is not None else (None, None, None)
+        self.gk.par_ilut_compute_l_u_factors_f64_i32(torch.cuda.current_stream().cuda_stream, self.n, *a, self.l_nnz, *self.l,
+                                                     self.u_nnz, *self.u, *ut, self.ws, self.nbytes)
+
+
+def par_ilut_generate(gk, n, row_ptrs, col_idxs, vals, iterations=5, fill_in_limit=2.0, approximate_select=True,
+                      skip_sorting=False, nrhs=1, ncols=None):
+    """preconditioner::Ilu over factorization::ParIlut (core/factorization/par_ilut.cpp:190-344), with the factors of the
+    reference executor bit for bit: sort, initialize_l_u, then per iteration spgemm, add_candidates, transpose, sweep,
+    threshold selection and filters, sweep.  Returns the Preconditioner; .L / .U hold the factors, .levels the number of
+    dependency levels of every sweep.
+    The CSC copy of U' exists only where its order matters: the approximate selection samples it.  The exact
+    selection does not depend on the order of the values, and the second sweep reads U by rows."""
+    # GKO_ASSERT_IS_SQUARE_MATRIX and the fill_in_limit check, before anything reaches the device
+    if ncols is not None and ncols != n:
+        raise ValueError(f"ParIlut needs a square matrix, got {n} x {ncols}")
+    if int(row_ptrs.numel()) != n + 1:
+        raise ValueError(f"ParIlut needs a square matrix: {int(row_ptrs.numel()) - 1} rows of row pointers for n = {n}")
+    if not fill_in_limit > 0.0:
+        raise ValueError(f"fill_in_limit must be positive, got {fill_in_limit}")
+    s = torch.cuda.current_stream().cuda_stream
+    dv = vals.device
+    ci, v = col_idxs.clone(), vals.clone()
+    if not skip_sorting:
+        sorted_flag = ctypes.c_int(0)
+        fws = torch.zeros(8, dtype=torch.uint8, device=dv)
+        gk.csr_is_sorted_by_column_index_i32(s, n, row_ptrs, ci, fws, 8, ctypes.addressof(sorted_flag))
+        if not sorted_flag.value:
+            gk.csr_sort_by_column_index_f64_i32(s, n, row_ptrs, ci, v)
+    a = (row_ptrs, ci, v)
+    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    urp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    sb = gk.prefix_sum_workspace_bytes(n + 1)
+    sws = _bytes(sb, dv)
+    gk.factorization_initialize_row_ptrs_l_u_i32(s, n, row_ptrs, ci, lrp, urp, sws, sb)
+    lnnz, unnz = int(lrp[n].item()), int(urp[n].item())
+    lc, lv = _empty_csr(n, lnnz, dv)
+    uc, uv = _empty_csr(n, unnz, dv)
+    gk.factorization_initialize_l_u_f64_i32(s, n, row_ptrs, ci, v, lrp, lc, lv, urp, uc, uv)
+    l, u = (lrp, lc, lv), (urp, uc, uv)
+    l_nnz_limit, u_nnz_limit = int(lnnz * fill_in_limit), int(unnz * fill_in_limit)
+    levels = []
+    for _ in range(iterations):
+        lu = par_ilut_spgemm(gk, n, l, u)
+        l_new, u_new = par_ilut_add_candidates(gk, n, lu, a, l, u)
+        u_new_csc = _transpose(gk, n, *u_new) if approximate_select else None
+        sweep = ParIlutSweep(gk, n, l_new, u_new)
+        sweep.compute(a, u_new_csc)
+        levels.append(sweep.nlevels)
+        l_rank = max(0, int(l_new[2].numel()) - l_nnz_limit - 1)
+        u_rank = max(0, int(u_new[2].numel()) - u_nnz_limit - 1)
+        if approximate_select:
+            l_threshold = par_ilut_threshold_approx(gk, l_new[2], l_rank)
+            u_threshold = par_ilut_threshold_approx(gk, u_new_csc[2], u_rank)
+        else:
+            l_threshold = par_ilut_threshold_select(gk, l_new[2], l_rank)
+            u_threshold = par_ilut_threshold_select(gk, u_new[2], u_rank)
+        l = par_ilut_threshold_filter(gk, n, l_new, l_threshold)
+        u = par_ilut_threshold_filter(gk, n, u_new, u_threshold)
+        sweep = ParIlutSweep(gk, n, l, u)
+        sweep.compute(a)
+        levels.append(sweep.nlevels)
+    p = ilu_from_factors(gk, n, l, u, nrhs=nrhs)
+    p.L, p.U, p.levels = l, u, levels
+    return p
+
+
 class FactorizationAnalysis:
     """gkomi_ilu_analyse_i32: diagonal positions, dependency levels and the launch list of the exact ILU(0) / IC(0)
     of one sparsity pattern (sorted rows, diagonal stored); reusable for any number of numeric calls."""

@@ -12,7 +12,7 @@
 //   gko::matrix::{Dense, Csr, Coo, Ell, Sellp, Hybrid},
 //   gko::stop::{Iteration, ResidualNorm, Combined},
 //   gko::solver::{Cg, Gmres, LowerTrs, UpperTrs},
-//   gko::preconditioner::{Jacobi, Ilu}, gko::factorization::ParIlu,
+//   gko::preconditioner::{Jacobi, Ilu}, gko::factorization::{ParIlu, ParIlut},
 //   gko::read / gko::write (MatrixMarket), gko::initialize, gko::share, lend.
 //
 // Kernels exist only for HipExecutor (the MI355X backend).  The host executors
@@ -1313,6 +1313,9 @@ private:
 };
 
 template <typename V = double, typename I = int32>
+class CooBuilder;
+
+template <typename V = double, typename I = int32>
 class Coo : public LinOp {
 public:
     static std::unique_ptr<Coo> create(std::shared_ptr<const Executor> exec, const dim<2>& size = dim<2>{}, size_type nnz = 0) { return std::unique_ptr<Coo>(new Coo(std::move(exec), size, nnz)); }
@@ -1388,6 +1391,23 @@ protected:
     mutable int sorted_state_{-1};   // -1 unknown, 0 not sorted, 1 sorted
     mutable int64_t max_row_nnz_{-1};
     mutable array<char> sorted_ws_;
+    friend class CooBuilder<V, I>;
+};
+
+// core/matrix/coo_builder.hpp:47-86: intrusive access to a Coo's arrays for kernels that rebuild them
+// (par_ilut_factorization::threshold_filter); what is known about the order of the rows is forgotten
+template <typename V, typename I>
+class CooBuilder {
+public:
+    array<I>& get_row_idx_array() { return matrix_->row_idxs_; }
+    array<I>& get_col_idx_array() { return matrix_->col_idxs_; }
+    array<V>& get_value_array() { return matrix_->values_; }
+    explicit CooBuilder(Coo<V, I>* matrix) : matrix_{matrix} {}
+    ~CooBuilder() { matrix_->sorted_state_ = -1; }
+    CooBuilder(const CooBuilder&) = delete;
+    CooBuilder& operator=(const CooBuilder&) = delete;
+private:
+    Coo<V, I>* matrix_;
 };
 
 template <typename V = double, typename I = int32>
@@ -3020,6 +3040,153 @@ protected:
     }
     std::shared_ptr<matrix_type> l_, lt_;
 };
+
+// ---- ParIlut, the threshold ILU (core/factorization/par_ilut.cpp:190-344) -------------------------------------
+// The factors are the reference executor's, bit for bit: its sweep is sequential and in place, so its result
+// is determined by the pattern, and the device reproduces it with a level schedule (csrc/par_ilut.hip).
+template <typename V = double, typename I = int32>
+class ParIlut {
+public:
+    using matrix_type = matrix::Csr<V, I>;
+    class Factory {
+    public:
+        Factory& with_iterations(size_type n) { iterations_ = n; return *this; }
+        Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
+        Factory& with_approximate_select(bool approximate) { approximate_select_ = approximate; return *this; }
+        // the reference executor's sample is deterministic either way; so is this one
+        Factory& with_deterministic_sample(bool deterministic) { deterministic_sample_ = deterministic; return *this; }
+        Factory& with_fill_in_limit(double limit) { fill_in_limit_ = limit; return *this; }
+        Factory& with_l_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { l_strategy_ = std::move(s); return *this; }
+        Factory& with_u_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { u_strategy_ = std::move(s); return *this; }
+        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
+        std::unique_ptr<ParIlut> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<ParIlut>(new ParIlut(*this, std::move(A))); }
+        std::shared_ptr<const Executor> exec_;
+        size_type iterations_{5};
+        bool skip_sorting_{false}, approximate_select_{true}, deterministic_sample_{false};
+        double fill_in_limit_{2.0};
+        std::shared_ptr<typename matrix_type::strategy_type> l_strategy_, u_strategy_;
+    };
+    static Factory build() { return Factory{}; }
+    std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
+    std::shared_ptr<const matrix_type> get_u_factor() const { return u_; }
+protected:
+    struct factor {
+        array<I> rp, ci;
+        array<V> v;
+        int64_t nnz() const { return static_cast<int64_t>(v.get_num_elems()); }
+    };
+    static factor filtered(const std::shared_ptr<const Executor>& exec, size_type n, const factor& m, double threshold)
+    {
+        factor out{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
+        array<char> ws(exec, gkomi_par_ilut_filter_workspace_bytes(n));
+        int64_t nnz = 0;
+        GKOMI_CALL(gkomi_par_ilut_threshold_filter_f64_i32(nullptr, n, m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), threshold, out.rp.get_data(), nullptr, nullptr, nullptr, &nnz,
+                                                           ws.get_data(), ws.get_num_elems()));
+        out.ci = array<I>(exec, nnz);
+        out.v = array<V>(exec, nnz);
+        GKOMI_CALL(gkomi_par_ilut_threshold_filter_f64_i32(nullptr, n, m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), threshold, out.rp.get_data(), out.ci.get_data(), out.v.get_data(), nullptr,
+                                                           &nnz, ws.get_data(), ws.get_num_elems()));
+        return out;
+    }
+    // compute_l_u_factors in place; ut: the CSC copy of u whose values are brought up to date, or nullptr
+    static void sweep(const std::shared_ptr<const Executor>& exec, size_type n, const matrix_type* a, factor& l, factor& u, factor* ut)
+    {
+        array<char> ws(exec, gkomi_par_ilut_sweep_workspace_bytes(n, l.nnz(), u.nnz()));
+        int64_t info[6] = {};
+        GKOMI_CALL(gkomi_par_ilut_analyse_i32(nullptr, n, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), u.nnz(), u.rp.get_const_data(), u.ci.get_const_data(), ws.get_data(), ws.get_num_elems(), info));
+        GKOMI_CALL(gkomi_par_ilut_compute_l_u_factors_f64_i32(nullptr, n, a->get_const_row_ptrs(), a->get_const_col_idxs(), a->get_const_values(), l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(),
+                                                              l.v.get_data(), u.nnz(), u.rp.get_const_data(), u.ci.get_const_data(), u.v.get_data(), ut ? ut->rp.get_const_data() : nullptr,
+                                                              ut ? ut->ci.get_const_data() : nullptr, ut ? ut->v.get_data() : nullptr, ws.get_const_data(), ws.get_num_elems()));
+        exec->synchronize();  // the workspace leaves scope
+    }
+    ParIlut(const Factory& f, std::shared_ptr<const LinOp> A)
+    {
+        static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "ParIlut is <double, int32>");
+        const auto& exec = f.exec_;
+        detail::require_device(exec, "par_ilut_factorization");
+        auto src = as<const matrix_type>(A.get());
+        const size_type n = src->get_size()[0];
+        if (n != src->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, "ParIlut needs a square matrix");
+        // GKO_ASSERT_EQ(parameters_.fill_in_limit > 0.0, true)
+        if (!(f.fill_in_limit_ > 0.0)) throw ValueMismatch(__FILE__, __LINE__, "ParIlut needs fill_in_limit > 0");
+        std::unique_ptr<matrix_type> sorted;
+        if (!f.skip_sorting_ && !src->is_sorted_by_column_index()) {
+            matrix_data<V, I> d;
+            src->write(d);
+            sorted = matrix_type::create(exec);
+            sorted->read(d);
+            sorted->sort_by_column_index();
+            src = sorted.get();
+        }
+        factor l{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)}, u{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
+        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
+        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_u_i32(nullptr, n, src->get_const_row_ptrs(), src->get_const_col_idxs(), l.rp.get_data(), u.rp.get_data(), sws.get_data(), sws.get_num_elems()));
+        const size_type lnnz = exec->copy_val_to_host(l.rp.get_const_data() + n), unnz = exec->copy_val_to_host(u.rp.get_const_data() + n);
+        l.ci = array<I>(exec, lnnz); l.v = array<V>(exec, lnnz);
+        u.ci = array<I>(exec, unnz); u.v = array<V>(exec, unnz);
+        GKOMI_CALL(gkomi_factorization_initialize_l_u_f64_i32(nullptr, n, src->get_const_row_ptrs(), src->get_const_col_idxs(), src->get_const_values(), l.rp.get_const_data(), l.ci.get_data(), l.v.get_data(),
+                                                              u.rp.get_const_data(), u.ci.get_data(), u.v.get_data()));
+        const int64_t l_nnz_limit = static_cast<I>(lnnz * f.fill_in_limit_), u_nnz_limit = static_cast<I>(unnz * f.fill_in_limit_);
+        array<char> gws(exec, gkomi_csr_spgemm_workspace_bytes(n, n)), cws(exec, gkomi_par_ilut_add_candidates_workspace_bytes(n));
+        array<char> tws(exec, gkomi_csr_transpose_workspace_bytes(n));
+        for (size_type it = 0; it < f.iterations_; ++it) {
+            // L U
+            factor lu{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
+            int64_t lu_nnz = 0;
+            auto spgemm = [&] {
+                GKOMI_CALL(gkomi_csr_spgemm_f64_i32(nullptr, n, n, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_const_data(), n, n, u.nnz(), u.rp.get_const_data(), u.ci.get_const_data(),
+                                                    u.v.get_const_data(), nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, lu.rp.get_data(), lu.ci.get_num_elems() ? lu.ci.get_data() : nullptr,
+                                                    lu.v.get_num_elems() ? lu.v.get_data() : nullptr, &lu_nnz, gws.get_data(), gws.get_num_elems()));
+            };
+            spgemm();
+            lu.ci = array<I>(exec, lu_nnz);
+            lu.v = array<V>(exec, lu_nnz);
+            if (lu_nnz > 0) spgemm();
+            // the candidates L', U'
+            factor l_new{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)}, u_new{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
+            int64_t l_new_nnz = 0, u_new_nnz = 0;
+            auto add_candidates = [&](bool fill) {
+                GKOMI_CALL(gkomi_par_ilut_add_candidates_f64_i32(
+                    nullptr, n, lu.rp.get_const_data(), lu.ci.get_const_data(), lu.v.get_const_data(), src->get_const_row_ptrs(), src->get_const_col_idxs(), src->get_const_values(), l.rp.get_const_data(),
+                    l.ci.get_const_data(), l.v.get_const_data(), u.rp.get_const_data(), u.ci.get_const_data(), u.v.get_const_data(), l_new.rp.get_data(), fill ? l_new.ci.get_data() : nullptr,
+                    fill ? l_new.v.get_data() : nullptr, u_new.rp.get_data(), fill ? u_new.ci.get_data() : nullptr, fill ? u_new.v.get_data() : nullptr, &l_new_nnz, &u_new_nnz, cws.get_data(), cws.get_num_elems()));
+            };
+            add_candidates(false);
+            l_new.ci = array<I>(exec, l_new_nnz); l_new.v = array<V>(exec, l_new_nnz);
+            u_new.ci = array<I>(exec, u_new_nnz); u_new.v = array<V>(exec, u_new_nnz);
+            if (n > 0) add_candidates(true);
+            // U' by columns only where the order of its values matters: the approximate selection samples it
+            factor u_new_csc{array<I>(exec), array<I>(exec), array<V>(exec)};
+            if (f.approximate_select_) {
+                u_new_csc = factor{array<I>(exec, n + 1), array<I>(exec, u_new_nnz), array<V>(exec, u_new_nnz)};
+                GKOMI_CALL(gkomi_csr_transpose_f64_i32(nullptr, n, n, u_new_nnz, u_new.rp.get_const_data(), u_new.ci.get_const_data(), u_new.v.get_const_data(), u_new_csc.rp.get_data(), u_new_csc.ci.get_data(),
+                                                       u_new_csc.v.get_data(), tws.get_data(), tws.get_num_elems()));
+            }
+            sweep(exec, n, src, l_new, u_new, f.approximate_select_ ? &u_new_csc : nullptr);
+            const int64_t l_rank = std::max<int64_t>(0, l_new_nnz - l_nnz_limit - 1), u_rank = std::max<int64_t>(0, u_new_nnz - u_nnz_limit - 1);
+            double l_threshold = 0.0, u_threshold = 0.0;
+            if (n > 0 && f.approximate_select_) {
+                array<char> ws(exec, gkomi_par_ilut_approx_workspace_bytes());
+                GKOMI_CALL(gkomi_par_ilut_threshold_approx_f64(nullptr, l_new_nnz, l_new.v.get_const_data(), l_rank, ws.get_data(), ws.get_num_elems(), &l_threshold));
+                GKOMI_CALL(gkomi_par_ilut_threshold_approx_f64(nullptr, u_new_nnz, u_new_csc.v.get_const_data(), u_rank, ws.get_data(), ws.get_num_elems(), &u_threshold));
+            } else if (n > 0) {
+                array<char> ws(exec, gkomi_par_ilut_select_workspace_bytes(std::max(l_new_nnz, u_new_nnz)));
+                GKOMI_CALL(gkomi_par_ilut_threshold_select_f64(nullptr, l_new_nnz, l_new.v.get_const_data(), l_rank, ws.get_data(), ws.get_num_elems(), &l_threshold));
+                GKOMI_CALL(gkomi_par_ilut_threshold_select_f64(nullptr, u_new_nnz, u_new.v.get_const_data(), u_rank, ws.get_data(), ws.get_num_elems(), &u_threshold));
+            }
+            l = filtered(exec, n, l_new, l_threshold);
+            u = filtered(exec, n, u_new, u_threshold);
+            sweep(exec, n, src, l, u, nullptr);
+        }
+        auto lm = matrix_type::create(exec); auto um = matrix_type::create(exec);
+        lm->adopt(dim<2>(n, n), std::move(l.rp), std::move(l.ci), std::move(l.v));
+        um->adopt(dim<2>(n, n), std::move(u.rp), std::move(u.ci), std::move(u.v));
+        if (f.l_strategy_) lm->set_strategy(f.l_strategy_);
+        if (f.u_strategy_) um->set_strategy(f.u_strategy_);
+        l_ = std::move(lm); u_ = std::move(um);
+    }
+    std::shared_ptr<matrix_type> l_, u_;
+};
 }  // namespace factorization
 
 
@@ -3075,14 +3242,18 @@ public:
         std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
         // the exact ILU(0) instead of the default ParIlu sweeps
         Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::Ilu<V, I>::Factory> f) { exact_ = std::move(f); return *this; }
+        // the threshold ILU
+        Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::ParIlut<V, I>::Factory> f) { ilut_ = std::move(f); return *this; }
         std::unique_ptr<Ilu> generate(std::shared_ptr<const LinOp> A) const
         {
+            if (ilut_) return std::unique_ptr<Ilu>(new Ilu(this->exec_, *ilut_, std::move(A)));
             if (exact_) return std::unique_ptr<Ilu>(new Ilu(this->exec_, *exact_, std::move(A)));
             return std::unique_ptr<Ilu>(new Ilu(this->exec_, iterations_, std::move(A)));
         }
         std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
         size_type iterations_{0};
         std::shared_ptr<const typename ::gko::factorization::Ilu<V, I>::Factory> exact_;
+        std::shared_ptr<const typename ::gko::factorization::ParIlut<V, I>::Factory> ilut_;
     };
     static Factory build() { return Factory{}; }
     std::shared_ptr<const LinOp> get_l_solver() const { return l_solver_; }
@@ -3108,7 +3279,9 @@ protected:
         l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(l_factor_);
         u_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(u_factor_);
     }
-    Ilu(std::shared_ptr<const Executor> exec, const typename ::gko::factorization::Ilu<V, I>::Factory& exact, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
+    // a factorization factory that gives get_l_factor() / get_u_factor(): factorization::Ilu or factorization::ParIlut
+    template <class FactorizationFactory>
+    Ilu(std::shared_ptr<const Executor> exec, const FactorizationFactory& exact, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
     {
         auto fact = (exact.exec_ ? exact : *exact.on(exec)).generate(std::move(A));
         l_factor_ = fact->get_l_factor();
