@@ -1176,6 +1176,62 @@ int gkomi_par_ilut_compute_l_u_factors_f64_i32(
     int64_t u_nnz, const int32_t* u_row_ptrs, const int32_t* u_col_idxs,
     double* u_vals, const int32_t* ut_row_ptrs, const int32_t* ut_col_idxs,
     double* ut_vals, const void* analysis_workspace, size_t workspace_bytes);
+/* ---- ParICT: factorization::ParIct (core/factorization/par_ict.cpp:174-292)
+ * The two kernels of core/factorization/par_ict_kernels.hpp with the results of
+ * the REFERENCE executor (reference/factorization/par_ict_kernels.cpp), bit for
+ * bit; <double, int32>.  Threshold selection and filter are the
+ * gkomi_par_ilut_threshold_* entries above (the reference executor's filter keeps
+ * |v| >= t || col == row whatever its `lower` flag says).  Conventions as there:
+ * the caller owns every allocation, a matrix is produced by a count call and a
+ * fill call, and every entry rejects bad arguments before any HIP call.
+ *
+ * add_candidates (:127-199 over reference/components/csr_spgeam.hpp:58-104): the
+ * merge of row i of A and of L L^T (both sorted), one lane per row, entries with
+ * col <= row only; the running match against old L; a value is the existing
+ * l(row, col), or (a - llh) / l(col, col) with l(col, col) the last entry of row
+ * col of L.  Count call (l_new_col_idxs == l_new_vals == NULL): l_new_row_ptrs
+ * (n + 1) and *host_l_new_nnz, blocking; l_col_idxs / l_vals are not read.  Fill
+ * call with those.  Workspace gkomi_par_ict_add_candidates_workspace_bytes(n),
+ * count call only. */
+size_t gkomi_par_ict_add_candidates_workspace_bytes(int64_t n);
+int gkomi_par_ict_add_candidates_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* llh_row_ptrs,
+    const int32_t* llh_col_idxs, const double* llh_vals,
+    const int32_t* a_row_ptrs, const int32_t* a_col_idxs, const double* a_vals,
+    const int32_t* l_row_ptrs, const int32_t* l_col_idxs, const double* l_vals,
+    int32_t* l_new_row_ptrs, int32_t* l_new_col_idxs, double* l_new_vals,
+    int64_t* host_l_new_nnz, void* workspace, size_t workspace_bytes);
+/* compute_factor (:65-121).  The reference executor's sweep is sequential and in
+ * place: entry (row, col) reads l(row, k), l(col, k) for k < col and l(col, col),
+ * all rewritten earlier in the same sweep, so its result is determined by the
+ * pattern and reproduced here by a level schedule (row i after the rows k for
+ * which l(i, k) is stored): per entry a sum from +0.0 of the same products in
+ * ascending k, one rounding per product and per sum, one difference a - sum
+ * (a = 0.0 where A does not store the entry), one IEEE square root on the
+ * diagonal or one IEEE quotient by l(col, col); a value that is not finite leaves
+ * the old one, which is what later entries read.
+ *   analyse  once per pattern of L (rows strictly ascending and ending in their
+ *            diagonal; anything else is GKOMI_EINVAL and leaves the workspace
+ *            invalid): gkomi_ilu_analyse_i32 on that pattern.  Blocking.
+ *            host_out[6] as there.
+ *   compute  on an analysed workspace, any number of times.  A sorted (rows
+ *            ascending).  One launch per wide level and row-length bin, one
+ *            single-workgroup launch per run of narrow levels; no kernel waits on
+ *            another workgroup.  A row too long for LDS works on l_vals itself.
+ * gkomi_par_ict_tuning: host_out[4] = { longest row a group of 8 lanes takes,
+ * longest a wave takes, longest a workgroup keeps in LDS, rows of the widest
+ * level that still counts as narrow } (unmeasured tuning constants). */
+size_t gkomi_par_ict_sweep_workspace_bytes(int64_t n, int64_t l_nnz);
+void gkomi_par_ict_tuning(int64_t* host_out);
+int gkomi_par_ict_analyse_i32(gkomi_stream_t s, int64_t n, int64_t l_nnz,
+                              const int32_t* l_row_ptrs,
+                              const int32_t* l_col_idxs, void* workspace,
+                              size_t workspace_bytes, int64_t* host_out);
+int gkomi_par_ict_compute_factor_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* a_row_ptrs,
+    const int32_t* a_col_idxs, const double* a_vals, int64_t l_nnz,
+    const int32_t* l_row_ptrs, const int32_t* l_col_idxs, double* l_vals,
+    const void* analysis_workspace, size_t workspace_bytes);
 /* ---- sparse direct solver: symbolic Cholesky, Lu, solver::Direct -----------
  * experimental::factorization::Lu (core/factorization/lu.cpp:85-145),
  * symbolic_cholesky (core/factorization/symbolic.cpp:66-93), elimination_forest

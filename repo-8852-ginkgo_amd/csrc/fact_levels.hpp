@@ -1,6 +1,6 @@
-// What the level-scheduled factorizations share (ilu.hip: exact ILU(0) / IC(0); par_ilut.hip: the ParILUT
-// sweep): the analysed workspace of gkomi_ilu_analyse_i32, the row-length bins and the ways a group of lanes
-// meets.  Internal to the library.
+// What the level-scheduled factorizations share (ilu.hip: exact ILU(0) / IC(0); par_ilut.hip, par_ict.hip: the
+// ParILUT and ParICT sweeps): the analysed workspace of gkomi_ilu_analyse_i32, the row-length bins and the ways
+// a group of lanes meets; and what the two add_candidates merges share.  Internal to the library.
 #pragma once
 #include "common.hpp"
 
@@ -68,6 +68,32 @@ inline analysis_layout make_layout(int64_t n)
 }
 
 __host__ __device__ __forceinline__ int bin_of(int len) { return len <= bin_short ? 0 : (len <= bin_wave ? 1 : 2); }
+
+// ---- the matrices of a merge kernel (add_candidates), and the end of its count call ----------------------
+struct csr_in {
+    const int32_t* row_ptrs;
+    const int32_t* col_idxs;
+    const double* vals;
+};
+struct csr_out {
+    int32_t* row_ptrs;
+    int32_t* col_idxs;
+    double* vals;
+};
+
+// counts in ptrs[0, n) -> row pointers in ptrs[0, n], the total to the host
+inline int finish_row_ptrs(hipStream_t stream, int64_t n, int32_t* ptrs, void* scan_ws, size_t scan_bytes, int64_t* host_total)
+{
+    GKOMI_TRY(static_cast<int>(hipMemsetAsync(ptrs + n, 0, sizeof(int32_t), stream)));
+    GKOMI_TRY(exclusive_sum_i32(stream, ptrs, ptrs, n + 1, scan_ws, scan_bytes));
+    int32_t total = 0;
+    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&total, ptrs + n, sizeof(total), hipMemcpyDeviceToHost, stream)));
+    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+    *host_total = total;
+    return GKOMI_SUCCESS;
+}
+
+inline size_t row_scan_bytes(int64_t n) { return align256(scan_workspace_bytes((n > 0 ? n : 1) + 1)) + 256; }
 
 #ifdef __HIPCC__
 // ---- how a group meets ------------------------------------------------------------------------------

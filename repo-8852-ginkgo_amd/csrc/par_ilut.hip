@@ -191,17 +191,6 @@ constexpr size_t approx_total = approx_histogram + 4 * bucket_count;
 static_assert(approx_histogram % 256 == 0 && approx_total % 256 == 0, "workspace pieces start on 256-byte boundaries");
 
 // ---- add_candidates (:355-464): the merge of row i of A and of LU, one lane per row ---------------------
-struct csr_in {
-    const int32_t* row_ptrs;
-    const int32_t* col_idxs;
-    const double* vals;
-};
-struct csr_out {
-    int32_t* row_ptrs;
-    int32_t* col_idxs;
-    double* vals;
-};
-
 template <bool Fill>
 __global__ __launch_bounds__(block) void add_candidates_kernel(int32_t n, csr_in lu, csr_in a, csr_in l, csr_in u,
                                                                csr_out l_new, csr_out u_new)
@@ -275,20 +264,6 @@ __global__ __launch_bounds__(block) void add_candidates_kernel(int32_t n, csr_in
         }
     }
 }
-
-// counts in ptrs[0, n) -> row pointers in ptrs[0, n], the total to the host
-int finish_row_ptrs(hipStream_t stream, int64_t n, int32_t* ptrs, void* scan_ws, size_t scan_bytes, int64_t* host_total)
-{
-    GKOMI_TRY(static_cast<int>(hipMemsetAsync(ptrs + n, 0, sizeof(int32_t), stream)));
-    GKOMI_TRY(exclusive_sum_i32(stream, ptrs, ptrs, n + 1, scan_ws, scan_bytes));
-    int32_t total = 0;
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&total, ptrs + n, sizeof(total), hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-    *host_total = total;
-    return GKOMI_SUCCESS;
-}
-
-size_t row_scan_bytes(int64_t n) { return align256(scan_workspace_bytes((n > 0 ? n : 1) + 1)) + 256; }
 
 // ---- compute_l_u_factors ---------------------------------------------------------------------------------
 struct sweep_header {

@@ -732,6 +732,97 @@ def par_ilut_generate(gk, n, row_ptrs, col_idxs, vals, iterations=5, fill_in_lim
     return p
 
 
+# ---- ParICT (core/factorization/par_ict.cpp:174-292) --------------------------------------------------------
+
+def par_ict_add_candidates(gk, n, llh, a, l):
+    """par_ict_factorization::add_candidates -> L'"""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = a[2].device
+    nb = gk.par_ict_add_candidates_workspace_bytes(n)
+    ws = _bytes(nb, dv)
+    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    lnnz = ctypes.c_int64(0)
+    gk.par_ict_add_candidates_f64_i32(s, n, *llh, *a, *l, lrp, None, None, ctypes.addressof(lnnz), ws, nb)
+    lc, lv = _empty_csr(n, int(lnnz.value), dv)
+    if n:
+        gk.par_ict_add_candidates_f64_i32(s, n, *llh, *a, *l, lrp, lc, lv, ctypes.addressof(lnnz), ws, nb)
+    return lrp, lc, lv
+
+
+class ParIctSweep:
+    """gkomi_par_ict_analyse_i32 of one pattern L'; .compute runs the exact sweep
+    (par_ict_factorization::compute_factor with the reference executor's result) in place."""
+
+    def __init__(self, gk, n, l):
+        self.gk, self.n, self.l = gk, n, l
+        self.l_nnz = int(l[2].numel())
+        self.nbytes = gk.par_ict_sweep_workspace_bytes(n, self.l_nnz)
+        self.ws = torch.zeros(max(self.nbytes, 8), dtype=torch.uint8, device=l[2].device)
+        out = (ctypes.c_int64 * 6)()
+        gk.par_ict_analyse_i32(torch.cuda.current_stream().cuda_stream, n, self.l_nnz, l[0], l[1], self.ws, self.nbytes,
+                               ctypes.addressof(out))
+        self.nlevels, self.longest_row, self.widest_level, self.launches, self.narrow_runs, self.nnz = (int(x) for x in out)
+
+    def compute(self, a):
+        self.gk.par_ict_compute_factor_f64_i32(torch.cuda.current_stream().cuda_stream, self.n, *a, self.l_nnz, *self.l,
+                                               self.ws, self.nbytes)
+
+
+def par_ict_generate(gk, n, row_ptrs, col_idxs, vals, iterations=5, fill_in_limit=2.0, approximate_select=True,
+                     skip_sorting=False, nrhs=1, ncols=None):
+    """preconditioner::Ic over factorization::ParIct (core/factorization/par_ict.cpp:174-292), with the factor of the
+    reference executor bit for bit: sort, initialize_l with the root of the diagonal, then per iteration spgemm(L, L^T),
+    add_candidates, sweep, threshold selection on L' in CSR order and filter, sweep, transpose.  Returns the
+    Preconditioner (L^-1 then L^-T); .L / .Lt hold the factors, .levels the number of dependency levels of every sweep."""
+    # GKO_ASSERT_IS_SQUARE_MATRIX and the fill_in_limit check, before anything reaches the device
+    if ncols is not None and ncols != n:
+        raise ValueError(f"ParIct needs a square matrix, got {n} x {ncols}")
+    if int(row_ptrs.numel()) != n + 1:
+        raise ValueError(f"ParIct needs a square matrix: {int(row_ptrs.numel()) - 1} rows of row pointers for n = {n}")
+    if not fill_in_limit > 0.0:
+        raise ValueError(f"fill_in_limit must be positive, got {fill_in_limit}")
+    s = torch.cuda.current_stream().cuda_stream
+    dv = vals.device
+    ci, v = col_idxs.clone(), vals.clone()
+    if not skip_sorting:
+        sorted_flag = ctypes.c_int(0)
+        fws = torch.zeros(8, dtype=torch.uint8, device=dv)
+        gk.csr_is_sorted_by_column_index_i32(s, n, row_ptrs, ci, fws, 8, ctypes.addressof(sorted_flag))
+        if not sorted_flag.value:
+            gk.csr_sort_by_column_index_f64_i32(s, n, row_ptrs, ci, v)
+    a = (row_ptrs, ci, v)
+    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    sb = gk.prefix_sum_workspace_bytes(n + 1)
+    sws = _bytes(sb, dv)
+    gk.factorization_initialize_row_ptrs_l_i32(s, n, row_ptrs, ci, lrp, sws, sb)
+    lnnz = int(lrp[n].item())
+    lc, lv = _empty_csr(n, lnnz, dv)
+    gk.factorization_initialize_l_f64_i32(s, n, row_ptrs, ci, v, lrp, lc, lv, 1)
+    l = (lrp, lc, lv)
+    lt = _transpose(gk, n, *l)
+    l_nnz_limit = int(lnnz * fill_in_limit)
+    levels = []
+    for _ in range(iterations):
+        llh = par_ilut_spgemm(gk, n, l, lt)
+        l_new = par_ict_add_candidates(gk, n, llh, a, l)
+        sweep = ParIctSweep(gk, n, l_new)
+        sweep.compute(a)
+        levels.append(sweep.nlevels)
+        rank = max(0, int(l_new[2].numel()) - l_nnz_limit - 1)
+        if approximate_select:
+            threshold = par_ilut_threshold_approx(gk, l_new[2], rank)
+        else:
+            threshold = par_ilut_threshold_select(gk, l_new[2], rank)
+        l = par_ilut_threshold_filter(gk, n, l_new, threshold)
+        sweep = ParIctSweep(gk, n, l)
+        sweep.compute(a)
+        levels.append(sweep.nlevels)
+        lt = _transpose(gk, n, *l)
+    p = ilu_from_factors(gk, n, l, lt, nrhs=nrhs)
+    p.L, p.Lt, p.levels = l, lt, levels
+    return p
+
+
 class FactorizationAnalysis:
     """gkomi_ilu_analyse_i32: diagonal positions, dependency levels and the launch list of the exact ILU(0) / IC(0)
     of one sparsity pattern (sorted rows, diagonal stored); reusable for any number of numeric calls."""

@@ -12,7 +12,7 @@
 //   gko::matrix::{Dense, Csr, Coo, Ell, Sellp, Hybrid},
 //   gko::stop::{Iteration, ResidualNorm, Combined},
 //   gko::solver::{Cg, Gmres, LowerTrs, UpperTrs},
-//   gko::preconditioner::{Jacobi, Ilu}, gko::factorization::{ParIlu, ParIlut},
+//   gko::preconditioner::{Jacobi, Ilu}, gko::factorization::{ParIlu, ParIlut, ParIct},
 //   gko::read / gko::write (MatrixMarket), gko::initialize, gko::share, lend.
 //
 // Kernels exist only for HipExecutor (the MI355X backend).  The host executors
@@ -3370,6 +3370,151 @@ protected:
     }
     std::shared_ptr<matrix_type> l_, lt_;
 };
+
+// ---- ParIct, the threshold IC (core/factorization/par_ict.cpp:174-292) ----------------------------------------
+// The factor is the reference executor's, bit for bit: its sweep is sequential and in place, so its result is
+// determined by the pattern, and the device reproduces it with a level schedule (csrc/par_ict.hip).  Selection and
+// filter are those of ParIlut.
+template <typename V = double, typename I = int32>
+class ParIct {
+public:
+    using matrix_type = matrix::Csr<V, I>;
+    class Factory {
+    public:
+        Factory& with_iterations(size_type n) { iterations_ = n; return *this; }
+        Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
+        Factory& with_approximate_select(bool approximate) { approximate_select_ = approximate; return *this; }
+        // the reference executor's sample is deterministic either way; so is this one
+        Factory& with_deterministic_sample(bool deterministic) { deterministic_sample_ = deterministic; return *this; }
+        Factory& with_fill_in_limit(double limit) { fill_in_limit_ = limit; return *this; }
+        Factory& with_l_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { l_strategy_ = std::move(s); return *this; }
+        Factory& with_lt_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { lt_strategy_ = std::move(s); return *this; }
+        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
+        std::unique_ptr<ParIct> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<ParIct>(new ParIct(*this, std::move(A))); }
+        std::shared_ptr<const Executor> exec_;
+        size_type iterations_{5};
+        bool skip_sorting_{false}, approximate_select_{true}, deterministic_sample_{false};
+        double fill_in_limit_{2.0};
+        std::shared_ptr<typename matrix_type::strategy_type> l_strategy_, lt_strategy_;
+    };
+    static Factory build() { return Factory{}; }
+    std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
+    std::shared_ptr<const matrix_type> get_lt_factor() const { return lt_; }
+protected:
+    struct factor {
+        array<I> rp, ci;
+        array<V> v;
+        int64_t nnz() const { return static_cast<int64_t>(v.get_num_elems()); }
+    };
+    static factor transposed(const std::shared_ptr<const Executor>& exec, size_type n, const factor& m)
+    {
+        factor out{array<I>(exec, n + 1), array<I>(exec, m.nnz()), array<V>(exec, m.nnz())};
+        array<char> ws(exec, gkomi_csr_transpose_workspace_bytes(n));
+        GKOMI_CALL(gkomi_csr_transpose_f64_i32(nullptr, n, n, m.nnz(), m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), out.rp.get_data(), out.ci.get_data(), out.v.get_data(), ws.get_data(),
+                                               ws.get_num_elems()));
+        exec->synchronize();  // the workspace leaves scope
+        return out;
+    }
+    // par_ilut_factorization::threshold_filter: the reference executor's keeps |v| >= threshold || col == row whatever its `lower` flag says
+    static factor filtered(const std::shared_ptr<const Executor>& exec, size_type n, const factor& m, double threshold)
+    {
+        factor out{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
+        array<char> ws(exec, gkomi_par_ilut_filter_workspace_bytes(n));
+        int64_t nnz = 0;
+        GKOMI_CALL(gkomi_par_ilut_threshold_filter_f64_i32(nullptr, n, m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), threshold, out.rp.get_data(), nullptr, nullptr, nullptr, &nnz,
+                                                           ws.get_data(), ws.get_num_elems()));
+        out.ci = array<I>(exec, nnz);
+        out.v = array<V>(exec, nnz);
+        GKOMI_CALL(gkomi_par_ilut_threshold_filter_f64_i32(nullptr, n, m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), threshold, out.rp.get_data(), out.ci.get_data(), out.v.get_data(), nullptr,
+                                                           &nnz, ws.get_data(), ws.get_num_elems()));
+        return out;
+    }
+    // compute_factor in place
+    static void sweep(const std::shared_ptr<const Executor>& exec, size_type n, const matrix_type* a, factor& l)
+    {
+        array<char> ws(exec, gkomi_par_ict_sweep_workspace_bytes(n, l.nnz()));
+        int64_t info[6] = {};
+        GKOMI_CALL(gkomi_par_ict_analyse_i32(nullptr, n, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), ws.get_data(), ws.get_num_elems(), info));
+        GKOMI_CALL(gkomi_par_ict_compute_factor_f64_i32(nullptr, n, a->get_const_row_ptrs(), a->get_const_col_idxs(), a->get_const_values(), l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_data(),
+                                                        ws.get_const_data(), ws.get_num_elems()));
+        exec->synchronize();  // the workspace leaves scope
+    }
+    ParIct(const Factory& f, std::shared_ptr<const LinOp> A)
+    {
+        static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "ParIct is <double, int32>");
+        const auto& exec = f.exec_;
+        detail::require_device(exec, "par_ict_factorization");
+        auto src = as<const matrix_type>(A.get());
+        const size_type n = src->get_size()[0];
+        if (n != src->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, "ParIct needs a square matrix");
+        // GKO_ASSERT_EQ(parameters_.fill_in_limit > 0.0, true)
+        if (!(f.fill_in_limit_ > 0.0)) throw ValueMismatch(__FILE__, __LINE__, "ParIct needs fill_in_limit > 0");
+        std::unique_ptr<matrix_type> sorted;
+        if (!f.skip_sorting_ && !src->is_sorted_by_column_index()) {
+            matrix_data<V, I> d;
+            src->write(d);
+            sorted = matrix_type::create(exec);
+            sorted->read(d);
+            sorted->sort_by_column_index();
+            src = sorted.get();
+        }
+        factor l{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
+        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
+        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_i32(nullptr, n, src->get_const_row_ptrs(), src->get_const_col_idxs(), l.rp.get_data(), sws.get_data(), sws.get_num_elems()));
+        const size_type lnnz = exec->copy_val_to_host(l.rp.get_const_data() + n);
+        l.ci = array<I>(exec, lnnz); l.v = array<V>(exec, lnnz);
+        // diag_sqrt = true
+        GKOMI_CALL(gkomi_factorization_initialize_l_f64_i32(nullptr, n, src->get_const_row_ptrs(), src->get_const_col_idxs(), src->get_const_values(), l.rp.get_const_data(), l.ci.get_data(), l.v.get_data(), 1));
+        const int64_t l_nnz_limit = static_cast<I>(lnnz * f.fill_in_limit_);
+        array<char> gws(exec, gkomi_csr_spgemm_workspace_bytes(n, n)), cws(exec, gkomi_par_ict_add_candidates_workspace_bytes(n));
+        factor lt = transposed(exec, n, l);
+        for (size_type it = 0; it < f.iterations_; ++it) {
+            // L L^T
+            factor llh{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
+            int64_t llh_nnz = 0;
+            auto spgemm = [&] {
+                GKOMI_CALL(gkomi_csr_spgemm_f64_i32(nullptr, n, n, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_const_data(), n, n, lt.nnz(), lt.rp.get_const_data(), lt.ci.get_const_data(),
+                                                    lt.v.get_const_data(), nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, llh.rp.get_data(), llh.ci.get_num_elems() ? llh.ci.get_data() : nullptr,
+                                                    llh.v.get_num_elems() ? llh.v.get_data() : nullptr, &llh_nnz, gws.get_data(), gws.get_num_elems()));
+            };
+            spgemm();
+            llh.ci = array<I>(exec, llh_nnz);
+            llh.v = array<V>(exec, llh_nnz);
+            if (llh_nnz > 0) spgemm();
+            // the candidates L'
+            factor l_new{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
+            int64_t l_new_nnz = 0;
+            auto add_candidates = [&](bool fill) {
+                GKOMI_CALL(gkomi_par_ict_add_candidates_f64_i32(nullptr, n, llh.rp.get_const_data(), llh.ci.get_const_data(), llh.v.get_const_data(), src->get_const_row_ptrs(), src->get_const_col_idxs(),
+                                                                src->get_const_values(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_const_data(), l_new.rp.get_data(),
+                                                                fill ? l_new.ci.get_data() : nullptr, fill ? l_new.v.get_data() : nullptr, &l_new_nnz, cws.get_data(), cws.get_num_elems()));
+            };
+            add_candidates(false);
+            l_new.ci = array<I>(exec, l_new_nnz); l_new.v = array<V>(exec, l_new_nnz);
+            if (n > 0) add_candidates(true);
+            sweep(exec, n, src, l_new);
+            const int64_t rank = std::max<int64_t>(0, l_new_nnz - l_nnz_limit - 1);
+            double threshold = 0.0;
+            if (n > 0 && f.approximate_select_) {
+                array<char> ws(exec, gkomi_par_ilut_approx_workspace_bytes());
+                GKOMI_CALL(gkomi_par_ilut_threshold_approx_f64(nullptr, l_new_nnz, l_new.v.get_const_data(), rank, ws.get_data(), ws.get_num_elems(), &threshold));
+            } else if (n > 0) {
+                array<char> ws(exec, gkomi_par_ilut_select_workspace_bytes(l_new_nnz));
+                GKOMI_CALL(gkomi_par_ilut_threshold_select_f64(nullptr, l_new_nnz, l_new.v.get_const_data(), rank, ws.get_data(), ws.get_num_elems(), &threshold));
+            }
+            l = filtered(exec, n, l_new, threshold);
+            sweep(exec, n, src, l);
+            lt = transposed(exec, n, l);
+        }
+        auto lm = matrix_type::create(exec); auto ltm = matrix_type::create(exec);
+        lm->adopt(dim<2>(n, n), std::move(l.rp), std::move(l.ci), std::move(l.v));
+        ltm->adopt(dim<2>(n, n), std::move(lt.rp), std::move(lt.ci), std::move(lt.v));
+        if (f.l_strategy_) lm->set_strategy(f.l_strategy_);
+        if (f.lt_strategy_) ltm->set_strategy(f.lt_strategy_);
+        l_ = std::move(lm); lt_ = std::move(ltm);
+    }
+    std::shared_ptr<matrix_type> l_, lt_;
+};
 }  // namespace factorization
 
 namespace preconditioner {
@@ -3386,14 +3531,18 @@ public:
         std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
         // the exact IC(0) instead of the default ParIc sweeps
         Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::Ic<V, I>::Factory> f) { exact_ = std::move(f); return *this; }
+        // the threshold IC
+        Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::ParIct<V, I>::Factory> f) { ict_ = std::move(f); return *this; }
         std::unique_ptr<Ic> generate(std::shared_ptr<const LinOp> A) const
         {
+            if (ict_) return std::unique_ptr<Ic>(new Ic(this->exec_, *ict_, std::move(A)));
             if (exact_) return std::unique_ptr<Ic>(new Ic(this->exec_, *exact_, std::move(A)));
             return std::unique_ptr<Ic>(new Ic(this->exec_, iterations_, std::move(A)));
         }
         std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
         size_type iterations_{0};
         std::shared_ptr<const typename ::gko::factorization::Ic<V, I>::Factory> exact_;
+        std::shared_ptr<const typename ::gko::factorization::ParIct<V, I>::Factory> ict_;
     };
     static Factory build() { return Factory{}; }
     std::shared_ptr<const LinOp> get_l_solver() const { return l_solver_; }
@@ -3411,6 +3560,12 @@ protected:
         auto both = exact;
         both.with_both_factors(true);  // the preconditioner needs L^T whatever the factory says
         auto fact = (both.exec_ ? both : *both.on(exec)).generate(std::move(A));
+        l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(fact->get_l_factor());
+        lh_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(fact->get_lt_factor());
+    }
+    Ic(std::shared_ptr<const Executor> exec, const typename ::gko::factorization::ParIct<V, I>::Factory& ict, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
+    {
+        auto fact = (ict.exec_ ? ict : *ict.on(exec)).generate(std::move(A));
         l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(fact->get_l_factor());
         lh_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(fact->get_lt_factor());
     }
