@@ -1,8 +1,27 @@
 // What the level-scheduled factorizations share (ilu.hip: exact ILU(0) / IC(0); par_ilut.hip, par_ict.hip: the
 // ParILUT and ParICT sweeps): the analysed workspace of gkomi_ilu_analyse_i32, the row-length bins and the ways
-// a group of lanes meets; and what the two add_candidates merges share.  Internal to the library.
+// a group of lanes meets, and the frame that schedules their rows; and what the two add_candidates merges share.
+// Internal to the library.
+//
+// Scheduling.  No kernel here waits on another workgroup: no flags, no spins, no device-wide meetings.
+//   (a) a level of more than `narrow_level_rows` rows is one launch per row-length bin it holds rows of (the
+//       group width follows the row), each a capped grid that strides over the level's list of rows and takes
+//       the rows of its bin;
+//   (b) a run of consecutive levels of at most `narrow_level_rows` rows each is ONE launch of ONE
+//       workgroup that walks the levels with __syncthreads in between (a chain or thin band would
+//       otherwise cost a launch per row).
+// All boundaries are tuning constants; none has been measured.
+//
+// The frame is written once, over a row policy `Rows`: an aggregate of the factorization's pointers, built in the
+// kernel from its fields (see kernel_arg), with
+//   length(row)                                  the length that bins the row (the one the analysis saw);
+//   needs_products                               whether row() wants fact_block doubles of LDS for its products;
+//   row<W, InMemory, Coherent>(t, row, w, products, meet)   one row by a group of W lanes, lane t;
+//   memory_row(row)                              the working row of a row longer than bin_lds.
 #pragma once
 #include "common.hpp"
+
+#include <vector>
 
 #include "sort_scan.hpp"
 
@@ -135,7 +154,197 @@ __device__ __forceinline__ void wst(double* p, double v)
         *p = v;
     }
 }
+
+// ---- the frame: the kernels of (a) and (b) over a row policy ------------------------------------------------
+// A kernel takes the policy's fields one by one and builds the policy itself.  A field that is a pointer to const
+// arrives as a `const T* __restrict__` kernel argument: the pattern, read-only and unaliased for the whole launch.
+// Only of such an argument does the compiler know that no store and no meeting of the kernel changes what it
+// points to, which keeps the uniform loads of the pattern scalar; a pointer inside a struct argument carries no
+// such promise.  Any other field (a pointer to the values, a struct of pointers) arrives as it is.
+template <class Field>
+struct kernel_arg {
+    using type = Field;
+};
+template <class T>
+struct kernel_arg<const T*> {
+    using type = const T* __restrict__;
+};
+
+// fact_block doubles of LDS for the products of the workgroup's lanes, only where the row routine forms any:
+// those of the group whose first lane is `lane`
+template <class Rows>
+__device__ __forceinline__ double* products_from(int lane)
+{
+    if constexpr (Rows::needs_products) {
+        __shared__ double products[fact_block];
+        return products + lane;
+    } else {
+        return nullptr;
+    }
+}
+
+// one row by a whole workgroup: in LDS when it fits, in memory otherwise.  image: bin_lds doubles.
+template <class Rows, bool Coherent>
+__device__ __forceinline__ void block_row(const Rows& rows, int row, double* image, double* products)
+{
+    if (rows.length(row) <= bin_lds) {
+        rows.template row<fact_block, false, Coherent>(threadIdx.x, row, image, products, block_meet{});
+    } else {
+        rows.template row<fact_block, true, Coherent>(threadIdx.x, row, rows.memory_row(row), products, block_meet{});
+    }
+}
+
+// (a) one wide level, its rows of bin Bin (at most Cap entries): a group of W lanes per row, grid-stride over
+// perm[first, last); rows of the other bins are left to their own launch (rows of a level are independent)
+template <class Rows, int W, int Cap, int Bin, class... Fields>
+__global__ __launch_bounds__(fact_block) void level_kernel(const int32_t* __restrict__ perm, int first, int last,
+                                                          typename kernel_arg<Fields>::type... fields)
+{
+    const Rows rows{fields...};
+    constexpr int groups = fact_block / W;
+    __shared__ double image[groups * Cap];
+    const int g = threadIdx.x / W, t = threadIdx.x % W;
+    double* products = products_from<Rows>(g * W);
+    for (int pos = first + blockIdx.x * groups + g; pos < last; pos += gridDim.x * groups) {
+        const int row = perm[pos];
+        if (bin_of(rows.length(row)) != Bin) continue;  // the same answer in every lane of the group
+        rows.template row<W, false, false>(t, row, image + g * Cap, products, wave_meet{});
+        wave_meet{}();  // the image is used again
+    }
+}
+
+// (a) the rows longer than bin_wave of one wide level: a workgroup per row
+template <class Rows, class... Fields>
+__global__ __launch_bounds__(fact_block) void level_block_kernel(const int32_t* __restrict__ perm, int first, int last,
+                                                                typename kernel_arg<Fields>::type... fields)
+{
+    const Rows rows{fields...};
+    __shared__ double image[bin_lds];
+    double* products = products_from<Rows>(0);
+    for (int pos = first + blockIdx.x; pos < last; pos += gridDim.x) {
+        const int row = perm[pos];
+        if (bin_of(rows.length(row)) != 2) continue;  // the same answer in the whole workgroup
+        block_row<Rows, false>(rows, row, image, products);
+        __syncthreads();
+    }
+}
+
+// (b) ONE workgroup walks the narrow levels [first_level, last_level): a wave per row of at most bin_wave entries,
+// then the workgroup per longer row, __syncthreads between levels.  What a level wrote is read by the
+// next through agent-scope loads after a release fence.
+template <class Rows, class... Fields>
+__global__ __launch_bounds__(fact_block) void run_kernel(const int32_t* __restrict__ perm,
+                                                        const int32_t* __restrict__ level_start,
+                                                        const int32_t* __restrict__ level_longest, int first_level,
+                                                        int last_level, typename kernel_arg<Fields>::type... fields)
+{
+    const Rows rows{fields...};
+    constexpr int waves = fact_block / wave_size;
+    static_assert(waves * bin_wave >= bin_lds, "the images of the waves hold the image of the workgroup");
+    __shared__ double image[waves * bin_wave];
+    const int wave = threadIdx.x / wave_size, lane = threadIdx.x % wave_size;
+    for (int lvl = first_level; lvl < last_level; ++lvl) {
+        const int first = level_start[lvl], last = level_start[lvl + 1];
+        // the rows of at most bin_wave entries: a wave each
+        for (int pos = first + wave; pos < last; pos += waves) {
+            const int row = perm[pos];
+            if (bin_of(rows.length(row)) == 2) continue;
+            rows.template row<wave_size, false, true>(lane, row, image + wave * bin_wave,
+                                                      products_from<Rows>(wave * wave_size), wave_meet{});
+            wave_meet{}();
+        }
+        // the longer ones, if the level has any: the workgroup, one after the other (the images are shared)
+        if (level_longest[lvl] > bin_wave) {
+            __syncthreads();
+            for (int pos = first; pos < last; ++pos) {
+                const int row = perm[pos];
+                if (bin_of(rows.length(row)) != 2) continue;
+                block_row<Rows, true>(rows, row, image, products_from<Rows>(0));
+                __syncthreads();
+            }
+        }
+        __threadfence();
+        __syncthreads();
+    }
+}
+
+// ---- the host side of the frame ------------------------------------------------------------------------------
+// the launches of an analysed workspace
+struct schedule {
+    analysis_header header;
+    std::vector<segment> segments;
+    const int32_t* perm;
+    const int32_t* level_start;
+    const int32_t* level_longest;
+};
+
+// Reads the workspace of gkomi_ilu_analyse_i32 at `ws` (the caller has checked its size).  GKOMI_EINVAL: no
+// analysis, a failed one (missing diagonal, unsorted row), or one of another n.  A sweep that keeps a header of
+// its own in front of its workspace has it fetched in the same round trip (outer_bytes of `outer` to
+// `outer_header`) and checks it itself.
+inline int load_schedule(hipStream_t stream, const char* ws, int64_t n, schedule* out, const void* outer = nullptr,
+                         void* outer_header = nullptr, size_t outer_bytes = 0)
+{
+    analysis_header& h = out->header;
+    if (outer != nullptr) {
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(outer_header, outer, outer_bytes, hipMemcpyDeviceToHost, stream)));
+    }
+    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost, stream)));
+    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+    if (h.magic != ws_magic || h.n != n || h.nsegments < 0 || h.nsegments > n) return GKOMI_EINVAL;
+    const analysis_layout l = make_layout(n);
+    out->segments.resize(static_cast<size_t>(h.nsegments));
+    if (h.nsegments > 0) {
+        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(out->segments.data(), ws + l.segments,
+                                                  sizeof(segment) * out->segments.size(), hipMemcpyDeviceToHost, stream)));
+        GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+    }
+    out->perm = reinterpret_cast<const int32_t*>(ws + l.perm);
+    out->level_start = reinterpret_cast<const int32_t*>(ws + l.level_start);
+    out->level_longest = reinterpret_cast<const int32_t*>(ws + l.level_longest);
+    return GKOMI_SUCCESS;
+}
+
+// the launches of `s` for the policy Rows{fields...}
+template <class Rows, class... Fields>
+int launch_schedule(hipStream_t stream, const schedule& s, Fields... fields)
+{
+    for (const segment& sg : s.segments) {
+        if (sg.kind == 1) {
+            hipLaunchKernelGGL((run_kernel<Rows, Fields...>), dim3(1), dim3(fact_block), 0, stream, s.perm, s.level_start,
+                               s.level_longest, sg.first, sg.last, fields...);
+            continue;
+        }
+        const int64_t count = sg.last - sg.first;
+        // one launch per bin the level holds rows of
+        if (sg.bins & 1) {
+            hipLaunchKernelGGL((level_kernel<Rows, short_width, bin_short, 0, Fields...>),
+                               dim3(grid_for(count, fact_block / short_width, max_level_grid)), dim3(fact_block), 0, stream,
+                               s.perm, sg.first, sg.last, fields...);
+        }
+        if (sg.bins & 2) {
+            hipLaunchKernelGGL((level_kernel<Rows, wave_size, bin_wave, 1, Fields...>),
+                               dim3(grid_for(count, fact_block / wave_size, max_level_grid)), dim3(fact_block), 0, stream,
+                               s.perm, sg.first, sg.last, fields...);
+        }
+        if (sg.bins & 4) {
+            hipLaunchKernelGGL((level_block_kernel<Rows, Fields...>), dim3(grid_for(count, 1, max_level_grid)),
+                               dim3(fact_block), 0, stream, s.perm, sg.first, sg.last, fields...);
+        }
+    }
+    return check_launch();
+}
 #endif
+
+// what gkomi_ilu_tuning, gkomi_par_ilut_tuning and gkomi_par_ict_tuning report
+inline void fill_tuning(int64_t* host_out)
+{
+    if (host_out == nullptr) return;
+    host_out[0] = bin_short;
+    host_out[1] = bin_wave;
+    host_out[2] = bin_lds;
+    host_out[3] = narrow_level_rows;
+}
 
 }  // namespace fact
 }  // namespace gkomi

@@ -20,14 +20,7 @@
 //
 // The working row lives in LDS (an "image" per group); finished rows are read from memory.
 //
-// Scheduling.  No kernel here waits on another workgroup: no flags, no spins, no device-wide meetings.
-//   (a) a level of more than `narrow_level_rows` rows is one launch per row-length bin it holds rows of (the
-//       bins of fact_levels.hpp: the group width follows the row), each a capped grid that strides over the level's list
-//       of rows and takes the rows of its bin;
-//   (b) a run of consecutive levels of at most `narrow_level_rows` rows each is ONE launch of ONE
-//       workgroup that walks the levels with __syncthreads in between (a chain or thin band would
-//       otherwise cost a launch per row).
-// All boundaries are tuning constants; none has been measured.
+// Scheduling: as in fact_levels.hpp, whose frame runs ilu_row and ic_row over the levels analysed here.
 #include "common.hpp"
 
 #include <vector>
@@ -39,7 +32,7 @@
 namespace gkomi {
 namespace {
 
-// the bins, the analysed workspace and the meetings are shared with the ParILUT sweep (fact_levels.hpp)
+// the bins, the analysed workspace, the meetings and the frame are shared with the sweeps (fact_levels.hpp)
 using namespace fact;
 
 // diag[row] = position of the diagonal; flags[0] |= 1: a row without diagonal, |= 2: a row that is not
@@ -165,121 +158,31 @@ __device__ __forceinline__ void ic_row(int t, int row, const int32_t* __restrict
     }
 }
 
-// one row by a whole workgroup: in LDS when it fits, in memory otherwise.  image: bin_lds doubles.
-template <bool Ic, bool Coherent>
-__device__ __forceinline__ void block_row(int row, const int32_t* __restrict__ row_ptrs,
-                                          const int32_t* __restrict__ col_idxs, const int32_t* __restrict__ diag,
-                                          double* vals, double* image, double* products)
-{
-    const int t = threadIdx.x;
-    const int begin = row_ptrs[row];
-    const int len = row_ptrs[row + 1] - begin;
-    if (len <= bin_lds) {
-        if (Ic) {
-            ic_row<fact_block, false, Coherent>(t, row, row_ptrs, col_idxs, diag, vals, image, products, block_meet{});
-        } else {
-            ilu_row<fact_block, false, Coherent>(t, row, row_ptrs, col_idxs, diag, vals, image, block_meet{});
-        }
-    } else {
-        if (Ic) {
-            ic_row<fact_block, true, Coherent>(t, row, row_ptrs, col_idxs, diag, vals, vals + begin, products, block_meet{});
-        } else {
-            ilu_row<fact_block, true, Coherent>(t, row, row_ptrs, col_idxs, diag, vals, vals + begin, block_meet{});
-        }
-    }
-}
-
-// (a) one wide level, its rows of bin Bin (at most Cap entries): a group of W lanes per row, grid-stride over
-// perm[first, last); rows of the other bins are left to their own launch (rows of a level are independent)
-template <bool Ic, int W, int Cap, int Bin>
-__global__ __launch_bounds__(fact_block) void fact_level_kernel(const int32_t* __restrict__ row_ptrs,
-                                                               const int32_t* __restrict__ col_idxs,
-                                                               const int32_t* __restrict__ diag,
-                                                               const int32_t* __restrict__ perm, int first, int last,
-                                                               double* vals)
-{
-    constexpr int groups = fact_block / W;
-    __shared__ double image[groups * Cap];
-    __shared__ double products[fact_block];
-    const int g = threadIdx.x / W, t = threadIdx.x % W;
-    for (int pos = first + blockIdx.x * groups + g; pos < last; pos += gridDim.x * groups) {
-        const int row = perm[pos];
-        if (bin_of(row_ptrs[row + 1] - row_ptrs[row]) != Bin) continue;  // the same answer in every lane of the group
-        if (Ic) {
-            ic_row<W, false, false>(t, row, row_ptrs, col_idxs, diag, vals, image + g * Cap, products + g * W, wave_meet{});
-        } else {
-            ilu_row<W, false, false>(t, row, row_ptrs, col_idxs, diag, vals, image + g * Cap, wave_meet{});
-        }
-        wave_meet{}();  // the image is loaded again
-    }
-}
-
-// (a) the rows longer than bin_wave of one wide level: a workgroup per row
+// ---- the row policies of the frame (fact_levels.hpp) -----------------------------------------------------
+// A's own rows bin them; a row too long for LDS is factorized in place
 template <bool Ic>
-__global__ __launch_bounds__(fact_block) void fact_level_block_kernel(const int32_t* __restrict__ row_ptrs,
-                                                                     const int32_t* __restrict__ col_idxs,
-                                                                     const int32_t* __restrict__ diag,
-                                                                     const int32_t* __restrict__ perm, int first,
-                                                                     int last, double* vals)
-{
-    __shared__ double image[bin_lds];
-    __shared__ double products[fact_block];
-    for (int pos = first + blockIdx.x; pos < last; pos += gridDim.x) {
-        const int row = perm[pos];
-        if (bin_of(row_ptrs[row + 1] - row_ptrs[row]) != 2) continue;  // the same answer in the whole workgroup
-        block_row<Ic, false>(row, row_ptrs, col_idxs, diag, vals, image, products);
-        __syncthreads();
-    }
-}
-
-// (b) ONE workgroup walks the narrow levels [first_level, last_level): a wave per row of at most bin_wave entries,
-// then the workgroup per longer row, __syncthreads between levels.  What a level wrote is read by the
-// next through agent-scope loads after a release fence.
-template <bool Ic>
-__global__ __launch_bounds__(fact_block) void fact_run_kernel(const int32_t* __restrict__ row_ptrs,
-                                                             const int32_t* __restrict__ col_idxs,
-                                                             const int32_t* __restrict__ diag,
-                                                             const int32_t* __restrict__ perm,
-                                                             const int32_t* __restrict__ level_start,
-                                                             const int32_t* __restrict__ level_longest,
-                                                             int first_level, int last_level, double* vals)
-{
-    constexpr int waves = fact_block / wave_size;
-    static_assert(waves * bin_wave >= bin_lds, "the images of the waves hold the image of the workgroup");
-    __shared__ double image[waves * bin_wave];
-    __shared__ double products[fact_block];
-    const int wave = threadIdx.x / wave_size, lane = threadIdx.x % wave_size;
-    for (int lvl = first_level; lvl < last_level; ++lvl) {
-        const int first = level_start[lvl], last = level_start[lvl + 1];
-        // the rows of at most bin_wave entries: a wave each
-        for (int pos = first + wave; pos < last; pos += waves) {
-            const int row = perm[pos];
-            if (bin_of(row_ptrs[row + 1] - row_ptrs[row]) == 2) continue;
-            if (Ic) {
-                ic_row<wave_size, false, true>(lane, row, row_ptrs, col_idxs, diag, vals, image + wave * bin_wave,
-                                               products + wave * wave_size, wave_meet{});
-            } else {
-                ilu_row<wave_size, false, true>(lane, row, row_ptrs, col_idxs, diag, vals, image + wave * bin_wave,
-                                                wave_meet{});
-            }
-            wave_meet{}();
+struct csr_rows {
+    const int32_t* row_ptrs;
+    const int32_t* col_idxs;
+    const int32_t* diag;
+    double* vals;
+    static constexpr bool needs_products = Ic;
+    __device__ __forceinline__ int length(int i) const { return row_ptrs[i + 1] - row_ptrs[i]; }
+    __device__ __forceinline__ double* memory_row(int i) const { return vals + row_ptrs[i]; }
+    template <int W, bool InMemory, bool Coherent, class Meet>
+    __device__ __forceinline__ void row(int t, int i, double* w, double* products, Meet meet) const
+    {
+        if constexpr (Ic) {
+            ic_row<W, InMemory, Coherent>(t, i, row_ptrs, col_idxs, diag, vals, w, products, meet);
+        } else {
+            ilu_row<W, InMemory, Coherent>(t, i, row_ptrs, col_idxs, diag, vals, w, meet);
         }
-        // the longer ones, if the level has any: the workgroup, one after the other (the images are shared)
-        if (level_longest[lvl] > bin_wave) {
-            __syncthreads();
-            for (int pos = first; pos < last; ++pos) {
-                const int row = perm[pos];
-                if (bin_of(row_ptrs[row + 1] - row_ptrs[row]) != 2) continue;
-                block_row<Ic, true>(row, row_ptrs, col_idxs, diag, vals, image, products);
-                __syncthreads();
-            }
-        }
-        __threadfence();
-        __syncthreads();
     }
-}
+};
+using ilu_rows = csr_rows<false>;
+using ic_rows = csr_rows<true>;
 
-template <bool Ic>
+template <class Rows>
 int compute(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs, double* vals,
             const void* workspace, size_t workspace_bytes)
 {
@@ -288,44 +191,10 @@ int compute(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_
     const analysis_layout l = make_layout(n);
     if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
     const char* ws = static_cast<const char*>(workspace);
-    analysis_header h{};
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-    // no analysis, a failed one (missing diagonal, unsorted row), or one of another matrix
-    if (h.magic != ws_magic || h.n != n || h.nsegments < 0 || h.nsegments > n) return GKOMI_EINVAL;
+    schedule sched;
+    GKOMI_TRY(load_schedule(stream, ws, n, &sched));
     if (n == 0) return GKOMI_SUCCESS;
-    std::vector<segment> segs(static_cast<size_t>(h.nsegments));
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(segs.data(), ws + l.segments, sizeof(segment) * segs.size(),
-                                              hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-    const int32_t* diag = reinterpret_cast<const int32_t*>(ws + l.diag);
-    const int32_t* perm = reinterpret_cast<const int32_t*>(ws + l.perm);
-    const int32_t* level_start = reinterpret_cast<const int32_t*>(ws + l.level_start);
-    const int32_t* level_longest = reinterpret_cast<const int32_t*>(ws + l.level_longest);
-    for (const segment& sg : segs) {
-        if (sg.kind == 1) {
-            hipLaunchKernelGGL(fact_run_kernel<Ic>, dim3(1), dim3(fact_block), 0, stream, row_ptrs, col_idxs, diag, perm,
-                               level_start, level_longest, sg.first, sg.last, vals);
-            continue;
-        }
-        const int64_t rows = sg.last - sg.first;
-        // one launch per bin the level holds rows of
-        if (sg.bins & 1) {
-            hipLaunchKernelGGL((fact_level_kernel<Ic, short_width, bin_short, 0>),
-                               dim3(grid_for(rows, fact_block / short_width, max_level_grid)), dim3(fact_block), 0, stream,
-                               row_ptrs, col_idxs, diag, perm, sg.first, sg.last, vals);
-        }
-        if (sg.bins & 2) {
-            hipLaunchKernelGGL((fact_level_kernel<Ic, wave_size, bin_wave, 1>),
-                               dim3(grid_for(rows, fact_block / wave_size, max_level_grid)), dim3(fact_block), 0, stream,
-                               row_ptrs, col_idxs, diag, perm, sg.first, sg.last, vals);
-        }
-        if (sg.bins & 4) {
-            hipLaunchKernelGGL(fact_level_block_kernel<Ic>, dim3(grid_for(rows, 1, max_level_grid)), dim3(fact_block), 0,
-                               stream, row_ptrs, col_idxs, diag, perm, sg.first, sg.last, vals);
-        }
-    }
-    return check_launch();
+    return launch_schedule<Rows>(stream, sched, row_ptrs, col_idxs, reinterpret_cast<const int32_t*>(ws + l.diag), vals);
 }
 
 }  // namespace
@@ -334,7 +203,7 @@ int compute(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_
 int ilu_compute_lu(hipStream_t stream, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs, double* vals,
                    const void* analysis_workspace, size_t workspace_bytes)
 {
-    return compute<false>(stream, n, row_ptrs, col_idxs, vals, analysis_workspace, workspace_bytes);
+    return compute<ilu_rows>(stream, n, row_ptrs, col_idxs, vals, analysis_workspace, workspace_bytes);
 }
 
 }  // namespace gkomi
@@ -457,14 +326,7 @@ extern "C" int gkomi_ilu_analyse_i32(gkomi_stream_t s, int64_t n, const int32_t*
     return GKOMI_SUCCESS;
 }
 
-extern "C" void gkomi_ilu_tuning(int64_t* host_out)
-{
-    if (host_out == nullptr) return;
-    host_out[0] = bin_short;
-    host_out[1] = bin_wave;
-    host_out[2] = bin_lds;
-    host_out[3] = narrow_level_rows;
-}
+extern "C" void gkomi_ilu_tuning(int64_t* host_out) { fill_tuning(host_out); }
 
 extern "C" int gkomi_ilu_compute_lu_f64_i32(gkomi_stream_t s, int64_t n, const int32_t* row_ptrs,
                                             const int32_t* col_idxs, double* vals, const void* analysis_workspace,
@@ -476,5 +338,5 @@ extern "C" int gkomi_ilu_compute_lu_f64_i32(gkomi_stream_t s, int64_t n, const i
 extern "C" int gkomi_ic_compute_f64_i32(gkomi_stream_t s, int64_t n, const int32_t* row_ptrs, const int32_t* col_idxs,
                                         double* vals, const void* analysis_workspace, size_t workspace_bytes)
 {
-    return compute<true>(to_stream(s), n, row_ptrs, col_idxs, vals, analysis_workspace, workspace_bytes);
+    return compute<ic_rows>(to_stream(s), n, row_ptrs, col_idxs, vals, analysis_workspace, workspace_bytes);
 }

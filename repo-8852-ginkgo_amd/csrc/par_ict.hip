@@ -21,14 +21,11 @@
 // of row col that this row does not store contributes +0.0, which leaves every bit alone because a sum that
 // starts at +0.0 is never -0.0.  The library is built with -ffp-contract=off.
 //
-// Scheduling: as in ilu.hip.  No kernel waits on another workgroup: no flags, no spins, no device-wide
-// meetings.  A wide level is one launch per row-length bin it holds rows of, a run of narrow levels one
-// launch of one workgroup.  All boundaries (gkomi_par_ict_tuning) are tuning constants; none has been
-// measured.
+// Scheduling: as in fact_levels.hpp, whose frame runs ict_row over the levels of L' (boundaries:
+// gkomi_par_ict_tuning).
 #include "common.hpp"
 
 #include <cmath>
-#include <vector>
 
 #include "fact_levels.hpp"
 #include "internal.hpp"
@@ -200,91 +197,18 @@ __device__ __forceinline__ void ict_row(int t, int row, const ict_args& g, doubl
     }
 }
 
-// one row by a whole workgroup: in LDS when it fits, in memory otherwise.  image: bin_lds doubles.
-template <bool Coherent>
-__device__ __forceinline__ void ict_block_row(int row, const ict_args& g, double* image, double* products)
-{
-    const int begin = g.l_row_ptrs[row];
-    if (g.l_row_ptrs[row + 1] - begin <= bin_lds) {
-        ict_row<fact_block, false, Coherent>(threadIdx.x, row, g, image, products, block_meet{});
-    } else {
-        ict_row<fact_block, true, Coherent>(threadIdx.x, row, g, g.l_vals + begin, products, block_meet{});
+// the row policy of the frame (fact_levels.hpp): the row of L' bins it; a row too long for LDS is swept in place
+struct ict_rows {
+    ict_args g;
+    static constexpr bool needs_products = true;
+    __device__ __forceinline__ int length(int i) const { return g.l_row_ptrs[i + 1] - g.l_row_ptrs[i]; }
+    __device__ __forceinline__ double* memory_row(int i) const { return g.l_vals + g.l_row_ptrs[i]; }
+    template <int W, bool InMemory, bool Coherent, class Meet>
+    __device__ __forceinline__ void row(int t, int i, double* w, double* products, Meet meet) const
+    {
+        ict_row<W, InMemory, Coherent>(t, i, g, w, products, meet);
     }
-}
-
-__device__ __forceinline__ int row_bin(const ict_args& g, int row)
-{
-    return bin_of(g.l_row_ptrs[row + 1] - g.l_row_ptrs[row]);
-}
-
-// (a) one wide level, its rows of bin Bin (at most Cap entries): a group of W lanes per row, grid-stride over
-// perm[first, last)
-template <int W, int Cap, int Bin>
-__global__ __launch_bounds__(fact_block) void ict_level_kernel(ict_args g, const int32_t* __restrict__ perm, int first,
-                                                              int last)
-{
-    constexpr int groups = fact_block / W;
-    __shared__ double image[groups * Cap];
-    __shared__ double products[fact_block];
-    const int grp = threadIdx.x / W, t = threadIdx.x % W;
-    for (int pos = first + blockIdx.x * groups + grp; pos < last; pos += gridDim.x * groups) {
-        const int row = perm[pos];
-        if (row_bin(g, row) != Bin) continue;  // the same answer in every lane of the group
-        ict_row<W, false, false>(t, row, g, image + grp * Cap, products + grp * W, wave_meet{});
-        wave_meet{}();  // the image is loaded again
-    }
-}
-
-// (a) the rows longer than bin_wave of one wide level: a workgroup per row
-__global__ __launch_bounds__(fact_block) void ict_level_block_kernel(ict_args g, const int32_t* __restrict__ perm,
-                                                                    int first, int last)
-{
-    __shared__ double image[bin_lds];
-    __shared__ double products[fact_block];
-    for (int pos = first + blockIdx.x; pos < last; pos += gridDim.x) {
-        const int row = perm[pos];
-        if (row_bin(g, row) != 2) continue;  // the same answer in the whole workgroup
-        ict_block_row<false>(row, g, image, products);
-        __syncthreads();
-    }
-}
-
-// (b) ONE workgroup walks the narrow levels [first_level, last_level): a wave per row of at most bin_wave
-// entries, then the workgroup per longer row, __syncthreads between levels.  What a level wrote is read by the
-// next through agent-scope loads after a release fence.
-__global__ __launch_bounds__(fact_block) void ict_run_kernel(ict_args g, const int32_t* __restrict__ perm,
-                                                            const int32_t* __restrict__ level_start,
-                                                            const int32_t* __restrict__ level_longest, int first_level,
-                                                            int last_level)
-{
-    constexpr int waves = fact_block / wave_size;
-    static_assert(waves * bin_wave >= bin_lds, "the images of the waves hold the image of the workgroup");
-    __shared__ double image[waves * bin_wave];
-    __shared__ double products[fact_block];
-    const int wave = threadIdx.x / wave_size, lane = threadIdx.x % wave_size;
-    for (int lvl = first_level; lvl < last_level; ++lvl) {
-        const int first = level_start[lvl], last = level_start[lvl + 1];
-        // the rows of at most bin_wave entries: a wave each
-        for (int pos = first + wave; pos < last; pos += waves) {
-            const int row = perm[pos];
-            if (row_bin(g, row) == 2) continue;
-            ict_row<wave_size, false, true>(lane, row, g, image + wave * bin_wave, products + wave * wave_size, wave_meet{});
-            wave_meet{}();
-        }
-        // the longer ones, if the level has any: the workgroup, one after the other (the images are shared)
-        if (level_longest[lvl] > bin_wave) {
-            __syncthreads();
-            for (int pos = first; pos < last; ++pos) {
-                const int row = perm[pos];
-                if (row_bin(g, row) != 2) continue;
-                ict_block_row<true>(row, g, image, products);
-                __syncthreads();
-            }
-        }
-        __threadfence();
-        __syncthreads();
-    }
-}
+};
 
 }  // namespace
 }  // namespace gkomi
@@ -335,14 +259,7 @@ extern "C" int gkomi_par_ict_add_candidates_f64_i32(gkomi_stream_t s, int64_t n,
     return check_launch();
 }
 
-extern "C" void gkomi_par_ict_tuning(int64_t* host_out)
-{
-    if (host_out == nullptr) return;
-    host_out[0] = bin_short;
-    host_out[1] = bin_wave;
-    host_out[2] = bin_lds;
-    host_out[3] = narrow_level_rows;
-}
+extern "C" void gkomi_par_ict_tuning(int64_t* host_out) { fill_tuning(host_out); }
 
 extern "C" size_t gkomi_par_ict_sweep_workspace_bytes(int64_t n, int64_t l_nnz)
 {
@@ -399,46 +316,10 @@ extern "C" int gkomi_par_ict_compute_factor_f64_i32(gkomi_stream_t s, int64_t n,
     hipStream_t stream = to_stream(s);
     const char* ws = static_cast<const char*>(analysis_workspace);
     ict_header ih{};
-    analysis_header h{};
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&ih, ws, sizeof(ih), hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&h, ws + l.levels, sizeof(h), hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+    schedule sched;
+    GKOMI_TRY(load_schedule(stream, ws + l.levels, n, &sched, ws, &ih, sizeof(ih)));
     // no analysis, a failed one, or one of another factor
-    if (ih.magic != ict_magic || ih.n != n || ih.l_nnz != l_nnz) return GKOMI_EINVAL;
-    if (h.magic != ws_magic || h.n != n || h.nnz != l_nnz || h.nsegments < 0 || h.nsegments > n) return GKOMI_EINVAL;
+    if (ih.magic != ict_magic || ih.n != n || ih.l_nnz != l_nnz || sched.header.nnz != l_nnz) return GKOMI_EINVAL;
     if (n == 0) return GKOMI_SUCCESS;
-    const analysis_layout al = make_layout(n);
-    const char* lws = ws + l.levels;
-    std::vector<segment> segs(static_cast<size_t>(h.nsegments));
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(segs.data(), lws + al.segments, sizeof(segment) * segs.size(),
-                                              hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-    const int32_t* perm = reinterpret_cast<const int32_t*>(lws + al.perm);
-    const int32_t* level_start = reinterpret_cast<const int32_t*>(lws + al.level_start);
-    const int32_t* level_longest = reinterpret_cast<const int32_t*>(lws + al.level_longest);
-    const ict_args g{a_row_ptrs, a_col_idxs, a_vals, l_row_ptrs, l_col_idxs, l_vals};
-    for (const segment& sg : segs) {
-        if (sg.kind == 1) {
-            hipLaunchKernelGGL(ict_run_kernel, dim3(1), dim3(fact_block), 0, stream, g, perm, level_start, level_longest,
-                               sg.first, sg.last);
-            continue;
-        }
-        const int64_t rows = sg.last - sg.first;
-        // one launch per bin the level holds rows of
-        if (sg.bins & 1) {
-            hipLaunchKernelGGL((ict_level_kernel<short_width, bin_short, 0>),
-                               dim3(grid_for(rows, fact_block / short_width, max_level_grid)), dim3(fact_block), 0, stream, g,
-                               perm, sg.first, sg.last);
-        }
-        if (sg.bins & 2) {
-            hipLaunchKernelGGL((ict_level_kernel<wave_size, bin_wave, 1>),
-                               dim3(grid_for(rows, fact_block / wave_size, max_level_grid)), dim3(fact_block), 0, stream, g,
-                               perm, sg.first, sg.last);
-        }
-        if (sg.bins & 4) {
-            hipLaunchKernelGGL(ict_level_block_kernel, dim3(grid_for(rows, 1, max_level_grid)), dim3(fact_block), 0, stream, g,
-                               perm, sg.first, sg.last);
-        }
-    }
-    return check_launch();
+    return launch_schedule<ict_rows>(stream, sched, ict_args{a_row_ptrs, a_col_idxs, a_vals, l_row_ptrs, l_col_idxs, l_vals});
 }

@@ -24,15 +24,12 @@
 // U is read by rows (CSR); the reference reads its CSC copy, which holds the same values at every moment
 // of its sweep.  ut_vals is brought up to date from u_vals afterwards.
 //
-// Scheduling: as in ilu.hip.  No kernel waits on another workgroup: no flags, no spins, no device-wide
-// meetings.  A wide level is one launch per row-length bin it holds rows of, a run of narrow levels one
-// launch of one workgroup.  All boundaries (gkomi_par_ilut_tuning) are tuning constants; none has been
-// measured.
+// Scheduling: as in fact_levels.hpp, whose frame runs sweep_row over the levels of M (boundaries:
+// gkomi_par_ilut_tuning).
 #include "common.hpp"
 
 #include <cmath>
 #include <cstring>
-#include <vector>
 
 #include "fact_levels.hpp"
 #include "internal.hpp"
@@ -397,87 +394,19 @@ __device__ __forceinline__ void sweep_row(int t, int row, const sweep_args& g, d
     }
 }
 
-// one row by a whole workgroup: the sums in LDS when they fit, in memory otherwise.  image: bin_lds doubles.
-template <bool Coherent>
-__device__ __forceinline__ void sweep_block_row(int row, const sweep_args& g, double* image)
-{
-    const int mb = g.m_row_ptrs[row];
-    if (g.m_row_ptrs[row + 1] - mb <= bin_lds) {
-        sweep_row<fact_block, false, Coherent>(threadIdx.x, row, g, image, block_meet{});
-    } else {
-        sweep_row<fact_block, true, Coherent>(threadIdx.x, row, g, g.sums + mb, block_meet{});
+// the row policy of the frame (fact_levels.hpp): the combined row bins it; the sums of a row too long for LDS
+// live in the workspace
+struct sweep_rows {
+    sweep_args g;
+    static constexpr bool needs_products = false;
+    __device__ __forceinline__ int length(int i) const { return g.m_row_ptrs[i + 1] - g.m_row_ptrs[i]; }
+    __device__ __forceinline__ double* memory_row(int i) const { return g.sums + g.m_row_ptrs[i]; }
+    template <int W, bool InMemory, bool Coherent, class Meet>
+    __device__ __forceinline__ void row(int t, int i, double* w, double*, Meet meet) const
+    {
+        sweep_row<W, InMemory, Coherent>(t, i, g, w, meet);
     }
-}
-
-__device__ __forceinline__ int combined_bin(const sweep_args& g, int row)
-{
-    return bin_of(g.m_row_ptrs[row + 1] - g.m_row_ptrs[row]);
-}
-
-// (a) one wide level, its rows of bin Bin (at most Cap entries): a group of W lanes per row, grid-stride over
-// perm[first, last)
-template <int W, int Cap, int Bin>
-__global__ __launch_bounds__(fact_block) void sweep_level_kernel(sweep_args g, const int32_t* __restrict__ perm,
-                                                                int first, int last)
-{
-    constexpr int groups = fact_block / W;
-    __shared__ double image[groups * Cap];
-    const int grp = threadIdx.x / W, t = threadIdx.x % W;
-    for (int pos = first + blockIdx.x * groups + grp; pos < last; pos += gridDim.x * groups) {
-        const int row = perm[pos];
-        if (combined_bin(g, row) != Bin) continue;  // the same answer in every lane of the group
-        sweep_row<W, false, false>(t, row, g, image + grp * Cap, wave_meet{});
-        wave_meet{}();  // the image is used again
-    }
-}
-
-// (a) the rows longer than bin_wave of one wide level: a workgroup per row
-__global__ __launch_bounds__(fact_block) void sweep_level_block_kernel(sweep_args g, const int32_t* __restrict__ perm,
-                                                                      int first, int last)
-{
-    __shared__ double image[bin_lds];
-    for (int pos = first + blockIdx.x; pos < last; pos += gridDim.x) {
-        const int row = perm[pos];
-        if (combined_bin(g, row) != 2) continue;  // the same answer in the whole workgroup
-        sweep_block_row<false>(row, g, image);
-        __syncthreads();
-    }
-}
-
-// (b) ONE workgroup walks the narrow levels [first_level, last_level): a wave per row of at most bin_wave
-// entries, then the workgroup per longer row, __syncthreads between levels.  What a level wrote is read by the
-// next through agent-scope loads after a release fence.
-__global__ __launch_bounds__(fact_block) void sweep_run_kernel(sweep_args g, const int32_t* __restrict__ perm,
-                                                              const int32_t* __restrict__ level_start,
-                                                              const int32_t* __restrict__ level_longest,
-                                                              int first_level, int last_level)
-{
-    constexpr int waves = fact_block / wave_size;
-    static_assert(waves * bin_wave >= bin_lds, "the images of the waves hold the image of the workgroup");
-    __shared__ double image[waves * bin_wave];
-    const int wave = threadIdx.x / wave_size, lane = threadIdx.x % wave_size;
-    for (int lvl = first_level; lvl < last_level; ++lvl) {
-        const int first = level_start[lvl], last = level_start[lvl + 1];
-        for (int pos = first + wave; pos < last; pos += waves) {
-            const int row = perm[pos];
-            if (combined_bin(g, row) == 2) continue;
-            sweep_row<wave_size, false, true>(lane, row, g, image + wave * bin_wave, wave_meet{});
-            wave_meet{}();
-        }
-        // the longer ones, if the level has any: the workgroup, one after the other (the images are shared)
-        if (level_longest[lvl] > bin_wave) {
-            __syncthreads();
-            for (int pos = first; pos < last; ++pos) {
-                const int row = perm[pos];
-                if (combined_bin(g, row) != 2) continue;
-                sweep_block_row<true>(row, g, image);
-                __syncthreads();
-            }
-        }
-        __threadfence();
-        __syncthreads();
-    }
-}
+};
 
 // ut_vals[q] = u(row, col) for the entry q of the CSC copy: col from the column pointers, row = ut_col_idxs[q]
 __global__ __launch_bounds__(block) void refresh_transposed_kernel(int32_t n, int32_t u_nnz,
@@ -678,14 +607,7 @@ extern "C" int gkomi_par_ilut_add_candidates_f64_i32(
     return check_launch();
 }
 
-extern "C" void gkomi_par_ilut_tuning(int64_t* host_out)
-{
-    if (host_out == nullptr) return;
-    host_out[0] = bin_short;
-    host_out[1] = bin_wave;
-    host_out[2] = bin_lds;
-    host_out[3] = narrow_level_rows;
-}
+extern "C" void gkomi_par_ilut_tuning(int64_t* host_out) { fill_tuning(host_out); }
 
 extern "C" size_t gkomi_par_ilut_sweep_workspace_bytes(int64_t n, int64_t l_nnz, int64_t u_nnz)
 {
@@ -751,53 +673,18 @@ extern "C" int gkomi_par_ilut_compute_l_u_factors_f64_i32(
     hipStream_t stream = to_stream(s);
     const char* ws = static_cast<const char*>(analysis_workspace);
     sweep_header sh{};
-    analysis_header h{};
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&sh, ws, sizeof(sh), hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&h, ws + l.levels, sizeof(h), hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
+    schedule sched;
+    GKOMI_TRY(load_schedule(stream, ws + l.levels, n, &sched, ws, &sh, sizeof(sh)));
     // no analysis, a failed one, or one of other factors
     if (sh.magic != sweep_magic || sh.n != n || sh.l_nnz != l_nnz || sh.u_nnz != u_nnz) return GKOMI_EINVAL;
-    if (h.magic != ws_magic || h.n != n || h.nsegments < 0 || h.nsegments > n) return GKOMI_EINVAL;
     if (n == 0) return GKOMI_SUCCESS;
-    const analysis_layout al = make_layout(n);
-    const char* lws = ws + l.levels;
-    std::vector<segment> segs(static_cast<size_t>(h.nsegments));
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(segs.data(), lws + al.segments, sizeof(segment) * segs.size(),
-                                              hipMemcpyDeviceToHost, stream)));
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-    const int32_t* perm = reinterpret_cast<const int32_t*>(lws + al.perm);
-    const int32_t* level_start = reinterpret_cast<const int32_t*>(lws + al.level_start);
-    const int32_t* level_longest = reinterpret_cast<const int32_t*>(lws + al.level_longest);
     // the sums of the rows too long for LDS live in the workspace, which the caller hands over as const: the
     // analysis owns the pattern, the numeric call its scratch
     char* scratch = const_cast<char*>(ws);
     const sweep_args g{a_row_ptrs, a_col_idxs, a_vals, l_row_ptrs, l_vals, u_row_ptrs, u_col_idxs, u_vals,
                        reinterpret_cast<const int32_t*>(ws + l.m_row_ptrs), reinterpret_cast<const int32_t*>(ws + l.m_cols),
                        reinterpret_cast<double*>(scratch + l.sums)};
-    for (const segment& sg : segs) {
-        if (sg.kind == 1) {
-            hipLaunchKernelGGL(sweep_run_kernel, dim3(1), dim3(fact_block), 0, stream, g, perm, level_start, level_longest,
-                               sg.first, sg.last);
-            continue;
-        }
-        const int64_t rows = sg.last - sg.first;
-        // one launch per bin the level holds rows of
-        if (sg.bins & 1) {
-            hipLaunchKernelGGL((sweep_level_kernel<short_width, bin_short, 0>),
-                               dim3(grid_for(rows, fact_block / short_width, max_level_grid)), dim3(fact_block), 0, stream, g,
-                               perm, sg.first, sg.last);
-        }
-        if (sg.bins & 2) {
-            hipLaunchKernelGGL((sweep_level_kernel<wave_size, bin_wave, 1>),
-                               dim3(grid_for(rows, fact_block / wave_size, max_level_grid)), dim3(fact_block), 0, stream, g,
-                               perm, sg.first, sg.last);
-        }
-        if (sg.bins & 4) {
-            hipLaunchKernelGGL(sweep_level_block_kernel, dim3(grid_for(rows, 1, max_level_grid)), dim3(fact_block), 0,
-                               stream, g, perm, sg.first, sg.last);
-        }
-    }
-    GKOMI_TRY(check_launch());
+    GKOMI_TRY(launch_schedule<sweep_rows>(stream, sched, g));
     if (refresh) {
         hipLaunchKernelGGL(refresh_transposed_kernel, dim3(grid_for(u_nnz, block)), dim3(block), 0, stream,
                            static_cast<int32_t>(n), static_cast<int32_t>(u_nnz), u_row_ptrs, u_col_idxs, u_vals, ut_row_ptrs,

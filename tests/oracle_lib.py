@@ -5,10 +5,12 @@ this.  Prototypes are parsed from the ORACLE_API definitions in oracle/*.c.
 Pointer arguments take numpy arrays (C-contiguous, right dtype) or None.
 """
 import ctypes
+import fcntl
 import glob
 import os
 import re
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -31,9 +33,17 @@ def build(force=False):
     if os.environ.get("GKO_ORACLE_LIB"):
         return LIB
     srcs = glob.glob(os.path.join(ORACLE_DIR, "*.c")) + glob.glob(os.path.join(ORACLE_DIR, "*.h"))
-    if force or not os.path.exists(LIB) or any(
-            os.path.getmtime(s) > os.path.getmtime(LIB) for s in srcs):
-        subprocess.run(["make", "-C", ORACLE_DIR], check=True, capture_output=True)
+
+    def stale():
+        return not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in srcs)
+
+    if force or stale():
+        # one build at a time: the ranks of a multi-process test all arrive here at once, and make writes the
+        # library in place; whoever waited finds it built
+        with open(os.path.join(tempfile.gettempdir(), f"gko_oracle_build_{os.getuid()}.lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            if force or stale():
+                subprocess.run(["make", "-C", ORACLE_DIR], check=True, capture_output=True)
     return LIB
 
 

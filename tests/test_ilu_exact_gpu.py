@@ -69,6 +69,12 @@ CASES = {
                                              NARROW_LEVEL_ROWS + 1, 1, 40]),
     # a wide level that holds a row longer than BIN_LDS and one longer than BIN_WAVE
     "wide_level_long_rows": lambda: xu.wide_level_with_long_rows(1300, 20, [BIN_LDS + 76, BIN_WAVE + 88]),
+    # 40 diagonal rows, then ONE level of NARROW_LEVEL_ROWS + 1 rows over them: the first with BIN_SHORT + 1 lower
+    # entries (a wave in a wide level, also once the pattern is made symmetric for IC), the others with two
+    "wide_level_wave_row": lambda: xu.from_rows(
+        [{i: 4.0 + 0.125 * i} for i in range(40)] +
+        [{**{j: -0.5 - 0.015625 * (j + r) for j in range(r, r + (BIN_SHORT + 1 if r == 0 else 2))}, 40 + r: 6.0 + r}
+         for r in range(NARROW_LEVEL_ROWS + 1)]),
     # one run of narrow levels whose widest level is neither its first nor its last
     "levels_1_5_3": lambda: xu.level_widths([1, 5, 3]),
     "n1": lambda: xu.dense_to_csr([[4.0]]),
@@ -162,6 +168,11 @@ def test_cases_reach_every_path(gk):
     m, _ = case("wide_level_long_rows", False)
     lens = np.diff(m[0])[3:23]          # the 20 rows of the wide level
     assert (lens > BIN_LDS).any() and ((lens > BIN_WAVE) & (lens <= BIN_LDS)).any() and (lens <= BIN_SHORT).any()
+    # a row for a wave in a wide level, in the pattern ILU sees and in the symmetric one IC sees
+    for ic in (False, True):
+        m, _ = case("wide_level_wave_row", ic)
+        widths, lens = level_widths_of(m), np.diff(m[0])
+        assert list(widths) == [40, NARROW_LEVEL_ROWS + 1] and BIN_SHORT < lens[40] <= BIN_WAVE and (lens[41:] <= BIN_SHORT).all()
 
 
 @pytest.mark.parametrize("ic", [False, True], ids=["ilu", "ic"])
