@@ -485,6 +485,83 @@ def ilu_from_factors(gk, n, L, U, nrhs=1, l_unit_diag=False, analyse=True, brick
     return p
 
 
+# ---- the pieces of a factorization's generate, each once -------------------------------------
+
+_CSR = (torch.int32, torch.float64)
+
+
+def _bytes(nbytes, dv):
+    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dv)
+
+
+def _empty_csr(n, nnz, dv):
+    return torch.zeros(nnz, dtype=torch.int32, device=dv), torch.zeros(nnz, dtype=torch.float64, device=dv)
+
+
+def _count_then_fill(call, counts, dv, dtypes=_CSR, always=False):
+    """The two-call idiom of the C ABI.  call(None, ...) writes the row pointers and `counts` (one ctypes.c_int64 per
+    output matrix); then one array per dtype is allocated for every count and call(*arrays) fills them, where there is
+    something to fill or `always`.  Returns the arrays."""
+    call(*[None] * (len(counts) * len(dtypes)))
+    arrays = [torch.zeros(int(c.value), dtype=t, device=dv) for c in counts for t in dtypes]
+    if always or any(c.value for c in counts):
+        call(*arrays)
+    return arrays
+
+
+def _sorted_copy(gk, n, row_ptrs, col_idxs, vals, skip_sorting):
+    """working copies of col_idxs and vals, every row sorted by column index unless skipped"""
+    ci, v = col_idxs.clone(), vals.clone()
+    if not skip_sorting:
+        s = torch.cuda.current_stream().cuda_stream
+        sorted_flag = ctypes.c_int(0)
+        fws = torch.zeros(8, dtype=torch.uint8, device=v.device)
+        gk.csr_is_sorted_by_column_index_i32(s, n, row_ptrs, ci, fws, 8, ctypes.addressof(sorted_flag))
+        if not sorted_flag.value:
+            gk.csr_sort_by_column_index_f64_i32(s, n, row_ptrs, ci, v)
+    return ci, v
+
+
+def _split_l_u(gk, n, rp, ci, v):
+    """factorization::initialize_row_ptrs_l_u + initialize_l_u -> (L, U), L with a unit diagonal"""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = v.device
+    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    urp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    sb = gk.prefix_sum_workspace_bytes(n + 1)
+    sws = _bytes(sb, dv)
+    gk.factorization_initialize_row_ptrs_l_u_i32(s, n, rp, ci, lrp, urp, sws, sb)
+    lc, lv = _empty_csr(n, int(lrp[n].item()), dv)
+    uc, uv = _empty_csr(n, int(urp[n].item()), dv)
+    gk.factorization_initialize_l_u_f64_i32(s, n, rp, ci, v, lrp, lc, lv, urp, uc, uv)
+    return (lrp, lc, lv), (urp, uc, uv)
+
+
+def _split_l(gk, n, rp, ci, v, diag_sqrt):
+    """factorization::initialize_row_ptrs_l + initialize_l -> L; diag_sqrt: store the root of the diagonal"""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = v.device
+    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    sb = gk.prefix_sum_workspace_bytes(n + 1)
+    sws = _bytes(sb, dv)
+    gk.factorization_initialize_row_ptrs_l_i32(s, n, rp, ci, lrp, sws, sb)
+    lc, lv = _empty_csr(n, int(lrp[n].item()), dv)
+    gk.factorization_initialize_l_f64_i32(s, n, rp, ci, v, lrp, lc, lv, int(diag_sqrt))
+    return lrp, lc, lv
+
+
+class _LevelAnalysis:
+    """What FactorizationAnalysis, ParIlutSweep and ParIctSweep share: the workspace one gkomi_*_analyse_i32 call
+    fills (.ws, .nbytes) and the six numbers it reports."""
+
+    def _analyse(self, gk, n, dv, nbytes, analyse, *pattern):
+        self.gk, self.n, self.nbytes = gk, n, nbytes
+        self.ws = torch.zeros(max(nbytes, 8), dtype=torch.uint8, device=dv)
+        out = (ctypes.c_int64 * 6)()
+        analyse(torch.cuda.current_stream().cuda_stream, n, *pattern, self.ws, nbytes, ctypes.addressof(out))
+        self.nlevels, self.longest_row, self.widest_level, self.launches, self.narrow_runs, self.nnz = (int(x) for x in out)
+
+
 def _with_diagonal(gk, n, row_ptrs, col_idxs, vals):
     """factorization::add_diagonal_elements on a working copy (par_ilu.cpp:93-95)"""
     s = torch.cuda.current_stream().cuda_stream
@@ -520,22 +597,14 @@ def par_ilu_generate(gk, n, row_ptrs, col_idxs, vals, iterations=0, nrhs=1):
     dv = vals.device
     rp, ci, v = _with_diagonal(gk, n, row_ptrs, col_idxs, vals)
     nnz = int(v.numel())
-    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
-    urp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
-    sb = gk.prefix_sum_workspace_bytes(n + 1)
-    sws = torch.empty(max(sb, 8), dtype=torch.uint8, device=dv)
-    gk.factorization_initialize_row_ptrs_l_u_i32(s, n, rp, ci, lrp, urp, sws, sb)
-    lnnz, unnz = int(lrp[n].item()), int(urp[n].item())
-    lc, lv = torch.zeros(lnnz, dtype=torch.int32, device=dv), torch.zeros(lnnz, dtype=torch.float64, device=dv)
-    uc, uv = torch.zeros(unnz, dtype=torch.int32, device=dv), torch.zeros(unnz, dtype=torch.float64, device=dv)
-    gk.factorization_initialize_l_u_f64_i32(s, n, rp, ci, v, lrp, lc, lv, urp, uc, uv)
-    utrp, utc, utv = _transpose(gk, n, urp, uc, uv)
+    L, U = _split_l_u(gk, n, rp, ci, v)
+    utrp, utc, utv = _transpose(gk, n, *U)
     rows = torch.zeros(max(nnz, 1), dtype=torch.int32, device=dv)
     gk.convert_ptrs_to_idxs_i32(s, rp, n, rows)
-    gk.par_ilu_compute_l_u_factors_f64_i32(s, iterations, nnz, rows, ci, v, lrp, lc, lv, utrp, utc, utv)
+    gk.par_ilu_compute_l_u_factors_f64_i32(s, iterations, nnz, rows, ci, v, *L, utrp, utc, utv)
     U = _transpose(gk, n, utrp, utc, utv)
-    p = ilu_from_factors(gk, n, (lrp, lc, lv), U, nrhs=nrhs)
-    p.L, p.U = (lrp, lc, lv), U
+    p = ilu_from_factors(gk, n, L, U, nrhs=nrhs)
+    p.L, p.U = L, U
     return p
 
 
@@ -544,14 +613,8 @@ def par_ic_generate(gk, n, row_ptrs, col_idxs, vals, iterations=0, nrhs=1):
     L^-1 then L^-T through the triangular solves; .L / .Lt hold the factors."""
     s = torch.cuda.current_stream().cuda_stream
     dv = vals.device
-    rp, ci, v = _with_diagonal(gk, n, row_ptrs, col_idxs, vals)
-    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
-    sb = gk.prefix_sum_workspace_bytes(n + 1)
-    sws = torch.empty(max(sb, 8), dtype=torch.uint8, device=dv)
-    gk.factorization_initialize_row_ptrs_l_i32(s, n, rp, ci, lrp, sws, sb)
-    lnnz = int(lrp[n].item())
-    lc, lv = torch.zeros(lnnz, dtype=torch.int32, device=dv), torch.zeros(lnnz, dtype=torch.float64, device=dv)
-    gk.factorization_initialize_l_f64_i32(s, n, rp, ci, v, lrp, lc, lv, 0)
+    lrp, lc, lv = _split_l(gk, n, *_with_diagonal(gk, n, row_ptrs, col_idxs, vals), diag_sqrt=False)
+    lnnz = int(lv.numel())
     a_vals = lv.clone()
     rows = torch.zeros(max(lnnz, 1), dtype=torch.int32, device=dv)
     gk.convert_ptrs_to_idxs_i32(s, lrp, n, rows)
@@ -565,14 +628,6 @@ def par_ic_generate(gk, n, row_ptrs, col_idxs, vals, iterations=0, nrhs=1):
 
 # ---- ParILUT (core/factorization/par_ilut.cpp:190-344) -----------------------------------------------------
 
-def _bytes(nbytes, dv):
-    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dv)
-
-
-def _empty_csr(n, nnz, dv):
-    return torch.zeros(nnz, dtype=torch.int32, device=dv), torch.zeros(nnz, dtype=torch.float64, device=dv)
-
-
 def par_ilut_spgemm(gk, n, a, b):
     """csr::spgemm of two n x n matrices (row_ptrs, col_idxs, vals)"""
     s = torch.cuda.current_stream().cuda_stream
@@ -585,11 +640,7 @@ def par_ilut_spgemm(gk, n, a, b):
     def call(cc, cv):
         gk.csr_spgemm_f64_i32(s, n, n, int(a[2].numel()), a[0], a[1], a[2], n, n, int(b[2].numel()), b[0], b[1], b[2],
                               None, None, 0, 0, 0, None, None, None, crp, cc, cv, ctypes.addressof(cnnz), ws, nb)
-    call(None, None)
-    cc, cv = _empty_csr(n, int(cnnz.value), dv)
-    if cnnz.value:
-        call(cc, cv)
-    return crp, cc, cv
+    return (crp, *_count_then_fill(call, [cnnz], dv))
 
 
 def par_ilut_add_candidates(gk, n, lu, a, l, u):
@@ -605,11 +656,7 @@ def par_ilut_add_candidates(gk, n, lu, a, l, u):
     def call(lc, lv, uc, uv):
         gk.par_ilut_add_candidates_f64_i32(s, n, *lu, *a, *l, *u, lrp, lc, lv, urp, uc, uv, ctypes.addressof(lnnz),
                                            ctypes.addressof(unnz), ws, nb)
-    call(None, None, None, None)
-    lc, lv = _empty_csr(n, int(lnnz.value), dv)
-    uc, uv = _empty_csr(n, int(unnz.value), dv)
-    if n:
-        call(lc, lv, uc, uv)
+    lc, lv, uc, uv = _count_then_fill(call, [lnnz, unnz], dv, always=n > 0)
     return (lrp, lc, lv), (urp, uc, uv)
 
 
@@ -633,6 +680,12 @@ def par_ilut_threshold_approx(gk, vals, rank):
     return out.value
 
 
+def _threshold(gk, vals, nnz_limit, approximate_select):
+    """the magnitude below which entries of a candidate factor are dropped so that about nnz_limit remain"""
+    rank = max(0, int(vals.numel()) - nnz_limit - 1)
+    return (par_ilut_threshold_approx if approximate_select else par_ilut_threshold_select)(gk, vals, rank)
+
+
 def par_ilut_threshold_filter(gk, n, m, threshold, with_coo=False):
     """par_ilut_factorization::threshold_filter -> (row_ptrs, col_idxs, vals) [, COO row indices]"""
     s = torch.cuda.current_stream().cuda_stream
@@ -641,33 +694,38 @@ def par_ilut_threshold_filter(gk, n, m, threshold, with_coo=False):
     ws = _bytes(nb, dv)
     nrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
     nnz = ctypes.c_int64(0)
-    gk.par_ilut_threshold_filter_f64_i32(s, n, *m, threshold, nrp, None, None, None, ctypes.addressof(nnz), ws, nb)
-    nc, nv = _empty_csr(n, int(nnz.value), dv)
-    rows = torch.zeros(int(nnz.value), dtype=torch.int32, device=dv) if with_coo else None
-    if nnz.value:
+
+    def call(nc, nv, rows=None):
         gk.par_ilut_threshold_filter_f64_i32(s, n, *m, threshold, nrp, nc, nv, rows, ctypes.addressof(nnz), ws, nb)
-    return ((nrp, nc, nv), rows) if with_coo else (nrp, nc, nv)
+    nc, nv, *rows = _count_then_fill(call, [nnz], dv, dtypes=_CSR + (torch.int32,) if with_coo else _CSR)
+    return ((nrp, nc, nv), rows[0]) if with_coo else (nrp, nc, nv)
 
 
-class ParIlutSweep:
+class ParIlutSweep(_LevelAnalysis):
     """gkomi_par_ilut_analyse_i32 of one pair of patterns (L', U'); .compute runs the exact sweep
     (par_ilut_factorization::compute_l_u_factors with the reference executor's result) in place."""
 
     def __init__(self, gk, n, l, u):
-        self.gk, self.n, self.l, self.u = gk, n, l, u
+        self.l, self.u = l, u
         self.l_nnz, self.u_nnz = int(l[2].numel()), int(u[2].numel())
-        self.nbytes = gk.par_ilut_sweep_workspace_bytes(n, self.l_nnz, self.u_nnz)
-        self.ws = torch.zeros(max(self.nbytes, 8), dtype=torch.uint8, device=l[2].device)
-        out = (ctypes.c_int64 * 6)()
-        gk.par_ilut_analyse_i32(torch.cuda.current_stream().cuda_stream, n, self.l_nnz, l[0], l[1], self.u_nnz, u[0], u[1],
-                                self.ws, self.nbytes, ctypes.addressof(out))
-        self.nlevels, self.longest_row, self.widest_level, self.launches, self.narrow_runs, self.nnz = (int(x) for x in out)
+        self._analyse(gk, n, l[2].device, gk.par_ilut_sweep_workspace_bytes(n, self.l_nnz, self.u_nnz),
+                      gk.par_ilut_analyse_i32, self.l_nnz, l[0], l[1], self.u_nnz, u[0], u[1])
 
     def compute(self, a, u_csc=None):
         """u_csc: the CSC copy of U, whose values are brought up to date"""
         ut = u_csc if u_csc is not None else (None, None, None)
         self.gk.par_ilut_compute_l_u_factors_f64_i32(torch.cuda.current_stream().cuda_stream, self.n, *a, self.l_nnz, *self.l,
                                                      self.u_nnz, *self.u, *ut, self.ws, self.nbytes)
+
+
+def _check_threshold_generate(who, n, row_ptrs, ncols, fill_in_limit):
+    """GKO_ASSERT_IS_SQUARE_MATRIX and the fill_in_limit check, before anything reaches the device"""
+    if ncols is not None and ncols != n:
+        raise ValueError(f"{who} needs a square matrix, got {n} x {ncols}")
+    if int(row_ptrs.numel()) != n + 1:
+        raise ValueError(f"{who} needs a square matrix: {int(row_ptrs.numel()) - 1} rows of row pointers for n = {n}")
+    if not fill_in_limit > 0.0:
+        raise ValueError(f"fill_in_limit must be positive, got {fill_in_limit}")
 
 
 def par_ilut_generate(gk, n, row_ptrs, col_idxs, vals, iterations=5, fill_in_limit=2.0, approximate_select=True,
@@ -678,34 +736,10 @@ def par_ilut_generate(gk, n, row_ptrs, col_idxs, vals, iterations=5, fill_in_lim
     dependency levels of every sweep.
     The CSC copy of U' exists only where its order matters: the approximate selection samples it.  The exact
     selection does not depend on the order of the values, and the second sweep reads U by rows."""
-    # GKO_ASSERT_IS_SQUARE_MATRIX and the fill_in_limit check, before anything reaches the device
-    if ncols is not None and ncols != n:
-        raise ValueError(f"ParIlut needs a square matrix, got {n} x {ncols}")
-    if int(row_ptrs.numel()) != n + 1:
-        raise ValueError(f"ParIlut needs a square matrix: {int(row_ptrs.numel()) - 1} rows of row pointers for n = {n}")
-    if not fill_in_limit > 0.0:
-        raise ValueError(f"fill_in_limit must be positive, got {fill_in_limit}")
-    s = torch.cuda.current_stream().cuda_stream
-    dv = vals.device
-    ci, v = col_idxs.clone(), vals.clone()
-    if not skip_sorting:
-        sorted_flag = ctypes.c_int(0)
-        fws = torch.zeros(8, dtype=torch.uint8, device=dv)
-        gk.csr_is_sorted_by_column_index_i32(s, n, row_ptrs, ci, fws, 8, ctypes.addressof(sorted_flag))
-        if not sorted_flag.value:
-            gk.csr_sort_by_column_index_f64_i32(s, n, row_ptrs, ci, v)
-    a = (row_ptrs, ci, v)
-    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
-    urp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
-    sb = gk.prefix_sum_workspace_bytes(n + 1)
-    sws = _bytes(sb, dv)
-    gk.factorization_initialize_row_ptrs_l_u_i32(s, n, row_ptrs, ci, lrp, urp, sws, sb)
-    lnnz, unnz = int(lrp[n].item()), int(urp[n].item())
-    lc, lv = _empty_csr(n, lnnz, dv)
-    uc, uv = _empty_csr(n, unnz, dv)
-    gk.factorization_initialize_l_u_f64_i32(s, n, row_ptrs, ci, v, lrp, lc, lv, urp, uc, uv)
-    l, u = (lrp, lc, lv), (urp, uc, uv)
-    l_nnz_limit, u_nnz_limit = int(lnnz * fill_in_limit), int(unnz * fill_in_limit)
+    _check_threshold_generate("ParIlut", n, row_ptrs, ncols, fill_in_limit)
+    a = (row_ptrs, *_sorted_copy(gk, n, row_ptrs, col_idxs, vals, skip_sorting))
+    l, u = _split_l_u(gk, n, *a)
+    l_nnz_limit, u_nnz_limit = int(int(l[2].numel()) * fill_in_limit), int(int(u[2].numel()) * fill_in_limit)
     levels = []
     for _ in range(iterations):
         lu = par_ilut_spgemm(gk, n, l, u)
@@ -714,14 +748,8 @@ def par_ilut_generate(gk, n, row_ptrs, col_idxs, vals, iterations=5, fill_in_lim
         sweep = ParIlutSweep(gk, n, l_new, u_new)
         sweep.compute(a, u_new_csc)
         levels.append(sweep.nlevels)
-        l_rank = max(0, int(l_new[2].numel()) - l_nnz_limit - 1)
-        u_rank = max(0, int(u_new[2].numel()) - u_nnz_limit - 1)
-        if approximate_select:
-            l_threshold = par_ilut_threshold_approx(gk, l_new[2], l_rank)
-            u_threshold = par_ilut_threshold_approx(gk, u_new_csc[2], u_rank)
-        else:
-            l_threshold = par_ilut_threshold_select(gk, l_new[2], l_rank)
-            u_threshold = par_ilut_threshold_select(gk, u_new[2], u_rank)
+        l_threshold = _threshold(gk, l_new[2], l_nnz_limit, approximate_select)
+        u_threshold = _threshold(gk, (u_new_csc if approximate_select else u_new)[2], u_nnz_limit, approximate_select)
         l = par_ilut_threshold_filter(gk, n, l_new, l_threshold)
         u = par_ilut_threshold_filter(gk, n, u_new, u_threshold)
         sweep = ParIlutSweep(gk, n, l, u)
@@ -742,26 +770,21 @@ def par_ict_add_candidates(gk, n, llh, a, l):
     ws = _bytes(nb, dv)
     lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
     lnnz = ctypes.c_int64(0)
-    gk.par_ict_add_candidates_f64_i32(s, n, *llh, *a, *l, lrp, None, None, ctypes.addressof(lnnz), ws, nb)
-    lc, lv = _empty_csr(n, int(lnnz.value), dv)
-    if n:
+
+    def call(lc, lv):
         gk.par_ict_add_candidates_f64_i32(s, n, *llh, *a, *l, lrp, lc, lv, ctypes.addressof(lnnz), ws, nb)
-    return lrp, lc, lv
+    return (lrp, *_count_then_fill(call, [lnnz], dv, always=n > 0))
 
 
-class ParIctSweep:
+class ParIctSweep(_LevelAnalysis):
     """gkomi_par_ict_analyse_i32 of one pattern L'; .compute runs the exact sweep
     (par_ict_factorization::compute_factor with the reference executor's result) in place."""
 
     def __init__(self, gk, n, l):
-        self.gk, self.n, self.l = gk, n, l
+        self.l = l
         self.l_nnz = int(l[2].numel())
-        self.nbytes = gk.par_ict_sweep_workspace_bytes(n, self.l_nnz)
-        self.ws = torch.zeros(max(self.nbytes, 8), dtype=torch.uint8, device=l[2].device)
-        out = (ctypes.c_int64 * 6)()
-        gk.par_ict_analyse_i32(torch.cuda.current_stream().cuda_stream, n, self.l_nnz, l[0], l[1], self.ws, self.nbytes,
-                               ctypes.addressof(out))
-        self.nlevels, self.longest_row, self.widest_level, self.launches, self.narrow_runs, self.nnz = (int(x) for x in out)
+        self._analyse(gk, n, l[2].device, gk.par_ict_sweep_workspace_bytes(n, self.l_nnz), gk.par_ict_analyse_i32,
+                      self.l_nnz, l[0], l[1])
 
     def compute(self, a):
         self.gk.par_ict_compute_factor_f64_i32(torch.cuda.current_stream().cuda_stream, self.n, *a, self.l_nnz, *self.l,
@@ -774,33 +797,11 @@ def par_ict_generate(gk, n, row_ptrs, col_idxs, vals, iterations=5, fill_in_limi
     reference executor bit for bit: sort, initialize_l with the root of the diagonal, then per iteration spgemm(L, L^T),
     add_candidates, sweep, threshold selection on L' in CSR order and filter, sweep, transpose.  Returns the
     Preconditioner (L^-1 then L^-T); .L / .Lt hold the factors, .levels the number of dependency levels of every sweep."""
-    # GKO_ASSERT_IS_SQUARE_MATRIX and the fill_in_limit check, before anything reaches the device
-    if ncols is not None and ncols != n:
-        raise ValueError(f"ParIct needs a square matrix, got {n} x {ncols}")
-    if int(row_ptrs.numel()) != n + 1:
-        raise ValueError(f"ParIct needs a square matrix: {int(row_ptrs.numel()) - 1} rows of row pointers for n = {n}")
-    if not fill_in_limit > 0.0:
-        raise ValueError(f"fill_in_limit must be positive, got {fill_in_limit}")
-    s = torch.cuda.current_stream().cuda_stream
-    dv = vals.device
-    ci, v = col_idxs.clone(), vals.clone()
-    if not skip_sorting:
-        sorted_flag = ctypes.c_int(0)
-        fws = torch.zeros(8, dtype=torch.uint8, device=dv)
-        gk.csr_is_sorted_by_column_index_i32(s, n, row_ptrs, ci, fws, 8, ctypes.addressof(sorted_flag))
-        if not sorted_flag.value:
-            gk.csr_sort_by_column_index_f64_i32(s, n, row_ptrs, ci, v)
-    a = (row_ptrs, ci, v)
-    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
-    sb = gk.prefix_sum_workspace_bytes(n + 1)
-    sws = _bytes(sb, dv)
-    gk.factorization_initialize_row_ptrs_l_i32(s, n, row_ptrs, ci, lrp, sws, sb)
-    lnnz = int(lrp[n].item())
-    lc, lv = _empty_csr(n, lnnz, dv)
-    gk.factorization_initialize_l_f64_i32(s, n, row_ptrs, ci, v, lrp, lc, lv, 1)
-    l = (lrp, lc, lv)
+    _check_threshold_generate("ParIct", n, row_ptrs, ncols, fill_in_limit)
+    a = (row_ptrs, *_sorted_copy(gk, n, row_ptrs, col_idxs, vals, skip_sorting))
+    l = _split_l(gk, n, *a, diag_sqrt=True)
     lt = _transpose(gk, n, *l)
-    l_nnz_limit = int(lnnz * fill_in_limit)
+    l_nnz_limit = int(int(l[2].numel()) * fill_in_limit)
     levels = []
     for _ in range(iterations):
         llh = par_ilut_spgemm(gk, n, l, lt)
@@ -808,12 +809,7 @@ def par_ict_generate(gk, n, row_ptrs, col_idxs, vals, iterations=5, fill_in_limi
         sweep = ParIctSweep(gk, n, l_new)
         sweep.compute(a)
         levels.append(sweep.nlevels)
-        rank = max(0, int(l_new[2].numel()) - l_nnz_limit - 1)
-        if approximate_select:
-            threshold = par_ilut_threshold_approx(gk, l_new[2], rank)
-        else:
-            threshold = par_ilut_threshold_select(gk, l_new[2], rank)
-        l = par_ilut_threshold_filter(gk, n, l_new, threshold)
+        l = par_ilut_threshold_filter(gk, n, l_new, _threshold(gk, l_new[2], l_nnz_limit, approximate_select))
         sweep = ParIctSweep(gk, n, l)
         sweep.compute(a)
         levels.append(sweep.nlevels)
@@ -823,18 +819,12 @@ def par_ict_generate(gk, n, row_ptrs, col_idxs, vals, iterations=5, fill_in_limi
     return p
 
 
-class FactorizationAnalysis:
+class FactorizationAnalysis(_LevelAnalysis):
     """gkomi_ilu_analyse_i32: diagonal positions, dependency levels and the launch list of the exact ILU(0) / IC(0)
     of one sparsity pattern (sorted rows, diagonal stored); reusable for any number of numeric calls."""
 
     def __init__(self, gk, n, row_ptrs, col_idxs):
-        self.gk, self.n = gk, n
-        self.nbytes = gk.ilu_analysis_workspace_bytes(n)
-        self.ws = torch.zeros(max(self.nbytes, 8), dtype=torch.uint8, device=row_ptrs.device)
-        out = (ctypes.c_int64 * 6)()
-        gk.ilu_analyse_i32(torch.cuda.current_stream().cuda_stream, n, row_ptrs, col_idxs, self.ws, self.nbytes,
-                           ctypes.addressof(out))
-        self.nlevels, self.longest_row, self.widest_level, self.launches, self.narrow_runs, self.nnz = (int(x) for x in out)
+        self._analyse(gk, n, row_ptrs.device, gk.ilu_analysis_workspace_bytes(n), gk.ilu_analyse_i32, row_ptrs, col_idxs)
 
     def compute_lu(self, row_ptrs, col_idxs, vals):
         self.gk.ilu_compute_lu_f64_i32(torch.cuda.current_stream().cuda_stream, self.n, row_ptrs, col_idxs, vals,
@@ -845,61 +835,33 @@ class FactorizationAnalysis:
                                    self.nbytes)
 
 
-def _sorted_with_diagonal(gk, n, row_ptrs, col_idxs, vals, skip_sorting):
-    """sort_by_column_index unless skipped, then add_diagonal_elements, on a working copy
-    (core/factorization/ilu.cpp:80-86)"""
-    ci, v = col_idxs.clone(), vals.clone()
-    if not skip_sorting:
-        sorted_flag = ctypes.c_int(0)
-        s = torch.cuda.current_stream().cuda_stream
-        ws = torch.zeros(8, dtype=torch.uint8, device=v.device)
-        gk.csr_is_sorted_by_column_index_i32(s, n, row_ptrs, ci, ws, 8, ctypes.addressof(sorted_flag))
-        if not sorted_flag.value:
-            gk.csr_sort_by_column_index_f64_i32(s, n, row_ptrs, ci, v)
-    rp, ci2, v2 = _with_diagonal(gk, n, row_ptrs, ci, v)
-    return rp, ci2, v2
+def _exact_working_copy(gk, n, row_ptrs, col_idxs, vals, skip_sorting):
+    """sort_by_column_index unless skipped, then add_diagonal_elements, on a working copy (core/factorization/ilu.cpp:80-86),
+    and its level analysis"""
+    rp, ci, v = _with_diagonal(gk, n, row_ptrs, *_sorted_copy(gk, n, row_ptrs, col_idxs, vals, skip_sorting))
+    return rp, ci, v, FactorizationAnalysis(gk, n, rp, ci)
 
 
 def ilu_generate(gk, n, row_ptrs, col_idxs, vals, nrhs=1, skip_sorting=False):
     """preconditioner::Ilu over factorization::Ilu, the exact ILU(0) (core/factorization/ilu.cpp:67-124): sort,
     add_diagonal_elements, compute_lu, initialize_l_u.  .L / .U hold the factors, .analysis the level analysis."""
-    s = torch.cuda.current_stream().cuda_stream
-    dv = vals.device
-    rp, ci, v = _sorted_with_diagonal(gk, n, row_ptrs, col_idxs, vals, skip_sorting)
-    an = FactorizationAnalysis(gk, n, rp, ci)
+    rp, ci, v, an = _exact_working_copy(gk, n, row_ptrs, col_idxs, vals, skip_sorting)
     an.compute_lu(rp, ci, v)
-    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
-    urp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
-    sb = gk.prefix_sum_workspace_bytes(n + 1)
-    sws = torch.empty(max(sb, 8), dtype=torch.uint8, device=dv)
-    gk.factorization_initialize_row_ptrs_l_u_i32(s, n, rp, ci, lrp, urp, sws, sb)
-    lnnz, unnz = int(lrp[n].item()), int(urp[n].item())
-    lc, lv = torch.zeros(lnnz, dtype=torch.int32, device=dv), torch.zeros(lnnz, dtype=torch.float64, device=dv)
-    uc, uv = torch.zeros(unnz, dtype=torch.int32, device=dv), torch.zeros(unnz, dtype=torch.float64, device=dv)
-    gk.factorization_initialize_l_u_f64_i32(s, n, rp, ci, v, lrp, lc, lv, urp, uc, uv)
-    p = ilu_from_factors(gk, n, (lrp, lc, lv), (urp, uc, uv), nrhs=nrhs)
-    p.L, p.U, p.analysis = (lrp, lc, lv), (urp, uc, uv), an
+    L, U = _split_l_u(gk, n, rp, ci, v)
+    p = ilu_from_factors(gk, n, L, U, nrhs=nrhs)
+    p.L, p.U, p.analysis = L, U, an
     return p
 
 
 def ic_generate(gk, n, row_ptrs, col_idxs, vals, nrhs=1, skip_sorting=False):
     """preconditioner::Ic over factorization::Ic, the exact IC(0) (core/factorization/ic.cpp:67-120): sort,
     add_diagonal_elements, compute, initialize_l, L^T.  .L / .Lt hold the factors."""
-    s = torch.cuda.current_stream().cuda_stream
-    dv = vals.device
-    rp, ci, v = _sorted_with_diagonal(gk, n, row_ptrs, col_idxs, vals, skip_sorting)
-    an = FactorizationAnalysis(gk, n, rp, ci)
+    rp, ci, v, an = _exact_working_copy(gk, n, row_ptrs, col_idxs, vals, skip_sorting)
     an.ic_compute(rp, ci, v)
-    lrp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
-    sb = gk.prefix_sum_workspace_bytes(n + 1)
-    sws = torch.empty(max(sb, 8), dtype=torch.uint8, device=dv)
-    gk.factorization_initialize_row_ptrs_l_i32(s, n, rp, ci, lrp, sws, sb)
-    lnnz = int(lrp[n].item())
-    lc, lv = torch.zeros(lnnz, dtype=torch.int32, device=dv), torch.zeros(lnnz, dtype=torch.float64, device=dv)
-    gk.factorization_initialize_l_f64_i32(s, n, rp, ci, v, lrp, lc, lv, 0)
-    Lt = _transpose(gk, n, lrp, lc, lv)
-    p = ilu_from_factors(gk, n, (lrp, lc, lv), Lt, nrhs=nrhs)
-    p.L, p.Lt, p.analysis = (lrp, lc, lv), Lt, an
+    L = _split_l(gk, n, rp, ci, v, diag_sqrt=False)
+    Lt = _transpose(gk, n, *L)
+    p = ilu_from_factors(gk, n, L, Lt, nrhs=nrhs)
+    p.L, p.Lt, p.analysis = L, Lt, an
     return p
 
 
@@ -953,11 +915,7 @@ def symbolic_cholesky(gk, n, row_ptrs, col_idxs, forest=None):
     def spgeam(cc, cv):
         gk.csr_spgeam_f64_i32(s, n, n, one, lnnz, trp, tc, tv, one, n, n, lnnz, lrp, lc, lv, crp, cc, cv,
                               ctypes.addressof(cnnz), gws, gb)
-    spgeam(None, None)
-    cc = torch.zeros(int(cnnz.value), dtype=torch.int32, device=dv)
-    cv = torch.zeros(int(cnnz.value), dtype=torch.float64, device=dv)
-    if cnnz.value:
-        spgeam(cc, cv)
+    cc, cv = _count_then_fill(spgeam, [cnnz], dv)
     return (lrp, lc, lv), (crp, cc, cv)
 
 

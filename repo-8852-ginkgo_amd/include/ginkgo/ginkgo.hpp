@@ -2839,138 +2839,283 @@ template <typename V = double, typename I = int32>
 using UpperTrs = Trs<false, V, I>;
 }  // namespace solver
 
-// ---- ParILU + Ilu (core/factorization/par_ilu.cpp:74-163, preconditioner/ilu.hpp:265-305) ------
+// ---- the factorizations: ParIlu, Ilu, Ic, ParIlut, ParIc, ParIct ---------------------------------------------------
+// (core/factorization/par_ilu.cpp:74-163, ilu.cpp:67-124, ic.cpp:67-120, par_ilut.cpp:190-344, par_ic.cpp:70-145,
+// par_ict.cpp:174-292)
 namespace factorization {
+// The pieces of a generate chain, each once.  A helper that is handed its workspace launches and returns: the caller
+// keeps the workspace alive and hoists it out of its loop.  A helper that owns its workspace ends in a blocking read of
+// a count, or synchronizes before the workspace leaves scope.
+namespace detail {
+using ::gko::detail::require_device;
+
+// a square CSR matrix as its three arrays
+template <typename V, typename I>
+struct csr_arrays {
+    array<I> rp, ci;
+    array<V> v;
+    csr_arrays() = default;
+    csr_arrays(const std::shared_ptr<const Executor>& exec, size_type n, size_type nnz = 0) : rp(exec, n + 1), ci(exec, nnz), v(exec, nnz) {}
+    int64_t nnz() const { return static_cast<int64_t>(v.get_num_elems()); }
+    // fresh col_idxs and vals of nnz entries under the row pointers there are
+    void resize(size_type nnz)
+    {
+        ci = array<I>(rp.get_executor(), nnz);
+        v = array<V>(rp.get_executor(), nnz);
+    }
+    std::shared_ptr<matrix::Csr<V, I>> to_csr(std::shared_ptr<typename matrix::Csr<V, I>::strategy_type> strategy = nullptr) &&
+    {
+        const size_type n = rp.get_num_elems() - 1;
+        std::shared_ptr<matrix::Csr<V, I>> m = matrix::Csr<V, I>::create(rp.get_executor());
+        m->adopt(dim<2>(n, n), std::move(rp), std::move(ci), std::move(v));
+        if (strategy) m->set_strategy(std::move(strategy));
+        return m;
+    }
+};
+
+// what the kernels read of a csr_arrays or a matrix::Csr
+template <typename V, typename I>
+struct csr_view {
+    csr_view(const csr_arrays<V, I>& m) : n(m.rp.get_num_elems() - 1), nnz(m.nnz()), rp(m.rp.get_const_data()), ci(m.ci.get_const_data()), v(m.v.get_const_data()) {}
+    csr_view(const matrix::Csr<V, I>* m)
+        : n(m->get_size()[0]), nnz(static_cast<int64_t>(m->get_num_stored_elements())), rp(m->get_const_row_ptrs()), ci(m->get_const_col_idxs()), v(m->get_const_values())
+    {}
+    size_type n;
+    int64_t nnz;
+    const I* rp;
+    const I* ci;
+    const V* v;
+};
+
+// the matrix a generate reads: a Csr on the device, square, its rows sorted by column index where asked
+template <typename V, typename I>
+struct source {
+    source(const std::shared_ptr<const Executor>& exec, const LinOp* A, const char* kernel, const std::string& who, bool sort)
+    {
+        static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "the factorizations are <double, int32>");
+        require_device(exec, kernel);
+        mtx = as<const matrix::Csr<V, I>>(A);
+        n = mtx->get_size()[0];
+        if (n != mtx->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, who + " needs a square matrix");
+        if (sort && !mtx->is_sorted_by_column_index()) {
+            matrix_data<V, I> d;
+            mtx->write(d);
+            sorted_ = matrix::Csr<V, I>::create(exec);
+            sorted_->read(d);
+            sorted_->sort_by_column_index();
+            mtx = sorted_.get();
+        }
+    }
+    const matrix::Csr<V, I>* mtx;
+    size_type n;
+private:
+    std::unique_ptr<matrix::Csr<V, I>> sorted_;
+};
+
+// factorization::add_diagonal_elements on a copy; ws: gkomi_factorization_workspace_bytes(n)
+template <typename V, typename I>
+csr_arrays<V, I> with_diagonal(const std::shared_ptr<const Executor>& exec, const matrix::Csr<V, I>* src, array<char>& ws)
+{
+    const size_type n = src->get_size()[0], nnz = src->get_num_stored_elements();
+    csr_arrays<V, I> w(exec, n);
+    exec->copy(n + 1, src->get_const_row_ptrs(), w.rp.get_data());
+    int64_t missing = 0;
+    GKOMI_CALL(gkomi_factorization_count_missing_diagonal_i32(nullptr, n, n, w.rp.get_const_data(), src->get_const_col_idxs(), ws.get_data(), ws.get_num_elems(), &missing));
+    w.resize(nnz + missing);
+    if (missing) {
+        GKOMI_CALL(gkomi_factorization_add_diagonal_elements_f64_i32(nullptr, n, n, w.rp.get_data(), src->get_const_col_idxs(), src->get_const_values(), w.ci.get_data(), w.v.get_data(), ws.get_const_data()));
+    } else {
+        exec->copy(nnz, src->get_const_col_idxs(), w.ci.get_data());
+        exec->copy(nnz, src->get_const_values(), w.v.get_data());
+    }
+    return w;
+}
+
+// factorization::initialize_row_ptrs_l_u + initialize_l_u: (L with a unit diagonal, U)
+template <typename V, typename I>
+std::pair<csr_arrays<V, I>, csr_arrays<V, I>> split_l_u(const std::shared_ptr<const Executor>& exec, csr_view<V, I> a)
+{
+    const size_type n = a.n;
+    csr_arrays<V, I> l(exec, n), u(exec, n);
+    {   // the scan's workspace goes while the stream is idle behind the blocking reads, not behind the launch below
+        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
+        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_u_i32(nullptr, n, a.rp, a.ci, l.rp.get_data(), u.rp.get_data(), sws.get_data(), sws.get_num_elems()));
+        const size_type lnnz = exec->copy_val_to_host(l.rp.get_const_data() + n), unnz = exec->copy_val_to_host(u.rp.get_const_data() + n);
+        l.resize(lnnz);
+        u.resize(unnz);
+    }
+    GKOMI_CALL(gkomi_factorization_initialize_l_u_f64_i32(nullptr, n, a.rp, a.ci, a.v, l.rp.get_const_data(), l.ci.get_data(), l.v.get_data(), u.rp.get_const_data(), u.ci.get_data(), u.v.get_data()));
+    return {std::move(l), std::move(u)};
+}
+
+// factorization::initialize_row_ptrs_l + initialize_l; diag_sqrt: the root of the diagonal is stored
+template <typename V, typename I>
+csr_arrays<V, I> split_l(const std::shared_ptr<const Executor>& exec, csr_view<V, I> a, bool diag_sqrt)
+{
+    const size_type n = a.n;
+    csr_arrays<V, I> l(exec, n);
+    {   // as in split_l_u
+        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
+        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_i32(nullptr, n, a.rp, a.ci, l.rp.get_data(), sws.get_data(), sws.get_num_elems()));
+        l.resize(exec->copy_val_to_host(l.rp.get_const_data() + n));
+    }
+    GKOMI_CALL(gkomi_factorization_initialize_l_f64_i32(nullptr, n, a.rp, a.ci, a.v, l.rp.get_const_data(), l.ci.get_data(), l.v.get_data(), diag_sqrt ? 1 : 0));
+    return l;
+}
+
+// out = m^T into arrays of m's sizes; ws: gkomi_csr_transpose_workspace_bytes(n)
+template <typename V, typename I>
+void transpose_into(csr_view<V, I> m, csr_arrays<V, I>& out, array<char>& ws)
+{
+    GKOMI_CALL(gkomi_csr_transpose_f64_i32(nullptr, m.n, m.n, m.nnz, m.rp, m.ci, m.v, out.rp.get_data(), out.ci.get_data(), out.v.get_data(), ws.get_data(), ws.get_num_elems()));
+}
+
+// m^T; without a workspace of the caller's it brings its own and waits for the transpose
+template <typename V, typename I>
+csr_arrays<V, I> transposed(const std::shared_ptr<const Executor>& exec, csr_view<V, I> m, array<char>* ws = nullptr)
+{
+    csr_arrays<V, I> out(exec, m.n, m.nnz);
+    if (ws != nullptr) {
+        transpose_into(m, out, *ws);
+    } else {
+        array<char> own(exec, gkomi_csr_transpose_workspace_bytes(m.n));
+        transpose_into(m, out, own);
+        exec->synchronize();  // the workspace leaves scope
+    }
+    return out;
+}
+
+// csr::spgemm a b, count then fill; ws: gkomi_csr_spgemm_workspace_bytes(n, n)
+template <typename V, typename I>
+csr_arrays<V, I> spgemm(const std::shared_ptr<const Executor>& exec, csr_view<V, I> a, csr_view<V, I> b, array<char>& ws)
+{
+    const size_type n = a.n;
+    csr_arrays<V, I> c(exec, n);
+    int64_t nnz = 0;
+    auto call = [&] {
+        GKOMI_CALL(gkomi_csr_spgemm_f64_i32(nullptr, n, n, a.nnz, a.rp, a.ci, a.v, n, n, b.nnz, b.rp, b.ci, b.v, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, c.rp.get_data(), c.ci.get_data(),
+                                            c.v.get_data(), &nnz, ws.get_data(), ws.get_num_elems()));
+    };
+    call();
+    c.resize(nnz);
+    if (nnz > 0) call();
+    return c;
+}
+
+// par_ilut_factorization::threshold_filter: the reference executor's keeps |v| >= threshold || col == row whatever its `lower` flag says
+template <typename V, typename I>
+csr_arrays<V, I> filtered(const std::shared_ptr<const Executor>& exec, csr_view<V, I> m, double threshold)
+{
+    csr_arrays<V, I> out(exec, m.n);
+    array<char> ws(exec, gkomi_par_ilut_filter_workspace_bytes(m.n));
+    int64_t nnz = 0;
+    auto call = [&] {
+        GKOMI_CALL(gkomi_par_ilut_threshold_filter_f64_i32(nullptr, m.n, m.rp, m.ci, m.v, threshold, out.rp.get_data(), out.ci.get_data(), out.v.get_data(), nullptr, &nnz, ws.get_data(), ws.get_num_elems()));
+    };
+    call();
+    out.resize(nnz);
+    call();
+    return out;
+}
+
+// the magnitude of a rank among the values of a candidate factor: the sampled selection of threshold_filter_approx or
+// the exact threshold_select, 0 without a launch for n == 0.  One workspace for the thresholds of one iteration.
+template <typename V>
+class threshold {
+public:
+    threshold(const std::shared_ptr<const Executor>& exec, size_type n, bool approximate, int64_t max_nnz)
+        : skip_(n == 0), approximate_(approximate), ws_(exec, skip_ ? 0 : (approximate ? gkomi_par_ilut_approx_workspace_bytes() : gkomi_par_ilut_select_workspace_bytes(max_nnz)))
+    {}
+    double operator()(const array<V>& vals, int64_t rank)
+    {
+        double t = 0.0;
+        if (skip_) return t;
+        auto select = approximate_ ? gkomi_par_ilut_threshold_approx_f64 : gkomi_par_ilut_threshold_select_f64;
+        GKOMI_CALL(select(nullptr, static_cast<int64_t>(vals.get_num_elems()), vals.get_const_data(), rank, ws_.get_data(), ws_.get_num_elems(), &t));
+        return t;
+    }
+private:
+    bool skip_, approximate_;
+    array<char> ws_;
+};
+
+// on(), generate() and the executor of a factorization's Factory; the class itself keeps build(), its with_* and getters
+template <typename Fact>
+class factory_base {
+public:
+    std::shared_ptr<typename Fact::Factory> on(std::shared_ptr<const Executor> exec) const
+    {
+        auto f = std::make_shared<typename Fact::Factory>(static_cast<const typename Fact::Factory&>(*this));
+        f->exec_ = std::move(exec);
+        return f;
+    }
+    std::unique_ptr<Fact> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Fact>(new Fact(static_cast<const typename Fact::Factory&>(*this), std::move(A))); }
+    std::shared_ptr<const Executor> exec_;
+};
+
+// the working copy both exact chains factorize: sorted unless skipped, explicit diagonal, then gkomi_ilu_analyse_i32
+// + the numeric phase in place
+template <typename V, typename I>
+csr_arrays<V, I> exact_factorized(const std::shared_ptr<const Executor>& exec, const LinOp* A, bool skip_sorting, bool ic, const char* who)
+{
+    source<V, I> src(exec, A, who, who, !skip_sorting);
+    const size_type n = src.n;
+    array<char> fws(exec, gkomi_factorization_workspace_bytes(n));
+    auto w = with_diagonal(exec, src.mtx, fws);
+    array<char> aws(exec, gkomi_ilu_analysis_workspace_bytes(n));
+    int64_t info[6] = {};
+    GKOMI_CALL(gkomi_ilu_analyse_i32(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), aws.get_data(), aws.get_num_elems(), info));
+    auto compute = ic ? gkomi_ic_compute_f64_i32 : gkomi_ilu_compute_lu_f64_i32;
+    GKOMI_CALL(compute(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), w.v.get_data(), aws.get_const_data(), aws.get_num_elems()));
+    exec->synchronize();  // the workspaces leave scope
+    return w;
+}
+}  // namespace detail
+
 template <typename V = double, typename I = int32>
 class ParIlu {
 public:
     using matrix_type = matrix::Csr<V, I>;
-    class Factory {
+    class Factory : public detail::factory_base<ParIlu> {
     public:
         Factory& with_iterations(size_type n) { iterations_ = n; return *this; }
         Factory& with_skip_sorting(bool) { return *this; }
-        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
-        std::unique_ptr<ParIlu> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<ParIlu>(new ParIlu(exec_, iterations_, std::move(A))); }
-        std::shared_ptr<const Executor> exec_;
         size_type iterations_{0};
     };
     static Factory build() { return Factory{}; }
     std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
     std::shared_ptr<const matrix_type> get_u_factor() const { return u_; }
 protected:
-    ParIlu(std::shared_ptr<const Executor> exec, size_type iterations, std::shared_ptr<const LinOp> A)
+    friend class detail::factory_base<ParIlu>;
+    ParIlu(const Factory& f, std::shared_ptr<const LinOp> A)
     {
-        detail::require_device(exec, "par_ilu_factorization");
-        auto src = as<const matrix_type>(A.get());
-        const size_type n = src->get_size()[0];
-        if (n != src->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, "ParIlu needs a square matrix");
-        // working copy with explicit diagonal
-        array<I> rp(exec, n + 1);
-        exec->copy(n + 1, src->get_const_row_ptrs(), rp.get_data());
-        size_type nnz = src->get_num_stored_elements();
-        array<char> fws(exec, gkomi_factorization_workspace_bytes(n));
-        int64_t missing = 0;
-        GKOMI_CALL(gkomi_factorization_count_missing_diagonal_i32(nullptr, n, n, rp.get_const_data(), src->get_const_col_idxs(), fws.get_data(), fws.get_num_elems(), &missing));
-        array<I> ci(exec, nnz + missing);
-        array<V> v(exec, nnz + missing);
-        if (missing) {
-            GKOMI_CALL(gkomi_factorization_add_diagonal_elements_f64_i32(nullptr, n, n, rp.get_data(), src->get_const_col_idxs(), src->get_const_values(), ci.get_data(), v.get_data(), fws.get_const_data()));
-        } else {
-            exec->copy(nnz, src->get_const_col_idxs(), ci.get_data());
-            exec->copy(nnz, src->get_const_values(), v.get_data());
-        }
-        nnz += missing;
-        array<I> lrp(exec, n + 1), urp(exec, n + 1);
-        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
-        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_u_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), lrp.get_data(), urp.get_data(), sws.get_data(), sws.get_num_elems()));
-        const size_type lnnz = exec->copy_val_to_host(lrp.get_const_data() + n), unnz = exec->copy_val_to_host(urp.get_const_data() + n);
-        array<I> lc(exec, lnnz), uc(exec, unnz);
-        array<V> lv(exec, lnnz), uv(exec, unnz);
-        GKOMI_CALL(gkomi_factorization_initialize_l_u_f64_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), v.get_const_data(), lrp.get_const_data(), lc.get_data(), lv.get_data(), urp.get_const_data(), uc.get_data(), uv.get_data()));
-        array<I> utrp(exec, n + 1), utc(exec, unnz);
-        array<V> utv(exec, unnz);
-        array<char> tws(exec, gkomi_csr_transpose_workspace_bytes(n));
-        GKOMI_CALL(gkomi_csr_transpose_f64_i32(nullptr, n, n, unnz, urp.get_const_data(), uc.get_const_data(), uv.get_const_data(), utrp.get_data(), utc.get_data(), utv.get_data(), tws.get_data(), tws.get_num_elems()));
-        array<I> rows(exec, nnz);
-        GKOMI_CALL(gkomi_convert_ptrs_to_idxs_i32(nullptr, rp.get_const_data(), n, rows.get_data()));
-        GKOMI_CALL(gkomi_par_ilu_compute_l_u_factors_f64_i32(nullptr, iterations, nnz, rows.get_const_data(), ci.get_const_data(), v.get_const_data(), lrp.get_const_data(), lc.get_const_data(), lv.get_data(),
-                                                             utrp.get_const_data(), utc.get_const_data(), utv.get_data()));
-        GKOMI_CALL(gkomi_csr_transpose_f64_i32(nullptr, n, n, unnz, utrp.get_const_data(), utc.get_const_data(), utv.get_const_data(), urp.get_data(), uc.get_data(), uv.get_data(), tws.get_data(), tws.get_num_elems()));
-        auto l = matrix_type::create(exec); auto u = matrix_type::create(exec);
-        l->adopt(dim<2>(n, n), std::move(lrp), std::move(lc), std::move(lv));
-        u->adopt(dim<2>(n, n), std::move(urp), std::move(uc), std::move(uv));
-        l_ = std::move(l); u_ = std::move(u);
+        const auto& exec = f.exec_;
+        detail::source<V, I> src(exec, A.get(), "par_ilu_factorization", "ParIlu", false);
+        const size_type n = src.n;
+        array<char> fws(exec, gkomi_factorization_workspace_bytes(n)), tws(exec, gkomi_csr_transpose_workspace_bytes(n));
+        auto w = detail::with_diagonal(exec, src.mtx, fws);
+        auto lu = detail::split_l_u<V, I>(exec, w);
+        auto& l = lu.first; auto& u = lu.second;
+        auto ut = detail::transposed<V, I>(exec, u, &tws);
+        array<I> rows(exec, w.nnz());
+        GKOMI_CALL(gkomi_convert_ptrs_to_idxs_i32(nullptr, w.rp.get_const_data(), n, rows.get_data()));
+        GKOMI_CALL(gkomi_par_ilu_compute_l_u_factors_f64_i32(nullptr, f.iterations_, w.nnz(), rows.get_const_data(), w.ci.get_const_data(), w.v.get_const_data(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_data(),
+                                                             ut.rp.get_const_data(), ut.ci.get_const_data(), ut.v.get_data()));
+        detail::transpose_into<V, I>(ut, u, tws);
+        l_ = std::move(l).to_csr(); u_ = std::move(u).to_csr();
     }
     std::shared_ptr<matrix_type> l_, u_;
 };
-}  // namespace factorization
-
-// ---- Ilu + Ic, the exact ILU(0) / IC(0) (core/factorization/ilu.cpp:67-124, ic.cpp:67-120) ------
-namespace factorization {
-namespace detail_exact {
-// the working copy both generate chains factorize: sorted unless skipped, explicit diagonal, then
-// gkomi_ilu_analyse_i32 + the numeric phase in place
-template <typename V, typename I>
-struct working_copy {
-    size_type n{0}, nnz{0};
-    array<I> rp, ci;
-    array<V> v;
-    working_copy(std::shared_ptr<const Executor> exec, const LinOp* A, bool skip_sorting, bool ic, const char* who)
-    {
-        static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "the exact factorizations are <double, int32>");
-        detail::require_device(exec, who);
-        auto src = as<const matrix::Csr<V, I>>(A);
-        n = src->get_size()[0];
-        if (n != src->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, std::string(who) + " needs a square matrix");
-        std::unique_ptr<matrix::Csr<V, I>> sorted;
-        if (!skip_sorting && !src->is_sorted_by_column_index()) {
-            matrix_data<V, I> d;
-            src->write(d);
-            sorted = matrix::Csr<V, I>::create(exec);
-            sorted->read(d);
-            sorted->sort_by_column_index();
-            src = sorted.get();
-        }
-        rp = array<I>(exec, n + 1);
-        exec->copy(n + 1, src->get_const_row_ptrs(), rp.get_data());
-        nnz = src->get_num_stored_elements();
-        array<char> fws(exec, gkomi_factorization_workspace_bytes(n));
-        int64_t missing = 0;
-        GKOMI_CALL(gkomi_factorization_count_missing_diagonal_i32(nullptr, n, n, rp.get_const_data(), src->get_const_col_idxs(), fws.get_data(), fws.get_num_elems(), &missing));
-        ci = array<I>(exec, nnz + missing);
-        v = array<V>(exec, nnz + missing);
-        if (missing) {
-            GKOMI_CALL(gkomi_factorization_add_diagonal_elements_f64_i32(nullptr, n, n, rp.get_data(), src->get_const_col_idxs(), src->get_const_values(), ci.get_data(), v.get_data(), fws.get_const_data()));
-        } else {
-            exec->copy(nnz, src->get_const_col_idxs(), ci.get_data());
-            exec->copy(nnz, src->get_const_values(), v.get_data());
-        }
-        nnz += missing;
-        array<char> aws(exec, gkomi_ilu_analysis_workspace_bytes(n));
-        int64_t info[6] = {};
-        GKOMI_CALL(gkomi_ilu_analyse_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), aws.get_data(), aws.get_num_elems(), info));
-        if (ic) {
-            GKOMI_CALL(gkomi_ic_compute_f64_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), v.get_data(), aws.get_const_data(), aws.get_num_elems()));
-        } else {
-            GKOMI_CALL(gkomi_ilu_compute_lu_f64_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), v.get_data(), aws.get_const_data(), aws.get_num_elems()));
-        }
-        exec->synchronize();  // the analysis workspace leaves scope
-    }
-};
-}  // namespace detail_exact
 
 template <typename V = double, typename I = int32>
 class Ilu {
 public:
     using matrix_type = matrix::Csr<V, I>;
-    class Factory {
+    class Factory : public detail::factory_base<Ilu> {
     public:
         Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
         Factory& with_l_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { l_strategy_ = std::move(s); return *this; }
         Factory& with_u_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { u_strategy_ = std::move(s); return *this; }
-        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
-        std::unique_ptr<Ilu> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Ilu>(new Ilu(*this, std::move(A))); }
-        std::shared_ptr<const Executor> exec_;
         bool skip_sorting_{false};
         std::shared_ptr<typename matrix_type::strategy_type> l_strategy_, u_strategy_;
     };
@@ -2978,24 +3123,12 @@ public:
     std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
     std::shared_ptr<const matrix_type> get_u_factor() const { return u_; }
 protected:
+    friend class detail::factory_base<Ilu>;
     Ilu(const Factory& f, std::shared_ptr<const LinOp> A)
     {
-        const auto& exec = f.exec_;
-        detail_exact::working_copy<V, I> w(exec, A.get(), f.skip_sorting_, false, "ilu_factorization");
-        const size_type n = w.n;
-        array<I> lrp(exec, n + 1), urp(exec, n + 1);
-        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
-        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_u_i32(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), lrp.get_data(), urp.get_data(), sws.get_data(), sws.get_num_elems()));
-        const size_type lnnz = exec->copy_val_to_host(lrp.get_const_data() + n), unnz = exec->copy_val_to_host(urp.get_const_data() + n);
-        array<I> lc(exec, lnnz), uc(exec, unnz);
-        array<V> lv(exec, lnnz), uv(exec, unnz);
-        GKOMI_CALL(gkomi_factorization_initialize_l_u_f64_i32(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), w.v.get_const_data(), lrp.get_const_data(), lc.get_data(), lv.get_data(), urp.get_const_data(), uc.get_data(), uv.get_data()));
-        auto l = matrix_type::create(exec); auto u = matrix_type::create(exec);
-        l->adopt(dim<2>(n, n), std::move(lrp), std::move(lc), std::move(lv));
-        u->adopt(dim<2>(n, n), std::move(urp), std::move(uc), std::move(uv));
-        if (f.l_strategy_) l->set_strategy(f.l_strategy_);
-        if (f.u_strategy_) u->set_strategy(f.u_strategy_);
-        l_ = std::move(l); u_ = std::move(u);
+        auto w = detail::exact_factorized<V, I>(f.exec_, A.get(), f.skip_sorting_, false, "ilu_factorization");
+        auto lu = detail::split_l_u<V, I>(f.exec_, w);
+        l_ = std::move(lu.first).to_csr(f.l_strategy_); u_ = std::move(lu.second).to_csr(f.u_strategy_);
     }
     std::shared_ptr<matrix_type> l_, u_;
 };
@@ -3004,14 +3137,11 @@ template <typename V = double, typename I = int32>
 class Ic {
 public:
     using matrix_type = matrix::Csr<V, I>;
-    class Factory {
+    class Factory : public detail::factory_base<Ic> {
     public:
         Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
         Factory& with_both_factors(bool both) { both_factors_ = both; return *this; }
         Factory& with_l_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { l_strategy_ = std::move(s); return *this; }
-        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
-        std::unique_ptr<Ic> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Ic>(new Ic(*this, std::move(A))); }
-        std::shared_ptr<const Executor> exec_;
         bool skip_sorting_{false}, both_factors_{true};
         std::shared_ptr<typename matrix_type::strategy_type> l_strategy_;
     };
@@ -3020,35 +3150,23 @@ public:
     // nullptr when generated with_both_factors(false)
     std::shared_ptr<const matrix_type> get_lt_factor() const { return lt_; }
 protected:
+    friend class detail::factory_base<Ic>;
     Ic(const Factory& f, std::shared_ptr<const LinOp> A)
     {
-        const auto& exec = f.exec_;
-        detail_exact::working_copy<V, I> w(exec, A.get(), f.skip_sorting_, true, "ic_factorization");
-        const size_type n = w.n;
-        array<I> lrp(exec, n + 1);
-        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
-        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_i32(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), lrp.get_data(), sws.get_data(), sws.get_num_elems()));
-        const size_type lnnz = exec->copy_val_to_host(lrp.get_const_data() + n);
-        array<I> lc(exec, lnnz);
-        array<V> lv(exec, lnnz);
-        GKOMI_CALL(gkomi_factorization_initialize_l_f64_i32(nullptr, n, w.rp.get_const_data(), w.ci.get_const_data(), w.v.get_const_data(), lrp.get_const_data(), lc.get_data(), lv.get_data(), 0));
-        auto l = matrix_type::create(exec);
-        l->adopt(dim<2>(n, n), std::move(lrp), std::move(lc), std::move(lv));
-        if (f.l_strategy_) l->set_strategy(f.l_strategy_);
-        if (f.both_factors_) lt_ = l->transpose();
-        l_ = std::move(l);
+        auto w = detail::exact_factorized<V, I>(f.exec_, A.get(), f.skip_sorting_, true, "ic_factorization");
+        l_ = detail::split_l<V, I>(f.exec_, w, false).to_csr(f.l_strategy_);
+        if (f.both_factors_) lt_ = l_->transpose();
     }
     std::shared_ptr<matrix_type> l_, lt_;
 };
 
-// ---- ParIlut, the threshold ILU (core/factorization/par_ilut.cpp:190-344) -------------------------------------
-// The factors are the reference executor's, bit for bit: its sweep is sequential and in place, so its result
-// is determined by the pattern, and the device reproduces it with a level schedule (csrc/par_ilut.hip).
+// ParIlut, the threshold ILU.  The factors are the reference executor's, bit for bit: its sweep is sequential and in
+// place, so its result is determined by the pattern, and the device reproduces it with a level schedule (csrc/par_ilut.hip).
 template <typename V = double, typename I = int32>
 class ParIlut {
 public:
     using matrix_type = matrix::Csr<V, I>;
-    class Factory {
+    class Factory : public detail::factory_base<ParIlut> {
     public:
         Factory& with_iterations(size_type n) { iterations_ = n; return *this; }
         Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
@@ -3058,9 +3176,6 @@ public:
         Factory& with_fill_in_limit(double limit) { fill_in_limit_ = limit; return *this; }
         Factory& with_l_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { l_strategy_ = std::move(s); return *this; }
         Factory& with_u_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { u_strategy_ = std::move(s); return *this; }
-        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
-        std::unique_ptr<ParIlut> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<ParIlut>(new ParIlut(*this, std::move(A))); }
-        std::shared_ptr<const Executor> exec_;
         size_type iterations_{5};
         bool skip_sorting_{false}, approximate_select_{true}, deterministic_sample_{false};
         double fill_in_limit_{2.0};
@@ -3070,129 +3185,217 @@ public:
     std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
     std::shared_ptr<const matrix_type> get_u_factor() const { return u_; }
 protected:
-    struct factor {
-        array<I> rp, ci;
-        array<V> v;
-        int64_t nnz() const { return static_cast<int64_t>(v.get_num_elems()); }
-    };
-    static factor filtered(const std::shared_ptr<const Executor>& exec, size_type n, const factor& m, double threshold)
-    {
-        factor out{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
-        array<char> ws(exec, gkomi_par_ilut_filter_workspace_bytes(n));
-        int64_t nnz = 0;
-        GKOMI_CALL(gkomi_par_ilut_threshold_filter_f64_i32(nullptr, n, m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), threshold, out.rp.get_data(), nullptr, nullptr, nullptr, &nnz,
-                                                           ws.get_data(), ws.get_num_elems()));
-        out.ci = array<I>(exec, nnz);
-        out.v = array<V>(exec, nnz);
-        GKOMI_CALL(gkomi_par_ilut_threshold_filter_f64_i32(nullptr, n, m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), threshold, out.rp.get_data(), out.ci.get_data(), out.v.get_data(), nullptr,
-                                                           &nnz, ws.get_data(), ws.get_num_elems()));
-        return out;
-    }
+    friend class detail::factory_base<ParIlut>;
+    using factor = detail::csr_arrays<V, I>;
+    using view = detail::csr_view<V, I>;
     // compute_l_u_factors in place; ut: the CSC copy of u whose values are brought up to date, or nullptr
-    static void sweep(const std::shared_ptr<const Executor>& exec, size_type n, const matrix_type* a, factor& l, factor& u, factor* ut)
+    static void sweep(const std::shared_ptr<const Executor>& exec, view a, factor& l, factor& u, factor* ut)
     {
+        const size_type n = a.n;
         array<char> ws(exec, gkomi_par_ilut_sweep_workspace_bytes(n, l.nnz(), u.nnz()));
         int64_t info[6] = {};
         GKOMI_CALL(gkomi_par_ilut_analyse_i32(nullptr, n, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), u.nnz(), u.rp.get_const_data(), u.ci.get_const_data(), ws.get_data(), ws.get_num_elems(), info));
-        GKOMI_CALL(gkomi_par_ilut_compute_l_u_factors_f64_i32(nullptr, n, a->get_const_row_ptrs(), a->get_const_col_idxs(), a->get_const_values(), l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(),
-                                                              l.v.get_data(), u.nnz(), u.rp.get_const_data(), u.ci.get_const_data(), u.v.get_data(), ut ? ut->rp.get_const_data() : nullptr,
-                                                              ut ? ut->ci.get_const_data() : nullptr, ut ? ut->v.get_data() : nullptr, ws.get_const_data(), ws.get_num_elems()));
+        GKOMI_CALL(gkomi_par_ilut_compute_l_u_factors_f64_i32(nullptr, n, a.rp, a.ci, a.v, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_data(), u.nnz(), u.rp.get_const_data(),
+                                                              u.ci.get_const_data(), u.v.get_data(), ut ? ut->rp.get_const_data() : nullptr, ut ? ut->ci.get_const_data() : nullptr,
+                                                              ut ? ut->v.get_data() : nullptr, ws.get_const_data(), ws.get_num_elems()));
         exec->synchronize();  // the workspace leaves scope
     }
     ParIlut(const Factory& f, std::shared_ptr<const LinOp> A)
     {
-        static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "ParIlut is <double, int32>");
         const auto& exec = f.exec_;
-        detail::require_device(exec, "par_ilut_factorization");
-        auto src = as<const matrix_type>(A.get());
-        const size_type n = src->get_size()[0];
-        if (n != src->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, "ParIlut needs a square matrix");
+        detail::source<V, I> src(exec, A.get(), "par_ilut_factorization", "ParIlut", !f.skip_sorting_);
         // GKO_ASSERT_EQ(parameters_.fill_in_limit > 0.0, true)
         if (!(f.fill_in_limit_ > 0.0)) throw ValueMismatch(__FILE__, __LINE__, "ParIlut needs fill_in_limit > 0");
-        std::unique_ptr<matrix_type> sorted;
-        if (!f.skip_sorting_ && !src->is_sorted_by_column_index()) {
-            matrix_data<V, I> d;
-            src->write(d);
-            sorted = matrix_type::create(exec);
-            sorted->read(d);
-            sorted->sort_by_column_index();
-            src = sorted.get();
-        }
-        factor l{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)}, u{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
-        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
-        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_u_i32(nullptr, n, src->get_const_row_ptrs(), src->get_const_col_idxs(), l.rp.get_data(), u.rp.get_data(), sws.get_data(), sws.get_num_elems()));
-        const size_type lnnz = exec->copy_val_to_host(l.rp.get_const_data() + n), unnz = exec->copy_val_to_host(u.rp.get_const_data() + n);
-        l.ci = array<I>(exec, lnnz); l.v = array<V>(exec, lnnz);
-        u.ci = array<I>(exec, unnz); u.v = array<V>(exec, unnz);
-        GKOMI_CALL(gkomi_factorization_initialize_l_u_f64_i32(nullptr, n, src->get_const_row_ptrs(), src->get_const_col_idxs(), src->get_const_values(), l.rp.get_const_data(), l.ci.get_data(), l.v.get_data(),
-                                                              u.rp.get_const_data(), u.ci.get_data(), u.v.get_data()));
-        const int64_t l_nnz_limit = static_cast<I>(lnnz * f.fill_in_limit_), u_nnz_limit = static_cast<I>(unnz * f.fill_in_limit_);
+        const size_type n = src.n;
+        const view a(src.mtx);
+        auto lu0 = detail::split_l_u<V, I>(exec, a);
+        factor l = std::move(lu0.first), u = std::move(lu0.second);
+        const int64_t l_nnz_limit = static_cast<I>(l.nnz() * f.fill_in_limit_), u_nnz_limit = static_cast<I>(u.nnz() * f.fill_in_limit_);
         array<char> gws(exec, gkomi_csr_spgemm_workspace_bytes(n, n)), cws(exec, gkomi_par_ilut_add_candidates_workspace_bytes(n));
         array<char> tws(exec, gkomi_csr_transpose_workspace_bytes(n));
         for (size_type it = 0; it < f.iterations_; ++it) {
-            // L U
-            factor lu{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
-            int64_t lu_nnz = 0;
-            auto spgemm = [&] {
-                GKOMI_CALL(gkomi_csr_spgemm_f64_i32(nullptr, n, n, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_const_data(), n, n, u.nnz(), u.rp.get_const_data(), u.ci.get_const_data(),
-                                                    u.v.get_const_data(), nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, lu.rp.get_data(), lu.ci.get_num_elems() ? lu.ci.get_data() : nullptr,
-                                                    lu.v.get_num_elems() ? lu.v.get_data() : nullptr, &lu_nnz, gws.get_data(), gws.get_num_elems()));
-            };
-            spgemm();
-            lu.ci = array<I>(exec, lu_nnz);
-            lu.v = array<V>(exec, lu_nnz);
-            if (lu_nnz > 0) spgemm();
+            auto lu = detail::spgemm<V, I>(exec, l, u, gws);
             // the candidates L', U'
-            factor l_new{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)}, u_new{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
+            factor l_new(exec, n), u_new(exec, n);
             int64_t l_new_nnz = 0, u_new_nnz = 0;
-            auto add_candidates = [&](bool fill) {
-                GKOMI_CALL(gkomi_par_ilut_add_candidates_f64_i32(
-                    nullptr, n, lu.rp.get_const_data(), lu.ci.get_const_data(), lu.v.get_const_data(), src->get_const_row_ptrs(), src->get_const_col_idxs(), src->get_const_values(), l.rp.get_const_data(),
-                    l.ci.get_const_data(), l.v.get_const_data(), u.rp.get_const_data(), u.ci.get_const_data(), u.v.get_const_data(), l_new.rp.get_data(), fill ? l_new.ci.get_data() : nullptr,
-                    fill ? l_new.v.get_data() : nullptr, u_new.rp.get_data(), fill ? u_new.ci.get_data() : nullptr, fill ? u_new.v.get_data() : nullptr, &l_new_nnz, &u_new_nnz, cws.get_data(), cws.get_num_elems()));
+            auto add_candidates = [&] {
+                GKOMI_CALL(gkomi_par_ilut_add_candidates_f64_i32(nullptr, n, lu.rp.get_const_data(), lu.ci.get_const_data(), lu.v.get_const_data(), a.rp, a.ci, a.v, l.rp.get_const_data(), l.ci.get_const_data(),
+                                                                 l.v.get_const_data(), u.rp.get_const_data(), u.ci.get_const_data(), u.v.get_const_data(), l_new.rp.get_data(), l_new.ci.get_data(), l_new.v.get_data(),
+                                                                 u_new.rp.get_data(), u_new.ci.get_data(), u_new.v.get_data(), &l_new_nnz, &u_new_nnz, cws.get_data(), cws.get_num_elems()));
             };
-            add_candidates(false);
-            l_new.ci = array<I>(exec, l_new_nnz); l_new.v = array<V>(exec, l_new_nnz);
-            u_new.ci = array<I>(exec, u_new_nnz); u_new.v = array<V>(exec, u_new_nnz);
-            if (n > 0) add_candidates(true);
+            add_candidates();
+            l_new.resize(l_new_nnz);
+            u_new.resize(u_new_nnz);
+            if (n > 0) add_candidates();
             // U' by columns only where the order of its values matters: the approximate selection samples it
-            factor u_new_csc{array<I>(exec), array<I>(exec), array<V>(exec)};
-            if (f.approximate_select_) {
-                u_new_csc = factor{array<I>(exec, n + 1), array<I>(exec, u_new_nnz), array<V>(exec, u_new_nnz)};
-                GKOMI_CALL(gkomi_csr_transpose_f64_i32(nullptr, n, n, u_new_nnz, u_new.rp.get_const_data(), u_new.ci.get_const_data(), u_new.v.get_const_data(), u_new_csc.rp.get_data(), u_new_csc.ci.get_data(),
-                                                       u_new_csc.v.get_data(), tws.get_data(), tws.get_num_elems()));
-            }
-            sweep(exec, n, src, l_new, u_new, f.approximate_select_ ? &u_new_csc : nullptr);
+            factor u_new_csc;
+            if (f.approximate_select_) u_new_csc = detail::transposed<V, I>(exec, u_new, &tws);
+            sweep(exec, a, l_new, u_new, f.approximate_select_ ? &u_new_csc : nullptr);
             const int64_t l_rank = std::max<int64_t>(0, l_new_nnz - l_nnz_limit - 1), u_rank = std::max<int64_t>(0, u_new_nnz - u_nnz_limit - 1);
-            double l_threshold = 0.0, u_threshold = 0.0;
-            if (n > 0 && f.approximate_select_) {
-                array<char> ws(exec, gkomi_par_ilut_approx_workspace_bytes());
-                GKOMI_CALL(gkomi_par_ilut_threshold_approx_f64(nullptr, l_new_nnz, l_new.v.get_const_data(), l_rank, ws.get_data(), ws.get_num_elems(), &l_threshold));
-                GKOMI_CALL(gkomi_par_ilut_threshold_approx_f64(nullptr, u_new_nnz, u_new_csc.v.get_const_data(), u_rank, ws.get_data(), ws.get_num_elems(), &u_threshold));
-            } else if (n > 0) {
-                array<char> ws(exec, gkomi_par_ilut_select_workspace_bytes(std::max(l_new_nnz, u_new_nnz)));
-                GKOMI_CALL(gkomi_par_ilut_threshold_select_f64(nullptr, l_new_nnz, l_new.v.get_const_data(), l_rank, ws.get_data(), ws.get_num_elems(), &l_threshold));
-                GKOMI_CALL(gkomi_par_ilut_threshold_select_f64(nullptr, u_new_nnz, u_new.v.get_const_data(), u_rank, ws.get_data(), ws.get_num_elems(), &u_threshold));
-            }
-            l = filtered(exec, n, l_new, l_threshold);
-            u = filtered(exec, n, u_new, u_threshold);
-            sweep(exec, n, src, l, u, nullptr);
+            detail::threshold<V> select(exec, n, f.approximate_select_, std::max(l_new_nnz, u_new_nnz));
+            const double l_threshold = select(l_new.v, l_rank), u_threshold = select(f.approximate_select_ ? u_new_csc.v : u_new.v, u_rank);
+            l = detail::filtered<V, I>(exec, l_new, l_threshold);
+            u = detail::filtered<V, I>(exec, u_new, u_threshold);
+            sweep(exec, a, l, u, nullptr);
         }
-        auto lm = matrix_type::create(exec); auto um = matrix_type::create(exec);
-        lm->adopt(dim<2>(n, n), std::move(l.rp), std::move(l.ci), std::move(l.v));
-        um->adopt(dim<2>(n, n), std::move(u.rp), std::move(u.ci), std::move(u.v));
-        if (f.l_strategy_) lm->set_strategy(f.l_strategy_);
-        if (f.u_strategy_) um->set_strategy(f.u_strategy_);
-        l_ = std::move(lm); u_ = std::move(um);
+        l_ = std::move(l).to_csr(f.l_strategy_); u_ = std::move(u).to_csr(f.u_strategy_);
     }
     std::shared_ptr<matrix_type> l_, u_;
 };
+
+template <typename V = double, typename I = int32>
+class ParIc {
+public:
+    using matrix_type = matrix::Csr<V, I>;
+    class Factory : public detail::factory_base<ParIc> {
+    public:
+        Factory& with_iterations(size_type n) { iterations_ = n; return *this; }
+        Factory& with_skip_sorting(bool) { return *this; }
+        Factory& with_both_factors(bool) { return *this; }
+        size_type iterations_{0};
+    };
+    static Factory build() { return Factory{}; }
+    std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
+    std::shared_ptr<const matrix_type> get_lt_factor() const { return lt_; }
+protected:
+    friend class detail::factory_base<ParIc>;
+    ParIc(const Factory& f, std::shared_ptr<const LinOp> A)
+    {
+        const auto& exec = f.exec_;
+        detail::source<V, I> src(exec, A.get(), "par_ic_factorization", "ParIc", false);
+        const size_type n = src.n;
+        array<char> fws(exec, gkomi_factorization_workspace_bytes(n));
+        auto w = detail::with_diagonal(exec, src.mtx, fws);
+        auto l = detail::split_l<V, I>(exec, w, false);
+        array<I> rows(exec, l.nnz());
+        array<V> a_vals(exec, l.v);  // the COO copy of the lower triangle (par_ic.cpp:121-131)
+        GKOMI_CALL(gkomi_convert_ptrs_to_idxs_i32(nullptr, l.rp.get_const_data(), n, rows.get_data()));
+        GKOMI_CALL(gkomi_par_ic_init_factor_f64_i32(nullptr, n, l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_data()));
+        GKOMI_CALL(gkomi_par_ic_compute_factor_f64_i32(nullptr, f.iterations_, l.nnz(), rows.get_const_data(), a_vals.get_const_data(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_data()));
+        l_ = std::move(l).to_csr();
+        lt_ = l_->transpose();
+    }
+    std::shared_ptr<matrix_type> l_, lt_;
+};
+
+// ParIct, the threshold IC.  The factor is the reference executor's, bit for bit: its sweep is sequential and in place,
+// so its result is determined by the pattern, and the device reproduces it with a level schedule (csrc/par_ict.hip).
+// Selection and filter are those of ParIlut.
+template <typename V = double, typename I = int32>
+class ParIct {
+public:
+    using matrix_type = matrix::Csr<V, I>;
+    class Factory : public detail::factory_base<ParIct> {
+    public:
+        Factory& with_iterations(size_type n) { iterations_ = n; return *this; }
+        Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
+        Factory& with_approximate_select(bool approximate) { approximate_select_ = approximate; return *this; }
+        // the reference executor's sample is deterministic either way; so is this one
+        Factory& with_deterministic_sample(bool deterministic) { deterministic_sample_ = deterministic; return *this; }
+        Factory& with_fill_in_limit(double limit) { fill_in_limit_ = limit; return *this; }
+        Factory& with_l_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { l_strategy_ = std::move(s); return *this; }
+        Factory& with_lt_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { lt_strategy_ = std::move(s); return *this; }
+        size_type iterations_{5};
+        bool skip_sorting_{false}, approximate_select_{true}, deterministic_sample_{false};
+        double fill_in_limit_{2.0};
+        std::shared_ptr<typename matrix_type::strategy_type> l_strategy_, lt_strategy_;
+    };
+    static Factory build() { return Factory{}; }
+    std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
+    std::shared_ptr<const matrix_type> get_lt_factor() const { return lt_; }
+protected:
+    friend class detail::factory_base<ParIct>;
+    using factor = detail::csr_arrays<V, I>;
+    using view = detail::csr_view<V, I>;
+    // compute_factor in place
+    static void sweep(const std::shared_ptr<const Executor>& exec, view a, factor& l)
+    {
+        const size_type n = a.n;
+        array<char> ws(exec, gkomi_par_ict_sweep_workspace_bytes(n, l.nnz()));
+        int64_t info[6] = {};
+        GKOMI_CALL(gkomi_par_ict_analyse_i32(nullptr, n, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), ws.get_data(), ws.get_num_elems(), info));
+        GKOMI_CALL(gkomi_par_ict_compute_factor_f64_i32(nullptr, n, a.rp, a.ci, a.v, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_data(), ws.get_const_data(), ws.get_num_elems()));
+        exec->synchronize();  // the workspace leaves scope
+    }
+    ParIct(const Factory& f, std::shared_ptr<const LinOp> A)
+    {
+        const auto& exec = f.exec_;
+        detail::source<V, I> src(exec, A.get(), "par_ict_factorization", "ParIct", !f.skip_sorting_);
+        // GKO_ASSERT_EQ(parameters_.fill_in_limit > 0.0, true)
+        if (!(f.fill_in_limit_ > 0.0)) throw ValueMismatch(__FILE__, __LINE__, "ParIct needs fill_in_limit > 0");
+        const size_type n = src.n;
+        const view a(src.mtx);
+        factor l = detail::split_l<V, I>(exec, a, true);
+        const int64_t l_nnz_limit = static_cast<I>(l.nnz() * f.fill_in_limit_);
+        array<char> gws(exec, gkomi_csr_spgemm_workspace_bytes(n, n)), cws(exec, gkomi_par_ict_add_candidates_workspace_bytes(n));
+        factor lt = detail::transposed<V, I>(exec, l);
+        for (size_type it = 0; it < f.iterations_; ++it) {
+            auto llh = detail::spgemm<V, I>(exec, l, lt, gws);
+            // the candidates L'
+            factor l_new(exec, n);
+            int64_t l_new_nnz = 0;
+            auto add_candidates = [&] {
+                GKOMI_CALL(gkomi_par_ict_add_candidates_f64_i32(nullptr, n, llh.rp.get_const_data(), llh.ci.get_const_data(), llh.v.get_const_data(), a.rp, a.ci, a.v, l.rp.get_const_data(), l.ci.get_const_data(),
+                                                                l.v.get_const_data(), l_new.rp.get_data(), l_new.ci.get_data(), l_new.v.get_data(), &l_new_nnz, cws.get_data(), cws.get_num_elems()));
+            };
+            add_candidates();
+            l_new.resize(l_new_nnz);
+            if (n > 0) add_candidates();
+            sweep(exec, a, l_new);
+            const int64_t rank = std::max<int64_t>(0, l_new_nnz - l_nnz_limit - 1);
+            l = detail::filtered<V, I>(exec, l_new, detail::threshold<V>(exec, n, f.approximate_select_, l_new_nnz)(l_new.v, rank));
+            sweep(exec, a, l);
+            lt = detail::transposed<V, I>(exec, l);
+        }
+        l_ = std::move(l).to_csr(f.l_strategy_); lt_ = std::move(lt).to_csr(f.lt_strategy_);
+    }
+    std::shared_ptr<matrix_type> l_, lt_;
+};
 }  // namespace factorization
 
-
+// ---- preconditioner::Ilu and Ic (include/ginkgo/core/preconditioner/ilu.hpp:265-305, ic.hpp) -------------------------
 namespace preconditioner {
+namespace detail {
+// What Ilu and Ic share: the two factors of whatever generates them, the triangular solvers over them, and the apply
+// through one intermediate vector.
+template <typename V, typename I>
+class two_solves : public LinOp, public Transposable {
+protected:
+    two_solves(std::shared_ptr<const Executor> exec, dim<2> size) : LinOp(std::move(exec), size) {}
+    // what a factorization's Factory generates of A, on this executor unless the factory has one
+    template <class FactorizationFactory>
+    auto generated(const FactorizationFactory& f, std::shared_ptr<const LinOp> A) const { return (f.exec_ ? f : *f.on(exec_)).generate(std::move(A)); }
+    void set_factors(std::shared_ptr<const matrix::Csr<V, I>> lower, std::shared_ptr<const matrix::Csr<V, I>> upper)
+    {
+        lower_factor_ = std::move(lower);
+        upper_factor_ = std::move(upper);
+        lower_solver_ = solver::LowerTrs<V, I>::build().on(exec_)->generate(lower_factor_);
+        upper_solver_ = solver::UpperTrs<V, I>::build().on(exec_)->generate(upper_factor_);
+    }
+    void apply_impl(const LinOp* b, LinOp* x) const override
+    {
+        auto db = matrix::detail_fmt::dense(b);
+        auto mid = matrix::Dense<V>::create(exec_, db->get_size());
+        lower_solver_->apply(b, mid.get());
+        upper_solver_->apply(mid.get(), x);
+    }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
+    {
+        auto dx = matrix::detail_fmt::dense(x);
+        auto x_clone = dx->clone();
+        this->apply_impl(b, x_clone.get());
+        dx->scale(matrix::detail_fmt::dense(beta));
+        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
+    }
+    std::shared_ptr<const matrix::Csr<V, I>> lower_factor_, upper_factor_;
+    std::shared_ptr<const LinOp> lower_solver_, upper_solver_;
+};
+}  // namespace detail
+
 template <typename V = double, typename I = int32>
-class Ilu : public LinOp, public Transposable, public ::gko::detail::native_preconditioner {
+class Ilu : public detail::two_solves<V, I>, public ::gko::detail::native_preconditioner {
+    using base = detail::two_solves<V, I>;
+    using base::exec_; using base::size_; using base::lower_factor_; using base::upper_factor_; using base::lower_solver_; using base::upper_solver_;
 public:
     // L^-1 then U^-1 as gkomi_ilu_apply_cb + record: the two brick solves of an apply then run as a chain (no launch
     // that pre-fills an output with the ready flags), and no Dense objects are built per apply.  The record, the
@@ -3201,8 +3404,8 @@ public:
     bool native_callback(gkomi_apply_fn& fn, void*& ctx, size_type nrhs) const override
     {
         if (!std::is_same<V, double>::value || !std::is_same<I, int32>::value) return false;
-        auto l = dynamic_cast<const solver::LowerTrs<V, I>*>(l_solver_.get());
-        auto u = dynamic_cast<const solver::UpperTrs<V, I>*>(u_solver_.get());
+        auto l = dynamic_cast<const solver::LowerTrs<V, I>*>(lower_solver_.get());
+        auto u = dynamic_cast<const solver::UpperTrs<V, I>*>(upper_solver_.get());
         if (l == nullptr || u == nullptr || u->has_unit_diagonal()) return false;
         const size_type n = size_[0];
         if (mid_.get_num_elems() != n * nrhs || mid_.get_executor() == nullptr) {
@@ -3219,12 +3422,12 @@ public:
         record_.pad_ = chain_state;
         record_.n = static_cast<int64_t>(n);
         record_.nrhs = static_cast<int64_t>(nrhs);
-        record_.l_row_ptrs = l_factor_->get_const_row_ptrs();
-        record_.l_col_idxs = l_factor_->get_const_col_idxs();
-        record_.l_vals = l_factor_->get_const_values();
-        record_.u_row_ptrs = u_factor_->get_const_row_ptrs();
-        record_.u_col_idxs = u_factor_->get_const_col_idxs();
-        record_.u_vals = u_factor_->get_const_values();
+        record_.l_row_ptrs = lower_factor_->get_const_row_ptrs();
+        record_.l_col_idxs = lower_factor_->get_const_col_idxs();
+        record_.l_vals = lower_factor_->get_const_values();
+        record_.u_row_ptrs = upper_factor_->get_const_row_ptrs();
+        record_.u_col_idxs = upper_factor_->get_const_col_idxs();
+        record_.u_vals = upper_factor_->get_const_values();
         record_.intermediate = mid_.get_data();
         record_.trs_workspace = tws_.get_data();
         record_.trs_workspace_bytes = tws_.get_num_elems();
@@ -3248,7 +3451,7 @@ public:
         {
             if (ilut_) return std::unique_ptr<Ilu>(new Ilu(this->exec_, *ilut_, std::move(A)));
             if (exact_) return std::unique_ptr<Ilu>(new Ilu(this->exec_, *exact_, std::move(A)));
-            return std::unique_ptr<Ilu>(new Ilu(this->exec_, iterations_, std::move(A)));
+            return std::unique_ptr<Ilu>(new Ilu(this->exec_, ::gko::factorization::ParIlu<V, I>::build().with_iterations(iterations_), std::move(A)));
         }
         std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
         size_type iterations_{0};
@@ -3256,271 +3459,35 @@ public:
         std::shared_ptr<const typename ::gko::factorization::ParIlut<V, I>::Factory> ilut_;
     };
     static Factory build() { return Factory{}; }
-    std::shared_ptr<const LinOp> get_l_solver() const { return l_solver_; }
-    std::shared_ptr<const LinOp> get_u_solver() const { return u_solver_; }
+    std::shared_ptr<const LinOp> get_l_solver() const { return lower_solver_; }
+    std::shared_ptr<const LinOp> get_u_solver() const { return upper_solver_; }
     // Ilu::transpose (include/ginkgo/core/preconditioner/ilu.hpp:200-230): (U^-1 L^-1)^T =
     // L^-T U^-T, i.e. the lower solver of U^T followed by the upper solver of L^T
     std::unique_ptr<LinOp> transpose() const override
     {
         std::unique_ptr<Ilu> t(new Ilu(exec_, size_));
-        t->l_factor_ = std::shared_ptr<const matrix::Csr<V, I>>(u_factor_->transpose());
-        t->u_factor_ = std::shared_ptr<const matrix::Csr<V, I>>(l_factor_->transpose());
-        t->l_solver_ = solver::LowerTrs<V, I>::build().on(exec_)->generate(t->l_factor_);
-        t->u_solver_ = solver::UpperTrs<V, I>::build().on(exec_)->generate(t->u_factor_);
+        t->set_factors(upper_factor_->transpose(), lower_factor_->transpose());
         return std::unique_ptr<LinOp>(t.release());
     }
 protected:
-    Ilu(std::shared_ptr<const Executor> exec, dim<2> size) : LinOp(std::move(exec), size) {}
-    Ilu(std::shared_ptr<const Executor> exec, size_type iterations, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
-    {
-        auto fact = factorization::ParIlu<V, I>::build().with_iterations(iterations).on(exec)->generate(std::move(A));
-        l_factor_ = fact->get_l_factor();
-        u_factor_ = fact->get_u_factor();
-        l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(l_factor_);
-        u_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(u_factor_);
-    }
-    // a factorization factory that gives get_l_factor() / get_u_factor(): factorization::Ilu or factorization::ParIlut
+    Ilu(std::shared_ptr<const Executor> exec, dim<2> size) : base(std::move(exec), size) {}
+    // a factorization factory that gives get_l_factor() / get_u_factor(): factorization::ParIlu, Ilu or ParIlut
     template <class FactorizationFactory>
-    Ilu(std::shared_ptr<const Executor> exec, const FactorizationFactory& exact, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
+    Ilu(std::shared_ptr<const Executor> exec, const FactorizationFactory& f, std::shared_ptr<const LinOp> A) : base(std::move(exec), A->get_size())
     {
-        auto fact = (exact.exec_ ? exact : *exact.on(exec)).generate(std::move(A));
-        l_factor_ = fact->get_l_factor();
-        u_factor_ = fact->get_u_factor();
-        l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(l_factor_);
-        u_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(u_factor_);
+        auto fact = this->generated(f, std::move(A));
+        this->set_factors(fact->get_l_factor(), fact->get_u_factor());
     }
-    void apply_impl(const LinOp* b, LinOp* x) const override
-    {
-        auto db = matrix::detail_fmt::dense(b);
-        auto mid = matrix::Dense<V>::create(exec_, db->get_size());
-        l_solver_->apply(b, mid.get());
-        u_solver_->apply(mid.get(), x);
-    }
-    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
-    {
-        auto dx = matrix::detail_fmt::dense(x);
-        auto x_clone = dx->clone();
-        this->apply_impl(b, x_clone.get());
-        dx->scale(matrix::detail_fmt::dense(beta));
-        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
-    }
-    std::shared_ptr<const matrix::Csr<V, I>> l_factor_, u_factor_;
-    std::shared_ptr<const LinOp> l_solver_, u_solver_;
     mutable gkomi_ilu_ctx record_{};
     mutable array<V> mid_;
     mutable array<char> tws_;
 };
-}  // namespace preconditioner
 
-// ---- ParIc + Ic (core/factorization/par_ic.cpp:70-145, include/ginkgo/core/preconditioner/ic.hpp) ------
-namespace factorization {
+// Ic::apply = L^-1 then L^-H (ic.hpp: two triangular solves, like Ilu).  Not a native_preconditioner: a solver reaches
+// it through the generic callback.
 template <typename V = double, typename I = int32>
-class ParIc {
-public:
-    using matrix_type = matrix::Csr<V, I>;
-    class Factory {
-    public:
-        Factory& with_iterations(size_type n) { iterations_ = n; return *this; }
-        Factory& with_skip_sorting(bool) { return *this; }
-        Factory& with_both_factors(bool) { return *this; }
-        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
-        std::unique_ptr<ParIc> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<ParIc>(new ParIc(exec_, iterations_, std::move(A))); }
-        std::shared_ptr<const Executor> exec_;
-        size_type iterations_{0};
-    };
-    static Factory build() { return Factory{}; }
-    std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
-    std::shared_ptr<const matrix_type> get_lt_factor() const { return lt_; }
-protected:
-    ParIc(std::shared_ptr<const Executor> exec, size_type iterations, std::shared_ptr<const LinOp> A)
-    {
-        detail::require_device(exec, "par_ic_factorization");
-        auto src = as<const matrix_type>(A.get());
-        const size_type n = src->get_size()[0];
-        if (n != src->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, "ParIc needs a square matrix");
-        array<I> rp(exec, n + 1);
-        exec->copy(n + 1, src->get_const_row_ptrs(), rp.get_data());
-        size_type nnz = src->get_num_stored_elements();
-        array<char> fws(exec, gkomi_factorization_workspace_bytes(n));
-        int64_t missing = 0;
-        GKOMI_CALL(gkomi_factorization_count_missing_diagonal_i32(nullptr, n, n, rp.get_const_data(), src->get_const_col_idxs(), fws.get_data(), fws.get_num_elems(), &missing));
-        array<I> ci(exec, nnz + missing);
-        array<V> v(exec, nnz + missing);
-        if (missing) {
-            GKOMI_CALL(gkomi_factorization_add_diagonal_elements_f64_i32(nullptr, n, n, rp.get_data(), src->get_const_col_idxs(), src->get_const_values(), ci.get_data(), v.get_data(), fws.get_const_data()));
-        } else {
-            exec->copy(nnz, src->get_const_col_idxs(), ci.get_data());
-            exec->copy(nnz, src->get_const_values(), v.get_data());
-        }
-        array<I> lrp(exec, n + 1);
-        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
-        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), lrp.get_data(), sws.get_data(), sws.get_num_elems()));
-        const size_type lnnz = exec->copy_val_to_host(lrp.get_const_data() + n);
-        array<I> lc(exec, lnnz), rows(exec, lnnz);
-        array<V> lv(exec, lnnz);
-        GKOMI_CALL(gkomi_factorization_initialize_l_f64_i32(nullptr, n, rp.get_const_data(), ci.get_const_data(), v.get_const_data(), lrp.get_const_data(), lc.get_data(), lv.get_data(), 0));
-        array<V> a_vals(exec, lv);  // the COO copy of the lower triangle (par_ic.cpp:121-131)
-        GKOMI_CALL(gkomi_convert_ptrs_to_idxs_i32(nullptr, lrp.get_const_data(), n, rows.get_data()));
-        GKOMI_CALL(gkomi_par_ic_init_factor_f64_i32(nullptr, n, lrp.get_const_data(), lc.get_const_data(), lv.get_data()));
-        GKOMI_CALL(gkomi_par_ic_compute_factor_f64_i32(nullptr, iterations, lnnz, rows.get_const_data(), a_vals.get_const_data(), lrp.get_const_data(), lc.get_const_data(), lv.get_data()));
-        auto l = matrix_type::create(exec);
-        l->adopt(dim<2>(n, n), std::move(lrp), std::move(lc), std::move(lv));
-        lt_ = l->transpose();
-        l_ = std::move(l);
-    }
-    std::shared_ptr<matrix_type> l_, lt_;
-};
-
-// ---- ParIct, the threshold IC (core/factorization/par_ict.cpp:174-292) ----------------------------------------
-// The factor is the reference executor's, bit for bit: its sweep is sequential and in place, so its result is
-// determined by the pattern, and the device reproduces it with a level schedule (csrc/par_ict.hip).  Selection and
-// filter are those of ParIlut.
-template <typename V = double, typename I = int32>
-class ParIct {
-public:
-    using matrix_type = matrix::Csr<V, I>;
-    class Factory {
-    public:
-        Factory& with_iterations(size_type n) { iterations_ = n; return *this; }
-        Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
-        Factory& with_approximate_select(bool approximate) { approximate_select_ = approximate; return *this; }
-        // the reference executor's sample is deterministic either way; so is this one
-        Factory& with_deterministic_sample(bool deterministic) { deterministic_sample_ = deterministic; return *this; }
-        Factory& with_fill_in_limit(double limit) { fill_in_limit_ = limit; return *this; }
-        Factory& with_l_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { l_strategy_ = std::move(s); return *this; }
-        Factory& with_lt_strategy(std::shared_ptr<typename matrix_type::strategy_type> s) { lt_strategy_ = std::move(s); return *this; }
-        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
-        std::unique_ptr<ParIct> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<ParIct>(new ParIct(*this, std::move(A))); }
-        std::shared_ptr<const Executor> exec_;
-        size_type iterations_{5};
-        bool skip_sorting_{false}, approximate_select_{true}, deterministic_sample_{false};
-        double fill_in_limit_{2.0};
-        std::shared_ptr<typename matrix_type::strategy_type> l_strategy_, lt_strategy_;
-    };
-    static Factory build() { return Factory{}; }
-    std::shared_ptr<const matrix_type> get_l_factor() const { return l_; }
-    std::shared_ptr<const matrix_type> get_lt_factor() const { return lt_; }
-protected:
-    struct factor {
-        array<I> rp, ci;
-        array<V> v;
-        int64_t nnz() const { return static_cast<int64_t>(v.get_num_elems()); }
-    };
-    static factor transposed(const std::shared_ptr<const Executor>& exec, size_type n, const factor& m)
-    {
-        factor out{array<I>(exec, n + 1), array<I>(exec, m.nnz()), array<V>(exec, m.nnz())};
-        array<char> ws(exec, gkomi_csr_transpose_workspace_bytes(n));
-        GKOMI_CALL(gkomi_csr_transpose_f64_i32(nullptr, n, n, m.nnz(), m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), out.rp.get_data(), out.ci.get_data(), out.v.get_data(), ws.get_data(),
-                                               ws.get_num_elems()));
-        exec->synchronize();  // the workspace leaves scope
-        return out;
-    }
-    // par_ilut_factorization::threshold_filter: the reference executor's keeps |v| >= threshold || col == row whatever its `lower` flag says
-    static factor filtered(const std::shared_ptr<const Executor>& exec, size_type n, const factor& m, double threshold)
-    {
-        factor out{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
-        array<char> ws(exec, gkomi_par_ilut_filter_workspace_bytes(n));
-        int64_t nnz = 0;
-        GKOMI_CALL(gkomi_par_ilut_threshold_filter_f64_i32(nullptr, n, m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), threshold, out.rp.get_data(), nullptr, nullptr, nullptr, &nnz,
-                                                           ws.get_data(), ws.get_num_elems()));
-        out.ci = array<I>(exec, nnz);
-        out.v = array<V>(exec, nnz);
-        GKOMI_CALL(gkomi_par_ilut_threshold_filter_f64_i32(nullptr, n, m.rp.get_const_data(), m.ci.get_const_data(), m.v.get_const_data(), threshold, out.rp.get_data(), out.ci.get_data(), out.v.get_data(), nullptr,
-                                                           &nnz, ws.get_data(), ws.get_num_elems()));
-        return out;
-    }
-    // compute_factor in place
-    static void sweep(const std::shared_ptr<const Executor>& exec, size_type n, const matrix_type* a, factor& l)
-    {
-        array<char> ws(exec, gkomi_par_ict_sweep_workspace_bytes(n, l.nnz()));
-        int64_t info[6] = {};
-        GKOMI_CALL(gkomi_par_ict_analyse_i32(nullptr, n, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), ws.get_data(), ws.get_num_elems(), info));
-        GKOMI_CALL(gkomi_par_ict_compute_factor_f64_i32(nullptr, n, a->get_const_row_ptrs(), a->get_const_col_idxs(), a->get_const_values(), l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_data(),
-                                                        ws.get_const_data(), ws.get_num_elems()));
-        exec->synchronize();  // the workspace leaves scope
-    }
-    ParIct(const Factory& f, std::shared_ptr<const LinOp> A)
-    {
-        static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "ParIct is <double, int32>");
-        const auto& exec = f.exec_;
-        detail::require_device(exec, "par_ict_factorization");
-        auto src = as<const matrix_type>(A.get());
-        const size_type n = src->get_size()[0];
-        if (n != src->get_size()[1]) throw DimensionMismatch(__FILE__, __LINE__, "ParIct needs a square matrix");
-        // GKO_ASSERT_EQ(parameters_.fill_in_limit > 0.0, true)
-        if (!(f.fill_in_limit_ > 0.0)) throw ValueMismatch(__FILE__, __LINE__, "ParIct needs fill_in_limit > 0");
-        std::unique_ptr<matrix_type> sorted;
-        if (!f.skip_sorting_ && !src->is_sorted_by_column_index()) {
-            matrix_data<V, I> d;
-            src->write(d);
-            sorted = matrix_type::create(exec);
-            sorted->read(d);
-            sorted->sort_by_column_index();
-            src = sorted.get();
-        }
-        factor l{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
-        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
-        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_i32(nullptr, n, src->get_const_row_ptrs(), src->get_const_col_idxs(), l.rp.get_data(), sws.get_data(), sws.get_num_elems()));
-        const size_type lnnz = exec->copy_val_to_host(l.rp.get_const_data() + n);
-        l.ci = array<I>(exec, lnnz); l.v = array<V>(exec, lnnz);
-        // diag_sqrt = true
-        GKOMI_CALL(gkomi_factorization_initialize_l_f64_i32(nullptr, n, src->get_const_row_ptrs(), src->get_const_col_idxs(), src->get_const_values(), l.rp.get_const_data(), l.ci.get_data(), l.v.get_data(), 1));
-        const int64_t l_nnz_limit = static_cast<I>(lnnz * f.fill_in_limit_);
-        array<char> gws(exec, gkomi_csr_spgemm_workspace_bytes(n, n)), cws(exec, gkomi_par_ict_add_candidates_workspace_bytes(n));
-        factor lt = transposed(exec, n, l);
-        for (size_type it = 0; it < f.iterations_; ++it) {
-            // L L^T
-            factor llh{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
-            int64_t llh_nnz = 0;
-            auto spgemm = [&] {
-                GKOMI_CALL(gkomi_csr_spgemm_f64_i32(nullptr, n, n, l.nnz(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_const_data(), n, n, lt.nnz(), lt.rp.get_const_data(), lt.ci.get_const_data(),
-                                                    lt.v.get_const_data(), nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, llh.rp.get_data(), llh.ci.get_num_elems() ? llh.ci.get_data() : nullptr,
-                                                    llh.v.get_num_elems() ? llh.v.get_data() : nullptr, &llh_nnz, gws.get_data(), gws.get_num_elems()));
-            };
-            spgemm();
-            llh.ci = array<I>(exec, llh_nnz);
-            llh.v = array<V>(exec, llh_nnz);
-            if (llh_nnz > 0) spgemm();
-            // the candidates L'
-            factor l_new{array<I>(exec, n + 1), array<I>(exec), array<V>(exec)};
-            int64_t l_new_nnz = 0;
-            auto add_candidates = [&](bool fill) {
-                GKOMI_CALL(gkomi_par_ict_add_candidates_f64_i32(nullptr, n, llh.rp.get_const_data(), llh.ci.get_const_data(), llh.v.get_const_data(), src->get_const_row_ptrs(), src->get_const_col_idxs(),
-                                                                src->get_const_values(), l.rp.get_const_data(), l.ci.get_const_data(), l.v.get_const_data(), l_new.rp.get_data(),
-                                                                fill ? l_new.ci.get_data() : nullptr, fill ? l_new.v.get_data() : nullptr, &l_new_nnz, cws.get_data(), cws.get_num_elems()));
-            };
-            add_candidates(false);
-            l_new.ci = array<I>(exec, l_new_nnz); l_new.v = array<V>(exec, l_new_nnz);
-            if (n > 0) add_candidates(true);
-            sweep(exec, n, src, l_new);
-            const int64_t rank = std::max<int64_t>(0, l_new_nnz - l_nnz_limit - 1);
-            double threshold = 0.0;
-            if (n > 0 && f.approximate_select_) {
-                array<char> ws(exec, gkomi_par_ilut_approx_workspace_bytes());
-                GKOMI_CALL(gkomi_par_ilut_threshold_approx_f64(nullptr, l_new_nnz, l_new.v.get_const_data(), rank, ws.get_data(), ws.get_num_elems(), &threshold));
-            } else if (n > 0) {
-                array<char> ws(exec, gkomi_par_ilut_select_workspace_bytes(l_new_nnz));
-                GKOMI_CALL(gkomi_par_ilut_threshold_select_f64(nullptr, l_new_nnz, l_new.v.get_const_data(), rank, ws.get_data(), ws.get_num_elems(), &threshold));
-            }
-            l = filtered(exec, n, l_new, threshold);
-            sweep(exec, n, src, l);
-            lt = transposed(exec, n, l);
-        }
-        auto lm = matrix_type::create(exec); auto ltm = matrix_type::create(exec);
-        lm->adopt(dim<2>(n, n), std::move(l.rp), std::move(l.ci), std::move(l.v));
-        ltm->adopt(dim<2>(n, n), std::move(lt.rp), std::move(lt.ci), std::move(lt.v));
-        if (f.l_strategy_) lm->set_strategy(f.l_strategy_);
-        if (f.lt_strategy_) ltm->set_strategy(f.lt_strategy_);
-        l_ = std::move(lm); lt_ = std::move(ltm);
-    }
-    std::shared_ptr<matrix_type> l_, lt_;
-};
-}  // namespace factorization
-
-namespace preconditioner {
-// Ic::apply = L^-1 then L^-H (ic.hpp: two triangular solves, like Ilu)
-template <typename V = double, typename I = int32>
-class Ic : public LinOp, public Transposable {
+class Ic : public detail::two_solves<V, I> {
+    using base = detail::two_solves<V, I>;
 public:
     // (L L^T)^-1 is symmetric: the transpose applies the same two solves
     std::unique_ptr<LinOp> transpose() const override { return std::unique_ptr<LinOp>(new Ic(*this)); }
@@ -3536,8 +3503,12 @@ public:
         std::unique_ptr<Ic> generate(std::shared_ptr<const LinOp> A) const
         {
             if (ict_) return std::unique_ptr<Ic>(new Ic(this->exec_, *ict_, std::move(A)));
-            if (exact_) return std::unique_ptr<Ic>(new Ic(this->exec_, *exact_, std::move(A)));
-            return std::unique_ptr<Ic>(new Ic(this->exec_, iterations_, std::move(A)));
+            if (exact_) {
+                auto both = *exact_;
+                both.with_both_factors(true);  // the preconditioner needs L^T whatever the factory says
+                return std::unique_ptr<Ic>(new Ic(this->exec_, both, std::move(A)));
+            }
+            return std::unique_ptr<Ic>(new Ic(this->exec_, ::gko::factorization::ParIc<V, I>::build().with_iterations(iterations_), std::move(A)));
         }
         std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
         size_type iterations_{0};
@@ -3545,46 +3516,17 @@ public:
         std::shared_ptr<const typename ::gko::factorization::ParIct<V, I>::Factory> ict_;
     };
     static Factory build() { return Factory{}; }
-    std::shared_ptr<const LinOp> get_l_solver() const { return l_solver_; }
-    std::shared_ptr<const LinOp> get_lh_solver() const { return lh_solver_; }
+    std::shared_ptr<const LinOp> get_l_solver() const { return this->lower_solver_; }
+    std::shared_ptr<const LinOp> get_lh_solver() const { return this->upper_solver_; }
 protected:
     Ic(const Ic&) = default;
-    Ic(std::shared_ptr<const Executor> exec, size_type iterations, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
+    // a factorization factory that gives get_l_factor() / get_lt_factor(): factorization::ParIc, Ic or ParIct
+    template <class FactorizationFactory>
+    Ic(std::shared_ptr<const Executor> exec, const FactorizationFactory& f, std::shared_ptr<const LinOp> A) : base(std::move(exec), A->get_size())
     {
-        auto fact = factorization::ParIc<V, I>::build().with_iterations(iterations).on(exec)->generate(std::move(A));
-        l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(fact->get_l_factor());
-        lh_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(fact->get_lt_factor());
+        auto fact = this->generated(f, std::move(A));
+        this->set_factors(fact->get_l_factor(), fact->get_lt_factor());
     }
-    Ic(std::shared_ptr<const Executor> exec, const typename ::gko::factorization::Ic<V, I>::Factory& exact, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
-    {
-        auto both = exact;
-        both.with_both_factors(true);  // the preconditioner needs L^T whatever the factory says
-        auto fact = (both.exec_ ? both : *both.on(exec)).generate(std::move(A));
-        l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(fact->get_l_factor());
-        lh_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(fact->get_lt_factor());
-    }
-    Ic(std::shared_ptr<const Executor> exec, const typename ::gko::factorization::ParIct<V, I>::Factory& ict, std::shared_ptr<const LinOp> A) : LinOp(exec, A->get_size())
-    {
-        auto fact = (ict.exec_ ? ict : *ict.on(exec)).generate(std::move(A));
-        l_solver_ = solver::LowerTrs<V, I>::build().on(exec)->generate(fact->get_l_factor());
-        lh_solver_ = solver::UpperTrs<V, I>::build().on(exec)->generate(fact->get_lt_factor());
-    }
-    void apply_impl(const LinOp* b, LinOp* x) const override
-    {
-        auto db = matrix::detail_fmt::dense(b);
-        auto mid = matrix::Dense<V>::create(exec_, db->get_size());
-        l_solver_->apply(b, mid.get());
-        lh_solver_->apply(mid.get(), x);
-    }
-    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
-    {
-        auto dx = matrix::detail_fmt::dense(x);
-        auto x_clone = dx->clone();
-        this->apply_impl(b, x_clone.get());
-        dx->scale(matrix::detail_fmt::dense(beta));
-        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
-    }
-    std::shared_ptr<const LinOp> l_solver_, lh_solver_;
 };
 }  // namespace preconditioner
 
@@ -3692,21 +3634,9 @@ public:
         static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "Factorization is <double, int32>");
         const auto& exec = exec_;
         ::gko::detail::require_device(exec, "factorization::initialize_l_u");
-        const size_type n = size_[0];
-        array<I> lrp(exec, n + 1), urp(exec, n + 1);
-        array<char> sws(exec, gkomi_prefix_sum_workspace_bytes(n + 1) + 8);
-        GKOMI_CALL(gkomi_factorization_initialize_row_ptrs_l_u_i32(nullptr, n, combined_->get_const_row_ptrs(), combined_->get_const_col_idxs(), lrp.get_data(), urp.get_data(),
-                                                                   sws.get_data(), sws.get_num_elems()));
-        const size_type lnnz = exec->copy_val_to_host(lrp.get_const_data() + n), unnz = exec->copy_val_to_host(urp.get_const_data() + n);
-        array<I> lc(exec, lnnz), uc(exec, unnz);
-        array<V> lv(exec, lnnz), uv(exec, unnz);
-        GKOMI_CALL(gkomi_factorization_initialize_l_u_f64_i32(nullptr, n, combined_->get_const_row_ptrs(), combined_->get_const_col_idxs(), combined_->get_const_values(),
-                                                              lrp.get_const_data(), lc.get_data(), lv.get_data(), urp.get_const_data(), uc.get_data(), uv.get_data()));
+        auto lu = ::gko::factorization::detail::split_l_u<V, I>(exec, combined_.get());
         GKOMI_CALL(gkomi_synchronize(nullptr));
-        auto l = matrix_type::create(exec); auto u = matrix_type::create(exec);
-        l->adopt(size_, std::move(lrp), std::move(lc), std::move(lv));
-        u->adopt(size_, std::move(urp), std::move(uc), std::move(uv));
-        return create_from_composition(std::move(l), std::move(u));
+        return create_from_composition(std::move(lu.first).to_csr(), std::move(lu.second).to_csr());
     }
 protected:
     Factorization(std::shared_ptr<const Executor> exec, const dim<2>& size, storage_type type) : LinOp(std::move(exec), size), type_(type) {}

@@ -33,12 +33,17 @@ def test_known_answers(gk):
         assert np.array_equal(Lt, Lg.T)
 
 
-@pytest.mark.parametrize("grid", [7, 40])
-def test_setup_bitexact_and_sweeps_converge_to_ic0(gk, oracle, grid):
+def perturbed_grid(grid):
     n, rp, ci, v = matgen.poisson_2d_5pt(grid)
     # drop a few diagonal entries' storage? no: IC needs an SPD matrix; make it less regular instead
     v = v * (1.0 + 0.1 * np.cos(np.arange(len(v))))
     v = 0.5 * (v + v[np.lexsort((np.repeat(np.arange(n), np.diff(rp)), ci))])  # symmetrise (pattern is symmetric)
+    return n, rp, ci, v
+
+
+@pytest.mark.parametrize("grid", [7, 40])
+def test_setup_bitexact_and_sweeps_converge_to_ic0(gk, oracle, grid):
+    n, rp, ci, v = perturbed_grid(grid)
     e = ilu_util.oracle_par_ic(oracle, n, rp, ci, v)
     lrp = np.zeros(n + 1, np.int32)
     oracle.ref_initialize_row_ptrs_l(n, rp, ci, lrp)
@@ -60,6 +65,24 @@ def test_setup_bitexact_and_sweeps_converge_to_ic0(gk, oracle, grid):
     assert matgen.rel_err(host(f["L"][2]), e["L"][2]) <= 1e-12
     few = ilu_util.gpu_par_ic(gk, torch, n, dev(rp), dev(ci), dev(v), iterations=0)   # "Auto" = 10 sweeps
     assert matgen.rel_err(host(few["L"][2]), e["L"][2]) <= 5e-2
+
+
+def test_par_ic_generate_of_the_python_layer_vs_oracle(gk, oracle):
+    """solvers.par_ic_generate itself, not the restatement in ilu_util, on the perturbed 7 x 7 grid: patterns exactly,
+    values to the bar of the test above, Lt the exact transpose of L"""
+    n, rp, ci, v = perturbed_grid(7)
+    e = ilu_util.oracle_par_ic(oracle, n, rp, ci, v)
+    p = solvers.par_ic_generate(gk, n, dev(rp), dev(ci), dev(v), iterations=60)
+    torch.cuda.synchronize()
+    for got, key in ((p.L, "L"), (p.Lt, "Lt")):
+        assert np.array_equal(host(got[0]), e[key][0]) and np.array_equal(host(got[1]), e[key][1]), key
+        err = matgen.rel_err(host(got[2]), e[key][2])
+        print(key, "rel_err", err)
+        assert err <= 1e-12, key
+    L = ilu_util.csr_to_dense(n, n, *(host(t) for t in p.L))
+    Lt = ilu_util.csr_to_dense(n, n, *(host(t) for t in p.Lt))
+    assert np.array_equal(Lt, L.T)
+    assert np.array_equal(host(p.Lt[1]), e["Lt"][1])
 
 
 def test_ic_preconditioned_cg(gk):

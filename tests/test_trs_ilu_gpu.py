@@ -186,6 +186,17 @@ def test_par_ilu_known_factors(gk, case):
     assert matgen.rel_err(U, case["U"]) <= max(case["tol"], 1e-14)
 
 
+def random_dd():
+    """n = 400, diagonally dominant, rows 7 and 123 without a stored diagonal"""
+    n = 400
+    rp, ci, v = matgen.random_csr(n, n, 2, 9, seed=12)
+    a = ilu_util.csr_to_dense(n, n, rp, ci, v) * 0.1
+    a[np.arange(n), np.arange(n)] = 3.0
+    a[7, 7] = 0.0
+    a[123, 123] = 0.0
+    return (n, *matgen.dense_to_csr(a))
+
+
 @pytest.mark.parametrize("name", ["poisson2d", "poisson3d", "random_dd"])
 def test_par_ilu_chain_vs_oracle(gk, oracle, name):
     if name == "poisson2d":
@@ -193,14 +204,7 @@ def test_par_ilu_chain_vs_oracle(gk, oracle, name):
     elif name == "poisson3d":
         n, rp, ci, v = matgen.poisson_3d_7pt(12, 11, 13)
     else:
-        n = 400
-        rp, ci, v = matgen.random_csr(n, n, 2, 9, seed=12)
-        # diagonally dominant, some rows without a stored diagonal
-        a = ilu_util.csr_to_dense(n, n, rp, ci, v) * 0.1
-        a[np.arange(n), np.arange(n)] = 3.0
-        a[7, 7] = 0.0
-        a[123, 123] = 0.0
-        rp, ci, v = matgen.dense_to_csr(a)
+        n, rp, ci, v = random_dd()
     e = ilu_util.oracle_par_ilu(oracle, n, rp, ci, v)
     f = ilu_util.gpu_par_ilu(gk, torch, n, dev(rp), dev(ci), dev(v), iterations=60)
     # integer parts of the chain: bit-exact
@@ -215,6 +219,21 @@ def test_par_ilu_chain_vs_oracle(gk, oracle, name):
     f10 = ilu_util.gpu_par_ilu(gk, torch, n, dev(rp), dev(ci), dev(v), iterations=0)
     assert matgen.rel_err(host(f10["L"][2]), e["L"][2]) <= 5e-2
     assert matgen.rel_err(host(f10["U"][2]), e["U"][2]) <= 5e-2
+
+
+def test_par_ilu_generate_of_the_python_layer_vs_oracle(gk, oracle):
+    """solvers.par_ilu_generate itself, not the restatement in ilu_util: random_dd lacks two stored diagonals, so the
+    add-diagonal path runs.  Patterns exactly, values to the bar of test_par_ilu_chain_vs_oracle."""
+    from gkomi import solvers
+    n, rp, ci, v = random_dd()
+    e = ilu_util.oracle_par_ilu(oracle, n, rp, ci, v)
+    p = solvers.par_ilu_generate(gk, n, dev(rp), dev(ci), dev(v), iterations=60)
+    torch.cuda.synchronize()
+    for got, key in ((p.L, "L"), (p.U, "U")):
+        assert np.array_equal(host(got[0]), e[key][0]) and np.array_equal(host(got[1]), e[key][1]), key
+        err = matgen.rel_err(host(got[2]), e[key][2])
+        print(key, "rel_err", err)
+        assert err <= 1e-12, key
 
 
 def test_transpose_bitexact_vs_oracle(gk, oracle):

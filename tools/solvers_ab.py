@@ -2,7 +2,8 @@
 """A/B of gkomi/solvers.py against another version of the same file, in one process and on one library: every public
 solve function is called through both modules with the same arguments, and x (torch.equal) and every other entry of
 the returned dict must be equal.  Then the working tree's module must refuse a strided b in every solve function
-before anything reaches the C ABI.
+before anything reaches the C ABI.  Then the generate functions of the factorizations go through both modules
+(generate_ab below).
 
     python tools/solvers_ab.py [other]
 
@@ -105,6 +106,73 @@ def same(ra, rb):
     return True
 
 
+def unsorted(m):
+    """every row's entries in another order (a fixed permutation per row)"""
+    rp, ci, v = (np.array(x) for x in m)
+    rng = np.random.default_rng(5)
+    for r in range(len(rp) - 1):
+        o = rng.permutation(rp[r + 1] - rp[r]) + rp[r]
+        ci[rp[r]:rp[r + 1]], v[rp[r]:rp[r + 1]] = ci[o], v[o]
+    return rp, ci, v
+
+
+def bits(t):
+    return t.view(torch.int64) if t.dtype == torch.float64 else t
+
+
+def same_csr(a, b, values=True):
+    return all(x.shape == y.shape and torch.equal(bits(x), bits(y)) for x, y in list(zip(a, b))[:3 if values else 2])
+
+
+def generate_ab(gk, other):
+    """par_ilu_generate, par_ic_generate, ilu_generate, ic_generate, par_ilut_generate, par_ict_generate, symbolic_cholesky
+    and lu_generate through both modules.  Matrices: ani1, the 24 x 20 grid, ilu_exact_util.arrow(1100), and ani1 with
+    the entries of every row permuted (for the four functions that sort; the others have no sort path and are not
+    handed unsorted rows).  The IC family, symbolic_cholesky and lu_generate get spd_version of the matrix (a symmetric
+    pattern).  Defaults, and approximate_select=False, fill_in_limit=1.2, iterations=2 for the threshold pair.  Every
+    factor array of the exact and threshold functions and of the direct solver's must be equal by its bits (row
+    pointers, column indices, values; .levels too); of the two asynchronous par_i*_generate the patterns."""
+    import ilu_exact_util as xu
+    import par_ilut_util as pu
+    mats = {"ani1": pu.RECORDED_CASES["ani1"](), "grid_24x20": pu.RECORDED_CASES["grid_24x20"](), "arrow(1100)": xu.arrow(1100)}
+    mats["ani1 unsorted"] = unsorted(mats["ani1"])
+    exact = dict(approximate_select=False, fill_in_limit=1.2, iterations=2)
+    runs = [("par_ilu_generate", False, {}, ("L", "U"), False), ("par_ic_generate", True, {}, ("L", "Lt"), False),
+            ("ilu_generate", False, {}, ("L", "U"), True), ("ic_generate", True, {}, ("L", "Lt"), True),
+            ("par_ilut_generate", False, {}, ("L", "U"), True), ("par_ilut_generate", False, exact, ("L", "U"), True),
+            ("par_ict_generate", True, {}, ("L", "Lt"), True), ("par_ict_generate", True, exact, ("L", "Lt"), True)]
+    cases = bad = 0
+
+    def check(label, ok):
+        nonlocal cases, bad
+        cases += 1
+        if not ok:
+            bad += 1
+            print(f"DIFFERS {label}")
+    for name, m in mats.items():
+        sorts = name.endswith("unsorted")
+        spd = xu.spd_version(m) if not sorts else unsorted(xu.spd_version(mats["ani1"]))
+        n = len(m[0]) - 1
+        for fn, symmetric, kw, factors, values in runs:
+            if sorts and not values:
+                continue
+            a = tuple(dev(x) for x in (spd if symmetric else m))
+            pa, pb = (getattr(mod, fn)(gk, n, *a, **kw) for mod in (other, solvers))
+            torch.cuda.synchronize()
+            ok = all(same_csr(getattr(pa, f), getattr(pb, f), values) for f in factors)
+            check(f"{name} {fn} {kw}", ok and getattr(pa, "levels", None) == getattr(pb, "levels", None))
+        if sorts:
+            continue
+        a = tuple(dev(x) for x in spd)
+        ra, rb = (mod.symbolic_cholesky(gk, n, a[0], a[1]) for mod in (other, solvers))
+        check(f"{name} symbolic_cholesky", same_csr(ra[0], rb[0]) and same_csr(ra[1], rb[1]))
+        fa, fb = (mod.lu_generate(gk, n, *a, symmetric_sparsity=True) for mod in (other, solvers))
+        torch.cuda.synchronize()
+        check(f"{name} lu_generate", same_csr(fa.combined, fb.combined) and torch.equal(fa.diag_idxs, fb.diag_idxs))
+    print(f"generate: {cases} cases, {bad} differ")
+    return bad
+
+
 def main():
     other = load_other(sys.argv[1] if len(sys.argv) > 1 else "HEAD~1")
     gk = gkomi.lib()
@@ -155,6 +223,7 @@ def main():
             refused += 1
     bad += len(attempts) - refused
     print(f"{cases} cases, {bad} differ; strided b refused by {refused} of {len(attempts)}")
+    bad += generate_ab(gk, other)
     return 1 if bad else 0
 
 
