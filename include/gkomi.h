@@ -93,6 +93,17 @@ enum {
     GKOMI_CSR_SPLIT = 4    /* nnz-split streaming through LDS over srow, bit-exact
                               (gkomi_csr_spmv_srow_f64_i32 only)               */
 };
+/* Variant bits of an explicit GKOMI_CSR_SPLIT (bits 8-15 of the strategy word), for tests
+ * and A/B timings -- never results:
+ *   2 << 8  nontemporal loads of the matrix streams;
+ *   4 << 8  force the row-major lane order of the gather of b: every wave transposes its
+ *           segment of the tile through LDS so that neighbouring lanes gather neighbouring
+ *           entries of b, with stride s = max_row_nnz_hint clamped to 1 .. tile / 256;
+ *   8 << 8  forbid it.
+ * With neither bit (and under GKOMI_CSR_AUTO) the launcher takes the row-major order only for
+ * matrices known to be regular, and where it was measured to pay: nrhs == 1, hint odd (an even
+ * stride has LDS bank conflicts), 2 <= hint <= tile / 256, tile <= 1536 and
+ * 64 nnz >= 63 hint nrows (gkomi_diag_csr_split_row_stride tells). */
 /* OR-ed into the strategy word: the caller's working set between two applies of
  * this matrix exceeds the 256 MiB Infinity Cache (a Krylov basis, other
  * matrices, ...), so the matrix arrays will come from HBM anyway: the automatic
@@ -1517,6 +1528,13 @@ int gkomi_diag_poisson3d_7pt_f64_i64(gkomi_stream_t s, int64_t g, int64_t* row_p
  * tracker found evicted from the Infinity Cache (more than 256 MiB of other CSR applies since
  * its last one) and that therefore read the matrix with nontemporal loads. */
 int64_t gkomi_diag_csr_evicted_applies(void);
+/* Diagnostics: the stride s of the row-major lane order that the nonzero-split launchers
+ * (gkomi_csr_spmv_srow_f64_i32 / _i64, the fused Krylov drivers) take for a matrix with these
+ * statistics and this srow tile, 0 when they keep the lane order of record; variant = bits 8-15
+ * of the strategy word (see GKOMI_CSR_SPLIT).  Host code only. */
+int64_t gkomi_diag_csr_split_row_stride(int64_t nrows, int64_t nnz, int64_t nrhs,
+                                        int64_t max_row_nnz_hint, int64_t srow_tile,
+                                        int64_t variant);
 int64_t gkomi_cg_persistent_solves(void);
 /* Process-wide switch of the single-launch CG (what GKOMI_CG_PERSISTENT sets at
  * start-up): 0 = off (every solve runs the three-launch iteration), 1 = on. */

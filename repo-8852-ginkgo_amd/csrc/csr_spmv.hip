@@ -295,8 +295,33 @@ __device__ __forceinline__ double add_products(double sum, const double* prod, i
 #ifndef GKOMI_GATHER_PROBE
 #define GKOMI_GATHER_PROBE 0
 #endif
+//
+// RowMajor = true: the lanes walk along the ROWS in the gather of b.  Above, lane l of gather instruction j holds
+// nonzero 256 j + l of the tile: on a stencil the columns of neighbouring lanes jump from band to band (r - 1000, r - 1,
+// r, r + 1, r + 1000, then the next row).  Here wave w owns the contiguous segment [w * 64 S, (w + 1) * 64 S) of the
+// tile (S = Tile / Block sweeps), streams it as before (lane l of load j takes segment slot 64 j + l: coalesced,
+// branch-free, the address from blockIdx alone), and transposes it through LDS -- written lane-linear, read back at
+//     n(j, l) = l * s + j  for j < s,    64 j + l  for s <= j < S        (a bijection of the segment for 1 <= s <= S)
+// with s = row_stride, the row length the caller promises (launcher: only for matrices whose rows nearly all have
+// it; a stride that does not match the rows makes one instruction touch every band of ~55 rows).  Lane l then holds
+// the whole of "row" l of the segment and neighbouring lanes gather neighbouring entries of b in every instruction
+// (adjacent-address lane pairs 0.40 -> 0.90 on the 5-pt stencil).  The columns go through LDS before the gathers, the
+// VALUES (not the gathered b) behind them, while the gathers are in flight: behind the gather the path stays
+// multiply -> ds_write -> barrier.  Product n is stored to the slot it has always had (segment base + n), so the row
+// sums, the over-read, the finish-from-memory loops, sparse-rows mode and the dot epilogue are the code above and
+// the bits cannot change: the same multiply of the same operands in the same slot, every row added by one thread.
+// The staging area is the wave's own segment of prod: columns first, values over them, products over those.  LDS
+// executes one wave's instructions in order and wave_lds_fence() keeps the compiler from reordering them, so every
+// read sees the write before it and none after it; no other wave touches the segment before the workgroup barrier.
+// No __syncthreads() (it would wait for the values still in flight: vmcnt(0)) and no LDS beyond prod.
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 template <typename I, int Block, int Tile, int MaxOver, bool Advanced, bool Swizzle,
-          bool Dot = false, bool NT = false, bool ColsFirst = true>
+          bool Dot = false, bool NT = false, bool ColsFirst = true, bool RowMajor = false>
 __global__ __launch_bounds__(Block) void csr_split_kernel(
     I nrows, typename index_traits<I>::pos nnz, const I* __restrict__ row_ptrs,
     const I* __restrict__ col_idxs, const double* __restrict__ vals,
@@ -307,7 +332,8 @@ __global__ __launch_bounds__(Block) void csr_split_kernel(
     double* __restrict__ dot_partial = nullptr,
     const uint8_t* __restrict__ stop_status = nullptr,
     const double* __restrict__ dot_w = nullptr,
-    double* __restrict__ dot_partial2 = nullptr
+    double* __restrict__ dot_partial2 = nullptr,
+    int row_stride = 0  // RowMajor: s, 1 <= s <= Tile / Block
 #ifdef GKOMI_TIMELINE
     , unsigned long long* __restrict__ stamps = nullptr
 #endif
@@ -316,6 +342,7 @@ __global__ __launch_bounds__(Block) void csr_split_kernel(
     using pos_t = typename index_traits<I>::pos;
     constexpr int sweeps = Tile / Block;
     static_assert(Tile % Block == 0, "tile must be a whole number of sweeps");
+    static_assert(!RowMajor || (ColsFirst && Block % wave_size == 0 && wave_size == 64), "row-major: whole waves of 64");
     static_assert(MaxOver <= Block, "one extra nonzero per lane at most");
     // tools/spmv_timeline.hip only: per-workgroup phase stamps (100 MHz
     // s_memrealtime, comparable across CUs) into a buffer nothing else reads
@@ -389,7 +416,17 @@ __global__ __launch_bounds__(Block) void csr_split_kernel(
     // the nonzeros behind the tile (rows that start in the tile and end behind
     // it); lanes past `over` repeat the last useful one (one request)
     const pos_t k_over = t0 + Tile + min(tid, max(over - 1, 0));
-    if (ColsFirst) {
+    // row-major: my wave's segment of the tile and my lane in it; load u takes segment slot 64 u + lane
+    const int lane = tid & (wave_size - 1);
+    const int seg = (tid - lane) * sweeps;
+    if (RowMajor) {
+#pragma unroll
+        for (int u = 0; u < sweeps; ++u) load_col(u, t0 + seg + u * wave_size + lane);
+        load_col(sweeps, k_over);
+#pragma unroll
+        for (int u = 0; u < sweeps; ++u) load_val(u, t0 + seg + u * wave_size + lane);
+        load_val(sweeps, k_over);
+    } else if (ColsFirst) {
 #pragma unroll
         for (int u = 0; u < sweeps; ++u) load_col(u, t0 + tid + u * Block);
         load_col(sweeps, k_over);
@@ -405,6 +442,11 @@ __global__ __launch_bounds__(Block) void csr_split_kernel(
         load_val(sweeps, k_over);
         load_col(sweeps, k_over);
     }
+
+    // row-major: slot n(u, lane) of my segment, worked out while the loads are in flight
+    int seg_slot[sweeps];
+#pragma unroll
+    for (int u = 0; u < sweeps; ++u) seg_slot[u] = RowMajor ? (u < row_stride ? lane * row_stride + u : u * wave_size + lane) : 0;
 
     // 2) row_ptrs of the rows that start in this tile
     double alpha = 1.0, beta = 0.0;
@@ -439,6 +481,18 @@ __global__ __launch_bounds__(Block) void csr_split_kernel(
         }
     }
 
+    // row-major: the columns through my segment of prod, written lane-linear, read transposed
+    if (RowMajor) {
+        typedef I __attribute__((may_alias)) staged_index;
+        staged_index* stage = reinterpret_cast<staged_index*>(prod + seg);
+#pragma unroll
+        for (int u = 0; u < sweeps; ++u) stage[u * wave_size + lane] = ci[u];
+        wave_lds_fence();
+#pragma unroll
+        for (int u = 0; u < sweeps; ++u) ci[u] = stage[seg_slot[u]];
+        wave_lds_fence();  // read before the values below overwrite them
+    }
+
     // 3) gather b (every loaded column is a stored one: always in bounds), products -> LDS
     double xv[sweeps + 1];
 #pragma unroll
@@ -453,12 +507,21 @@ __global__ __launch_bounds__(Block) void csr_split_kernel(
         xv[u] = b[ci[u] * b_stride];
 #endif
     }
+    if (RowMajor) {  // the values the same way, while the gathers are in flight
+        double* stage = prod + seg;
+#pragma unroll
+        for (int u = 0; u < sweeps; ++u) stage[u * wave_size + lane] = v[u];
+        wave_lds_fence();
+#pragma unroll
+        for (int u = 0; u < sweeps; ++u) v[u] = stage[seg_slot[u]];
+        // (no fence: product n goes to the slot this lane has just read)
+    }
 #pragma unroll
     for (int u = 0; u <= sweeps; ++u) {
         // reference order: (valpha * val) * b
         const double pr = Advanced ? (alpha * v[u]) * xv[u] : v[u] * xv[u];
         if (u < sweeps) {
-            prod[tid + u * Block] = pr;
+            prod[RowMajor ? seg + seg_slot[u] : tid + u * Block] = pr;
         } else {
             // unconditional (lanes past `over` repeat the last useful nonzero and
             // store the same product to the same slot): a branch here makes the
@@ -1099,7 +1162,7 @@ int launch_split(hipStream_t stream, bool swizzle, I nrows, typename index_trait
                  const I* row_ptrs, const I* col_idxs,
                  const double* vals, const double* b, int64_t b_stride,
                  double* c, int64_t c_stride, const double* alpha,
-                 const double* beta, const I* srow, int over, int chunk = 0)
+                 const double* beta, const I* srow, int over, int chunk = 0, int row_stride = 0)
 {
     constexpr int MaxOver = split_max_over;
     const int ntiles = static_cast<int>(nnz / Tile + 1);
@@ -1113,11 +1176,26 @@ int launch_split(hipStream_t stream, bool swizzle, I nrows, typename index_trait
         (csr_split_kernel<I, Block, Tile, MaxOver, ADV, SWZ, false, NT, true>), \
         grid, dim3(Block), 0, stream, nrows, nnz, row_ptrs, col_idxs, vals, b, \
         b_stride, c, c_stride, alpha, beta, srow, ntiles, per, over)
-    if (alpha != nullptr) {
+    // the row-major lane order (csr_split_row_stride says when)
+#define GKOMI_LAUNCH_RM(ADV, SWZ)                                              \
+    hipLaunchKernelGGL(                                                        \
+        (csr_split_kernel<I, Block, Tile, MaxOver, ADV, SWZ, false, NT, true, true>), \
+        grid, dim3(Block), 0, stream, nrows, nnz, row_ptrs, col_idxs, vals, b, \
+        b_stride, c, c_stride, alpha, beta, srow, ntiles, per, over, nullptr,  \
+        nullptr, nullptr, nullptr, row_stride)
+    if (row_stride > 0) {
+        if (row_stride > Tile / Block) return GKOMI_EINVAL;
+        if (alpha != nullptr) {
+            if (swz) GKOMI_LAUNCH_RM(true, true); else GKOMI_LAUNCH_RM(true, false);
+        } else {
+            if (swz) GKOMI_LAUNCH_RM(false, true); else GKOMI_LAUNCH_RM(false, false);
+        }
+    } else if (alpha != nullptr) {
         if (swz) GKOMI_LAUNCH(true, true); else GKOMI_LAUNCH(true, false);
     } else {
         if (swz) GKOMI_LAUNCH(false, true); else GKOMI_LAUNCH(false, false);
     }
+#undef GKOMI_LAUNCH_RM
 #undef GKOMI_LAUNCH
     return check_launch();
 }
@@ -1256,7 +1334,8 @@ namespace {
 template <int Tile>
 int launch_split_dot(hipStream_t stream, int nrows, int nnz, const int32_t* row_ptrs, const int32_t* col_idxs,
                      const double* vals, const double* p, double* q, double* partial, const uint8_t* stop_status,
-                     const int32_t* srow, int over, bool swizzle, bool nt, const double* dot_w, double* partial2)
+                     const int32_t* srow, int over, bool swizzle, bool nt, const double* dot_w, double* partial2,
+                     int row_stride)
 {
     constexpr int Block = 256;
     const int ntiles = nnz / Tile + 1;
@@ -1270,11 +1349,24 @@ int launch_split_dot(hipStream_t stream, int nrows, int nnz, const int32_t* row_
     hipLaunchKernelGGL((csr_split_kernel<int32_t, Block, Tile, split_max_over, false, SWZ, true, NT, true>), grid, \
                        dim3(Block), 0, stream, nrows, nnz, row_ptrs, col_idxs, vals, p, int64_t{1}, q,    \
                        int64_t{1}, nullptr, nullptr, srow, ntiles, per, over, partial, stop_status, dot_w, partial2)
-    if (swz) {
+#define GKOMI_SPLIT_DOT_RM(SWZ, NT)                                                                       \
+    hipLaunchKernelGGL((csr_split_kernel<int32_t, Block, Tile, split_max_over, false, SWZ, true, NT, true, true>), grid, \
+                       dim3(Block), 0, stream, nrows, nnz, row_ptrs, col_idxs, vals, p, int64_t{1}, q,    \
+                       int64_t{1}, nullptr, nullptr, srow, ntiles, per, over, partial, stop_status, dot_w, partial2, \
+                       row_stride)
+    if (row_stride > 0) {  // the row-major lane order (csr_split_row_stride)
+        if (row_stride > Tile / Block) return GKOMI_EINVAL;
+        if (swz) {
+            if (nt) GKOMI_SPLIT_DOT_RM(true, true); else GKOMI_SPLIT_DOT_RM(true, false);
+        } else {
+            if (nt) GKOMI_SPLIT_DOT_RM(false, true); else GKOMI_SPLIT_DOT_RM(false, false);
+        }
+    } else if (swz) {
         if (nt) GKOMI_SPLIT_DOT(true, true); else GKOMI_SPLIT_DOT(true, false);
     } else {
         if (nt) GKOMI_SPLIT_DOT(false, true); else GKOMI_SPLIT_DOT(false, false);
     }
+#undef GKOMI_SPLIT_DOT_RM
 #undef GKOMI_SPLIT_DOT
     return check_launch();
 }
@@ -1319,19 +1411,41 @@ int compress_partials_launch(hipStream_t stream, const double* raw, int nraw, do
 int csr_split_dot_launch(hipStream_t stream, int nrows, int64_t nnz, const int32_t* row_ptrs,
                          const int32_t* col_idxs, const double* vals, const double* p, double* q,
                          double* partial, const uint8_t* stop_status, const int32_t* srow, int64_t tile,
-                         int over, bool swizzle, bool nontemporal, const double* dot_w, double* partial2)
+                         int over, bool swizzle, bool nontemporal, const double* dot_w, double* partial2, int row_stride)
 {
     if (csr_split_dot_num_partials(nnz, tile) <= 0) return GKOMI_ENOTSUPPORTED;
     const int z = static_cast<int>(nnz);
     if (tile == 1536) {
         return launch_split_dot<1536>(stream, nrows, z, row_ptrs, col_idxs, vals, p, q, partial, stop_status, srow,
-                                      over, swizzle, nontemporal, dot_w, partial2);
+                                      over, swizzle, nontemporal, dot_w, partial2, row_stride);
     } else if (tile == 2048) {
         return launch_split_dot<2048>(stream, nrows, z, row_ptrs, col_idxs, vals, p, q, partial, stop_status, srow,
-                                      over, swizzle, nontemporal, dot_w, partial2);
+                                      over, swizzle, nontemporal, dot_w, partial2, row_stride);
     }
     return launch_split_dot<3072>(stream, nrows, z, row_ptrs, col_idxs, vals, p, q, partial, stop_status, srow,
-                                  over, swizzle, nontemporal, dot_w, partial2);
+                                  over, swizzle, nontemporal, dot_w, partial2, row_stride);
+}
+
+// The stride s of the row-major lane order of the nonzero-split kernel (csr_split_kernel<..., RowMajor>), 0 for the
+// lane order of record.  Taken only where the rows are KNOWN to be regular: one right-hand side, a hint that fits
+// the tile's sweeps (2 <= hint <= S = tile / 256: 7-pt rows at tile 1536 stay as they are) and nearly every row as
+// long as the hint says, 64 nnz >= 63 hint nrows (deficit 0.08 % on the 1000^2 5-pt matrix, 0.33 % on 256^3 7-pt).  A
+// stride that does not match the rows is worse than none: 7-pt rows walked with stride 6 touch 35 lines of b per
+// gather instruction instead of 10.  Two more conditions come from the measurements (profiles/r06_rowmajor_gather.md):
+//   * s odd.  An even stride puts the transposed LDS reads and the product stores of neighbouring lanes on the same
+//     banks (s = 8: 8 lanes per bank); rows of 4 / 6 / 8 / 12 entries ran 2-15 % slower than in the lane order.
+//   * tile <= 1536.  The row-major instantiations of the larger tiles need 69-96 VGPRs, one or two waves per SIMD
+//     fewer than the lane order's; 7-pt rows at tile 3072 gained nothing on the 256^3 matrix (299.2 vs 299.9 us) and
+//     lost 2 % on a narrow band.
+// variant (the strategy word's bits 8-15) bit 4 forces the order for any rows, any tile and any number of columns
+// (s = the hint clamped to 1 .. S; s = 1 is the lane order of record), bit 8 forbids it.
+int csr_split_row_stride(int64_t nrows, int64_t nnz, int64_t nrhs, int64_t hint, int64_t tile, int variant)
+{
+    const int64_t sweeps = tile / 256;
+    if ((variant & 8) != 0 || sweeps < 1) return 0;
+    if ((variant & 4) != 0) return static_cast<int>(std::min(std::max<int64_t>(hint, 1), sweeps));
+    if (nrhs != 1 || hint < 2 || hint > sweeps || hint % 2 == 0 || tile > 1536) return 0;
+    return 64 * nnz >= 63 * hint * nrows ? static_cast<int>(hint) : 0;
 }
 
 // swizzle heuristic shared by the automatic strategy: XCD-chunked row blocks
@@ -1566,12 +1680,13 @@ extern "C" int gkomi_csr_spmv_srow_f64_i32(
             over = 0;
         }
         const int z = static_cast<int>(nnz);
+        const int row_stride = csr_split_row_stride(nrows, nnz, nrhs, max_row_nnz_hint, srow_tile, variant);
         for (int j = 0; j < r; ++j) {  // explicit strategy with several columns: one launch each
             int err = GKOMI_EINVAL;
 #define GKOMI_SPLIT_ARGS                                                            \
     stream, !no_swizzle, n, z, row_ptrs, col_idxs, vals, b + j, b_stride, c + j,    \
-        c_stride, alpha, beta, srow, over, chunk > 0 ? chunk : auto_chunk
-            // variant bit 2: nontemporal streams.  (Write-through stores of c, 8 or 16 bytes wide, and
+        c_stride, alpha, beta, srow, over, chunk > 0 ? chunk : auto_chunk, row_stride
+            // variant bit 2: nontemporal streams; bits 4 / 8: the row-major lane order forced / forbidden.  (Write-through stores of c, 8 or 16 bytes wide, and
             // nontemporal stores of c were measured and dropped: 17.2 / 16.9 vs 16.6 us cold,
             // profiles/r02_tune_split.log, r02_tune_ntstore.log.)
 #define GKOMI_SPLIT_TILE(BLOCK, TILE)                                               \
@@ -1787,13 +1902,16 @@ extern "C" int gkomi_csr_spmv_srow_f64_i64(gkomi_stream_t stream_, int64_t nrows
         }
         // streams from HBM: 16 consecutive tiles per XCD (see the int32 entry); resident: one eighth each
         const int chunk = resident ? 0 : 16;
+        // the row-major lane order: the rule of the int32 entry; variant bits 4 / 8 of an explicit GKOMI_CSR_SPLIT
+        const int row_stride = csr_split_row_stride(nrows, nnz, nrhs, max_row_nnz_hint, srow_tile,
+                                                    kind == GKOMI_CSR_SPLIT ? (strategy >> 8) & 0xff : 0);
         for (int j = 0; j < r; ++j) {
             int err;
 #define GKOMI_SPLIT64(TILE)                                                                                          \
     err = nt ? launch_split<256, TILE, true, int64_t>(stream, true, nrows, nnz, row_ptrs, col_idxs, vals, b + j, b_stride, \
-                                                      c + j, c_stride, alpha, beta, srow, over, chunk)               \
+                                                      c + j, c_stride, alpha, beta, srow, over, chunk, row_stride)   \
              : launch_split<256, TILE, false, int64_t>(stream, true, nrows, nnz, row_ptrs, col_idxs, vals, b + j,    \
-                                                       b_stride, c + j, c_stride, alpha, beta, srow, over, chunk)
+                                                       b_stride, c + j, c_stride, alpha, beta, srow, over, chunk, row_stride)
             if (srow_tile == 1536) {
                 GKOMI_SPLIT64(1536);
             } else if (srow_tile == 2048) {
@@ -1825,3 +1943,10 @@ extern "C" int gkomi_csr_spmv_f64_i64(gkomi_stream_t stream_, int64_t nrows, int
 
 /* diagnostics: how many automatic applies of this process found their matrix evicted (csr_probably_evicted) */
 extern "C" int64_t gkomi_diag_csr_evicted_applies(void) { return gkomi::csr_evicted_applies.load(); }
+
+/* diagnostics: the stride of the row-major lane order the nonzero-split launchers take for such a matrix, 0 = none */
+extern "C" int64_t gkomi_diag_csr_split_row_stride(int64_t nrows, int64_t nnz, int64_t nrhs, int64_t max_row_nnz_hint,
+                                                   int64_t srow_tile, int64_t variant)
+{
+    return gkomi::csr_split_row_stride(nrows, nnz, nrhs, max_row_nnz_hint, srow_tile, static_cast<int>(variant));
+}

@@ -17,7 +17,10 @@ int csr_split_dot_launch(hipStream_t stream, int nrows, int64_t nnz, const int32
                          const int32_t* col_idxs, const double* vals, const double* p, double* q,
                          double* partial, const uint8_t* stop_status, const int32_t* srow, int64_t tile,
                          int over, bool swizzle, bool nontemporal, const double* dot_w = nullptr,
-                         double* partial2 = nullptr);
+                         double* partial2 = nullptr, int row_stride = 0);
+// stride of the row-major lane order of the nonzero-split kernel for such a matrix (0: the lane order of record);
+// variant = bits 8-15 of the strategy word (csr_spmv.hip)
+int csr_split_row_stride(int64_t nrows, int64_t nnz, int64_t nrhs, int64_t hint, int64_t tile, int variant);
 bool csr_auto_swizzle(int64_t nrows, int64_t nnz);
 // `raw` partial sums -> at most spmv_dot_max_partials, in place order (each output = the sum of a run of
 // consecutive inputs, added in index order by one wave): what the consumers of a fused driver re-add
@@ -277,7 +280,7 @@ struct spmv_dot_plan {
     int num_partials = 0;  // what the consumers re-add (<= spmv_dot_max_partials once compressed)
     int raw_partials = 0;  // what the launch leaves (behind the compressed ones when there are more)
     bool csr = false, swizzle = false, split = false, nontemporal = false;
-    int over = 0;
+    int over = 0, row_stride = 0;
     sysmat A;
     explicit spmv_dot_plan(const sysmat& A_) : A(A_)
     {
@@ -301,6 +304,8 @@ struct spmv_dot_plan {
                 split = true;
                 raw_partials = nsplit;
                 over = A.hint < 0 ? 64 : (A.hint <= 1 ? 0 : static_cast<int>(A.hint / 2 * 2));
+                row_stride = csr_split_row_stride(A.n, A.nnz, 1, A.hint, A.srow_tile,
+                                                  kind == GKOMI_CSR_SPLIT ? (A.strategy >> 8) & 0xff : 0);
             }
         } else if (A.ctx != nullptr) {
             raw_partials = op_spmv_dot_num_partials(A.op, A.ctx);
@@ -319,7 +324,8 @@ struct spmv_dot_plan {
         int err;
         if (split) {
             err = csr_split_dot_launch(stream, static_cast<int>(A.n), A.nnz, A.row_ptrs, A.col_idxs, A.vals, in, out,
-                                       raw, stop_status, A.srow, A.srow_tile, over, swizzle, nontemporal, dot_w, raw2);
+                                       raw, stop_status, A.srow, A.srow_tile, over, swizzle, nontemporal, dot_w, raw2,
+                                       row_stride);
         } else if (csr) {
             err = csr_spmv_dot_launch(stream, static_cast<int>(A.n), A.nnz, A.row_ptrs, A.col_idxs,
                                       A.vals, in, out, raw, stop_status, swizzle, dot_w, raw2, nontemporal);
