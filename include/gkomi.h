@@ -1243,6 +1243,62 @@ int gkomi_par_ict_compute_factor_f64_i32(
     const int32_t* a_col_idxs, const double* a_vals, int64_t l_nnz,
     const int32_t* l_row_ptrs, const int32_t* l_col_idxs, double* l_vals,
     const void* analysis_workspace, size_t workspace_bytes);
+/* ---- ISAI: preconditioner::Isai (core/preconditioner/isai.cpp:121-265) ------
+ * The five kernels of core/preconditioner/isai_kernels.hpp with the results of
+ * reference/preconditioner/isai_kernels.cpp, bit for bit; <double, int32>.  M is
+ * the matrix to invert, rows sorted; the inverse arrives with its pattern (a
+ * sparsity power of M, rows sorted) and receives its values.  The caller owns
+ * every allocation; every entry rejects bad arguments before any HIP call
+ * (GKOMI_EINVAL for sizes and pointers, GKOMI_EWORKSPACE for a missing or short
+ * workspace); nothing here blocks.
+ *
+ * generate_tri_inverse (:192-236) / generate_general_inverse (:268-331), both
+ * over generic_generate (:80-188).  A row of the inverse with at most 32 entries
+ * (kernels::isai::row_size_limit) is solved directly: the dense system
+ * M[S(i), S(i)] is gathered by matching the sorted rows of M against the row's
+ * pattern, zero where M stores nothing; tri solves it by the reference's
+ * column-oriented substitution (lower: columns descending, upper: ascending),
+ * general by the reference's Gauss-Jordan elimination of the transposed system
+ * with the first maximum of |.| as pivot, spd additionally scales the row by
+ * 1 / sqrt(its last entry).  A value that is not finite becomes 1 on the diagonal
+ * and 0 elsewhere.  A longer row is left alone and counted: excess_rhs_ptrs and
+ * excess_nz_ptrs (n + 1 entries each) receive the exclusive prefix sums of the
+ * lengths of the long rows and of their numbers of matches.  lower / spd: 0 or 1.
+ * Workspace: gkomi_isai_generate_workspace_bytes(n). */
+size_t gkomi_isai_generate_workspace_bytes(int64_t n);
+int gkomi_isai_generate_tri_inverse_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* m_row_ptrs,
+    const int32_t* m_col_idxs, const double* m_vals, const int32_t* i_row_ptrs,
+    const int32_t* i_col_idxs, double* i_vals, int32_t* excess_rhs_ptrs,
+    int32_t* excess_nz_ptrs, int lower, void* workspace,
+    size_t workspace_bytes);
+int gkomi_isai_generate_general_inverse_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* m_row_ptrs,
+    const int32_t* m_col_idxs, const double* m_vals, const int32_t* i_row_ptrs,
+    const int32_t* i_col_idxs, double* i_vals, int32_t* excess_rhs_ptrs,
+    int32_t* excess_nz_ptrs, int spd, void* workspace, size_t workspace_bytes);
+/* generate_excess_system (:338-394): the block-diagonal system of the long rows
+ * of [e_start, e_end) and its right-hand side.  e_dim = excess_rhs_ptrs[e_end] -
+ * excess_rhs_ptrs[e_start] rows, e_nnz = the same difference of excess_nz_ptrs
+ * entries (the caller reads both prefix arrays on the host, as isai.cpp:184-190
+ * does); e_row_ptrs[e_dim + 1], e_col_idxs / e_vals[e_nnz], e_rhs[e_dim]. */
+int gkomi_isai_generate_excess_system_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* m_row_ptrs,
+    const int32_t* m_col_idxs, const double* m_vals, const int32_t* i_row_ptrs,
+    const int32_t* i_col_idxs, const int32_t* excess_rhs_ptrs,
+    const int32_t* excess_nz_ptrs, int64_t e_dim, int64_t e_nnz,
+    int32_t* e_row_ptrs, int32_t* e_col_idxs, double* e_vals, double* e_rhs,
+    int64_t e_start, int64_t e_end);
+/* scale_excess_solution (:401-422): every non-empty block of the solution times
+ * 1 / sqrt(its last entry) (spd).  scatter_excess_solution (:429-447): block
+ * `row` of the solution becomes the values of row `row` of the inverse. */
+int gkomi_isai_scale_excess_solution_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* excess_block_ptrs,
+    double* excess_solution, int64_t e_start, int64_t e_end);
+int gkomi_isai_scatter_excess_solution_f64_i32(
+    gkomi_stream_t s, int64_t n, const int32_t* excess_block_ptrs,
+    const double* excess_solution, const int32_t* i_row_ptrs, double* i_vals,
+    int64_t e_start, int64_t e_end);
 /* ---- sparse direct solver: symbolic Cholesky, Lu, solver::Direct -----------
  * experimental::factorization::Lu (core/factorization/lu.cpp:85-145),
  * symbolic_cholesky (core/factorization/symbolic.cpp:66-93), elimination_forest
@@ -2094,6 +2150,23 @@ int gkomi_jacobi_apply_cb(void* ctx, gkomi_stream_t s, const double* in,
                           double* out);
 int gkomi_ilu_apply_cb(void* ctx, gkomi_stream_t s, const double* in,
                        double* out);
+/* The generated state of preconditioner::Isai (include/ginkgo/core/preconditioner/
+ * isai.hpp: apply_impl is approximate_inverse_->apply): out = first * in, or with
+ * two matrices out = second * (first * in) through the intermediate vector --
+ * SpdIsai (L, then L^T) and preconditioner::Ilu / Ic over two Isai solvers (the
+ * lower inverse, then the upper one).  Each matrix is a gkomi_csr_ctx; with its
+ * srow the nonzero-split SpMV kernel runs.  The apply is
+ * gkomi_csr_spmv_srow_f64_i32 and nothing else. */
+typedef struct gkomi_isai_ctx {
+    int64_t n;
+    int64_t nrhs;            /* columns of the vectors (stride == nrhs) */
+    int64_t num_matrices;    /* 1 or 2 */
+    gkomi_csr_ctx first;
+    gkomi_csr_ctx second;    /* unused with one matrix */
+    double* intermediate;    /* n x nrhs scratch, two matrices only */
+} gkomi_isai_ctx;
+int gkomi_isai_apply_cb(void* ctx, gkomi_stream_t s, const double* in,
+                        double* out);
 
 /* ---- GMRES (core/solver/common_gmres_kernels.hpp, core/solver/gmres_kernels.hpp,
  *      driver core/solver/gmres.cpp:139-372) ------------------------------ */

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from ._lib import GkomiError
+from .formats import Csr, CsrCtx
 
 GKOMI_ENOTSUPPORTED = -2
 
@@ -862,6 +863,193 @@ def ic_generate(gk, n, row_ptrs, col_idxs, vals, nrhs=1, skip_sorting=False):
     Lt = _transpose(gk, n, *L)
     p = ilu_from_factors(gk, n, L, Lt, nrhs=nrhs)
     p.L, p.Lt, p.analysis = L, Lt, an
+    return p
+
+
+# ---- ISAI (core/preconditioner/isai.cpp:87-265) ----------------------------------------------------------------
+
+ISAI_KINDS = ("lower", "upper", "general", "spd")
+
+
+class IsaiCtx(ctypes.Structure):
+    """gkomi_isai_ctx (include/gkomi.h)."""
+    _fields_ = [("n", ctypes.c_int64), ("nrhs", ctypes.c_int64), ("num_matrices", ctypes.c_int64),
+                ("first", CsrCtx), ("second", CsrCtx), ("intermediate", ctypes.c_void_p)]
+
+
+def _check_isai(kind, n, row_ptrs, ncols, sparsity_power, excess_limit):
+    """GKO_ASSERT_IS_SQUARE_MATRIX and the parameter checks, before anything reaches the device"""
+    if kind not in ISAI_KINDS:
+        raise ValueError(f"unknown isai kind {kind!r}: one of {', '.join(ISAI_KINDS)}")
+    if int(sparsity_power) != sparsity_power or sparsity_power < 1:
+        raise ValueError(f"sparsity_power must be an integer >= 1, got {sparsity_power}")
+    if int(excess_limit) != excess_limit or excess_limit < 0:
+        raise ValueError(f"excess_limit must be an integer >= 0, got {excess_limit}")
+    if ncols is not None and ncols != n:
+        raise ValueError(f"Isai needs a square matrix, got {n} x {ncols}")
+    if int(row_ptrs.numel()) != n + 1:
+        raise ValueError(f"Isai needs a square matrix: {int(row_ptrs.numel()) - 1} rows of row pointers for n = {n}")
+
+
+def isai_extend_sparsity(gk, n, m, power):
+    """extend_sparsity (isai.cpp:87-118): m^power by square-and-multiply through csr::spgemm, as it is written there"""
+    if power == 1:
+        return m[0].clone(), m[1].clone(), m[2].clone()
+    id_power, acc = m, m
+    i = power - 1
+    while i > 1:
+        if i % 2 != 0:
+            acc = par_ilut_spgemm(gk, n, id_power, acc)
+            i -= 1
+        id_power = par_ilut_spgemm(gk, n, id_power, id_power)
+        i //= 2
+    return par_ilut_spgemm(gk, n, id_power, acc)
+
+
+def isai_generate_kernel(gk, kind, n, m, inverse):
+    """isai::generate_tri_inverse / generate_general_inverse on a pattern: fills the values of the short rows of
+    `inverse` in place -> (excess_rhs_ptrs, excess_nz_ptrs), device int32 arrays of n + 1 entries"""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = m[2].device
+    rhs_ptrs = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    nz_ptrs = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    nb = gk.isai_generate_workspace_bytes(n)
+    ws = _bytes(nb, dv)
+    if kind in ("lower", "upper"):
+        gk.isai_generate_tri_inverse_f64_i32(s, n, *m, *inverse, rhs_ptrs, nz_ptrs, int(kind == "lower"), ws, nb)
+    else:
+        gk.isai_generate_general_inverse_f64_i32(s, n, *m, *inverse, rhs_ptrs, nz_ptrs, int(kind == "spd"), ws, nb)
+    return rhs_ptrs, nz_ptrs
+
+
+def isai_excess_system(gk, n, m, inverse, rhs_ptrs, nz_ptrs, e_dim, e_nnz, e_start, e_end):
+    """isai::generate_excess_system -> ((row_ptrs, col_idxs, vals), rhs)"""
+    s = torch.cuda.current_stream().cuda_stream
+    dv = m[2].device
+    erp = torch.zeros(e_dim + 1, dtype=torch.int32, device=dv)
+    ec, ev = _empty_csr(e_dim, e_nnz, dv)
+    rhs = torch.zeros(e_dim, dtype=torch.float64, device=dv)
+    gk.isai_generate_excess_system_f64_i32(s, n, *m, inverse[0], inverse[1], rhs_ptrs, nz_ptrs, e_dim, e_nnz, erp, ec, ev,
+                                           rhs, e_start, e_end)
+    return (erp, ec, ev), rhs
+
+
+def isai_gmres_excess_solver(gk, e_dim, system, rhs, x):
+    """The reference's default for general and spd (isai.cpp:230-244): GMRES with block-Jacobi(32), at most e_dim
+    iterations, residual reduction 1e-6 against the norm of the rhs; x comes in as the initial guess."""
+    pre = jacobi_generate(gk, e_dim, *system, max_block_size=32)
+    gmres_solve(gk, e_dim, *system, rhs, x=x, max_iters=e_dim, reduction=1e-6, baseline="rhs_norm", precond=pre)
+    return x
+
+
+def _isai_trs_excess_solver(lower):
+    def solve(gk, e_dim, system, rhs, x):
+        s = torch.cuda.current_stream().cuda_stream
+        nb = gk.trs_workspace_bytes()
+        ws = torch.zeros(nb, dtype=torch.uint8, device=rhs.device)
+        (gk.lower_trs_solve_f64_i32 if lower else gk.upper_trs_solve_f64_i32)(s, e_dim, 1, *system, 0, rhs, 1, x, 1, ws, nb)
+        return x
+    return solve
+
+
+def isai_generate(gk, kind, n, row_ptrs, col_idxs, vals, sparsity_power=1, excess_limit=0, skip_sorting=False,
+                  excess_solver=None, ncols=None, trace=None):
+    """Isai::generate_inverse (core/preconditioner/isai.cpp:121-265) for kind in "lower", "upper", "general", "spd":
+    a sorted copy, for spd its lower part (initialize_l, diag_sqrt = false), the sparsity power, the generate kernel,
+    then the long rows block by block over excess_limit (0: one block): excess system, transpose, solve -- UpperTrs for
+    lower, LowerTrs for upper, GMRES with block-Jacobi(32) for general and spd, or excess_solver(gk, dim, system, rhs,
+    x) -- scale (spd) and scatter.  Returns the inverse as CSR; for spd (L, L^T).
+    trace: a dict that receives the prefix arrays (host) and the (start, end) of every block."""
+    _check_isai(kind, n, row_ptrs, ncols, sparsity_power, excess_limit)
+    s = torch.cuda.current_stream().cuda_stream
+    to_invert = (row_ptrs, *_sorted_copy(gk, n, row_ptrs, col_idxs, vals, skip_sorting))
+    if kind != "spd":
+        inverted = isai_extend_sparsity(gk, n, to_invert, sparsity_power)
+    else:
+        base = _split_l(gk, n, *to_invert, diag_sqrt=False)
+        inverted = base if sparsity_power == 1 else isai_extend_sparsity(gk, n, base, sparsity_power)
+    rhs_ptrs, nz_ptrs = isai_generate_kernel(gk, kind, n, to_invert, inverted)
+    host_rhs_ptrs, host_nz_ptrs = rhs_ptrs.cpu().numpy(), nz_ptrs.cpu().numpy()
+    total = int(host_rhs_ptrs[n])
+    lim = total if excess_limit == 0 else int(excess_limit)
+    if trace is not None:
+        trace.update(excess_rhs_ptrs=host_rhs_ptrs, excess_nz_ptrs=host_nz_ptrs, blocks=[])
+    if excess_solver is None:
+        excess_solver = (isai_gmres_excess_solver if kind in ("general", "spd") else _isai_trs_excess_solver(kind == "upper"))
+    block = 0
+    while total > 0 and block < n:
+        start = block
+        e_dim = 0
+        while e_dim < lim and block < n:
+            block += 1
+            e_dim = int(host_rhs_ptrs[block] - host_rhs_ptrs[start])
+        if e_dim == 0:
+            break
+        e_nnz = int(host_nz_ptrs[block] - host_nz_ptrs[start])
+        system, rhs = isai_excess_system(gk, n, to_invert, inverted, rhs_ptrs, nz_ptrs, e_dim, e_nnz, start, block)
+        tws = _bytes(gk.csr_transpose_workspace_bytes(e_dim), rhs.device)
+        trp = torch.zeros(e_dim + 1, dtype=torch.int32, device=rhs.device)
+        tc, tv = torch.zeros_like(system[1]), torch.zeros_like(system[2])
+        gk.csr_transpose_f64_i32(s, e_dim, e_dim, e_nnz, *system, trp, tc, tv, tws, int(tws.numel()))
+        solution = excess_solver(gk, e_dim, (trp, tc, tv), rhs, rhs.clone())
+        if kind == "spd":
+            gk.isai_scale_excess_solution_f64_i32(s, n, rhs_ptrs, solution, start, block)
+        gk.isai_scatter_excess_solution_f64_i32(s, n, rhs_ptrs, solution, inverted[0], inverted[2], start, block)
+        if trace is not None:
+            trace["blocks"].append((start, block))
+    if kind == "spd":
+        return inverted, _transpose(gk, n, *inverted)
+    return inverted
+
+
+def _isai_csr_ctx(gk, n, m, keep):
+    """the gkomi_csr_ctx of an inverse, with its srow and its longest row"""
+    c = Csr(gk, n, n, *m)
+    keep.append(c)
+    return c.callback().ctx
+
+
+def isai_from_inverses(gk, n, first, second=None, nrhs=1):
+    """The Preconditioner over gkomi_isai_apply_cb: x = first b, or x = second (first b)."""
+    keep = [first, second]
+    c1 = _isai_csr_ctx(gk, n, first, keep)
+    c2 = _isai_csr_ctx(gk, n, second, keep) if second is not None else type(c1)()
+    inter = torch.zeros((n, nrhs), dtype=torch.float64, device=first[2].device) if second is not None else None
+    keep.append(inter)
+    ctx = IsaiCtx(n, nrhs, 1 if second is None else 2, c1, c2, inter.data_ptr() if inter is not None else None)
+    p = Preconditioner(gk, "gkomi_isai_apply_cb", ctx, keep)
+    p.inverses = (first,) if second is None else (first, second)
+    return p
+
+
+def isai_preconditioner(gk, kind, n, row_ptrs, col_idxs, vals, sparsity_power=1, excess_limit=0, skip_sorting=False,
+                        nrhs=1, excess_solver=None):
+    """preconditioner::Isai<kind>::generate: LowerIsai / UpperIsai / GeneralIsai apply one SpMV, SpdIsai two (L, L^T)"""
+    inv = isai_generate(gk, kind, n, row_ptrs, col_idxs, vals, sparsity_power, excess_limit, skip_sorting, excess_solver)
+    return isai_from_inverses(gk, n, *inv, nrhs=nrhs) if kind == "spd" else isai_from_inverses(gk, n, inv, nrhs=nrhs)
+
+
+def ilu_isai_from_factors(gk, n, L, U, sparsity_power=1, excess_limit=0, skip_sorting=False, nrhs=1):
+    """preconditioner::Ilu (or Ic, with U = L^T) with LowerIsai and UpperIsai as its solvers: x = U^-1 (L^-1 b) as two
+    SpMVs.  .l_inverse / .u_inverse hold the approximate inverses."""
+    for f in (L, U):
+        _check_isai("lower", n, f[0], None, sparsity_power, excess_limit)
+    li = isai_generate(gk, "lower", n, *L, sparsity_power, excess_limit, skip_sorting)
+    ui = isai_generate(gk, "upper", n, *U, sparsity_power, excess_limit, skip_sorting)
+    p = isai_from_inverses(gk, n, li, ui, nrhs=nrhs)
+    p.l_inverse, p.u_inverse = li, ui
+    return p
+
+
+def ic_isai_from_factor(gk, n, L, sparsity_power=1, excess_limit=0, skip_sorting=False, nrhs=1):
+    """preconditioner::Ic with LowerIsai as its solver: the second solver is the transpose of the first (ic.hpp:327-328),
+    not an UpperIsai of L^T -- the two differ, and only this one keeps the preconditioner symmetric for CG.
+    .l_inverse / .u_inverse hold the approximate inverse and its transpose."""
+    _check_isai("lower", n, L[0], None, sparsity_power, excess_limit)
+    li = isai_generate(gk, "lower", n, *L, sparsity_power, excess_limit, skip_sorting)
+    ui = _transpose(gk, n, *li)
+    p = isai_from_inverses(gk, n, li, ui, nrhs=nrhs)
+    p.l_inverse, p.u_inverse = li, ui
     return p
 
 

@@ -2004,6 +2004,22 @@ struct matrix_callback {
         return 0;
     }
 };
+// A Csr as the record of gkomi_csr_matrix_apply_cb (and of gkomi_isai_apply_cb): the matrix travels with its srow and
+// its row statistic, so the drivers run the kernel Csr::apply runs, also inside their fused SpMV + dot launches
+inline void fill_csr_ctx(const matrix::Csr<double, int32>* c, gkomi_csr_ctx& csr)
+{
+    c->make_srow();
+    csr.nrows = static_cast<int64_t>(c->get_size()[0]);
+    csr.ncols = static_cast<int64_t>(c->get_size()[1]);
+    csr.nnz = static_cast<int64_t>(c->get_num_stored_elements());
+    csr.row_ptrs = c->get_const_row_ptrs();
+    csr.col_idxs = c->get_const_col_idxs();
+    csr.vals = c->get_const_values();
+    csr.strategy = c->get_strategy()->get_code();
+    csr.max_row_nnz_hint = c->get_max_row_nnz();
+    csr.srow = c->get_num_srow_elements() ? c->get_const_srow() : nullptr;
+    csr.srow_tile = c->get_num_srow_elements() ? c->get_srow_tile() : 0;
+}
 // The system matrix of a solver as (gkomi_matrix_apply_fn, context): Ell and
 // Sellp go by the library's own callbacks + records, which the fused drivers
 // recognise (SpMV with the dot-product epilogue, csrc/formats.hip), Fbcsr by its
@@ -2021,19 +2037,7 @@ struct system_callback {
         : generic{A, std::move(exec), n}, fn(&matrix_callback::call), ctx(&generic)
     {
         if (auto c = dynamic_cast<const matrix::Csr<double, int32>*>(A)) {
-            // the matrix travels with its srow and its row statistic: the drivers then run the kernel
-            // Csr::apply runs, also inside their fused SpMV + dot launches
-            c->make_srow();
-            csr.nrows = static_cast<int64_t>(c->get_size()[0]);
-            csr.ncols = static_cast<int64_t>(c->get_size()[1]);
-            csr.nnz = static_cast<int64_t>(c->get_num_stored_elements());
-            csr.row_ptrs = c->get_const_row_ptrs();
-            csr.col_idxs = c->get_const_col_idxs();
-            csr.vals = c->get_const_values();
-            csr.strategy = c->get_strategy()->get_code();
-            csr.max_row_nnz_hint = c->get_max_row_nnz();
-            csr.srow = c->get_num_srow_elements() ? c->get_const_srow() : nullptr;
-            csr.srow_tile = c->get_num_srow_elements() ? c->get_srow_tile() : 0;
+            fill_csr_ctx(c, csr);
             fn = &gkomi_csr_matrix_apply_cb;
             ctx = &csr;
         } else if (auto e = dynamic_cast<const matrix::Ell<double, int32>*>(A)) {
@@ -3354,10 +3358,264 @@ protected:
 }  // namespace factorization
 
 // ---- preconditioner::Ilu and Ic (include/ginkgo/core/preconditioner/ilu.hpp:265-305, ic.hpp) -------------------------
+// ---- Composition (include/ginkgo/core/base/composition.hpp): what SpdIsai needs of it and no more -- create from
+// operators, get_operators(), and the apply through intermediates: x = op[0] (op[1] (... op[k-1] b)).
+template <typename V = double>
+class Composition : public LinOp {
+public:
+    template <typename... Rest>
+    static std::unique_ptr<Composition> create(std::shared_ptr<const LinOp> first, Rest&&... rest)
+    {
+        std::unique_ptr<Composition> c(new Composition(first->get_executor()));
+        c->add(std::move(first));
+        int each[] = {0, (c->add(std::shared_ptr<const LinOp>(std::forward<Rest>(rest))), 0)...};
+        (void)each;
+        return c;
+    }
+    const std::vector<std::shared_ptr<const LinOp>>& get_operators() const noexcept { return operators_; }
+protected:
+    explicit Composition(std::shared_ptr<const Executor> exec) : LinOp(std::move(exec)) {}
+    void add(std::shared_ptr<const LinOp> op)
+    {
+        if (!operators_.empty() && operators_.back()->get_size()[1] != op->get_size()[0]) {
+            throw DimensionMismatch(__FILE__, __LINE__, "Composition: the operators do not conform");
+        }
+        operators_.push_back(std::move(op));
+        this->set_size(dim<2>(operators_.front()->get_size()[0], operators_.back()->get_size()[1]));
+    }
+    void apply_impl(const LinOp* b, LinOp* x) const override
+    {
+        std::vector<std::unique_ptr<matrix::Dense<V>>> mids;
+        const LinOp* in = b;
+        for (size_type k = operators_.size(); k-- > 1;) {
+            mids.push_back(matrix::Dense<V>::create(exec_, dim<2>(operators_[k]->get_size()[0], b->get_size()[1])));
+            operators_[k]->apply(in, mids.back().get());
+            in = mids.back().get();
+        }
+        operators_[0]->apply(in, x);
+    }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
+    {
+        auto dx = matrix::detail_fmt::dense(x);
+        auto x_clone = dx->clone();
+        this->apply_impl(b, x_clone.get());
+        dx->scale(matrix::detail_fmt::dense(beta));
+        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
+    }
+    std::vector<std::shared_ptr<const LinOp>> operators_;
+};
+
 namespace preconditioner {
+// ---- Isai (include/ginkgo/core/preconditioner/isai.hpp, core/preconditioner/isai.cpp:87-265) --------------------------
+// The incomplete sparse approximate inverse of a triangular, general or spd matrix on the sparsity pattern of one of
+// its powers, generated on the device by the gkomi_isai_* kernels with the reference executor's results; every apply is
+// one CSR SpMV (two for spd).  <double, int32>.
+enum struct isai_type { lower, upper, general, spd };
+
 namespace detail {
-// What Ilu and Ic share: the two factors of whatever generates them, the triangular solvers over them, and the apply
-// through one intermediate vector.
+using ::gko::detail::fill_csr_ctx;
+// the record of gkomi_isai_apply_cb over one or two inverses; mid: n x nrhs scratch for two
+inline void fill_isai_ctx(gkomi_isai_ctx& r, size_type n, size_type nrhs, const matrix::Csr<double, int32>* first, const matrix::Csr<double, int32>* second, double* mid)
+{
+    r = gkomi_isai_ctx{};
+    r.n = static_cast<int64_t>(n);
+    r.nrhs = static_cast<int64_t>(nrhs);
+    r.num_matrices = second != nullptr ? 2 : 1;
+    fill_csr_ctx(first, r.first);
+    if (second != nullptr) fill_csr_ctx(second, r.second);
+    r.intermediate = mid;
+}
+}  // namespace detail
+
+template <isai_type Type, typename V = double, typename I = int32>
+class Isai : public LinOp, public Transposable, public ::gko::detail::native_preconditioner {
+    template <isai_type, typename, typename>
+    friend class Isai;
+public:
+    using value_type = V;
+    using index_type = I;
+    using Csr = matrix::Csr<V, I>;
+    using Comp = Composition<V>;
+    using transposed_type = Isai<Type == isai_type::general ? isai_type::general : Type == isai_type::spd ? isai_type::spd : Type == isai_type::lower ? isai_type::upper : isai_type::lower, V, I>;
+    using inverse_type = typename std::conditional<Type == isai_type::spd, Comp, Csr>::type;
+    static constexpr isai_type type{Type};
+
+    class Factory : public LinOpFactory {
+    public:
+        Factory() : LinOpFactory(nullptr) {}
+        Factory& with_skip_sorting(bool s) { skip_sorting_ = s; return *this; }
+        Factory& with_sparsity_power(int p) { sparsity_power_ = p; return *this; }
+        Factory& with_excess_limit(size_type l) { excess_limit_ = l; return *this; }
+        Factory& with_excess_solver_factory(std::shared_ptr<const LinOpFactory> f) { excess_solver_factory_ = std::move(f); return *this; }
+        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
+        std::unique_ptr<Isai> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Isai>(new Isai(*this, std::move(A))); }
+        std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
+        bool skip_sorting_{false};
+        int sparsity_power_{1};
+        size_type excess_limit_{0};
+        std::shared_ptr<const LinOpFactory> excess_solver_factory_;
+    };
+    static Factory build() { return Factory{}; }
+
+    // the approximate inverse: a Csr, for spd the Composition (L^T, L)
+    std::shared_ptr<const inverse_type> get_approximate_inverse() const { return std::dynamic_pointer_cast<const inverse_type>(approximate_inverse_); }
+
+    // isai.cpp:321-345: spd is its own transpose, any other kind the transposed kind over the transposed inverse
+    std::unique_ptr<LinOp> transpose() const override
+    {
+        if (Type == isai_type::spd) return std::unique_ptr<LinOp>(new Isai(*this));
+        std::unique_ptr<transposed_type> t(new transposed_type(exec_, dim<2>(size_[1], size_[0])));
+        t->approximate_inverse_ = share(dynamic_cast<const Csr&>(*approximate_inverse_).transpose());
+        return std::unique_ptr<LinOp>(t.release());
+    }
+
+    // one SpMV, or L then L^T, as gkomi_isai_apply_cb + record
+    bool native_callback(gkomi_apply_fn& fn, void*& ctx, size_type nrhs) const override
+    {
+        if (!std::is_same<V, double>::value || !std::is_same<I, int32>::value || !approximate_inverse_) return false;
+        const size_type n = size_[0];
+        if (Type == isai_type::spd) {
+            const auto& ops = dynamic_cast<const Comp&>(*approximate_inverse_).get_operators();
+            if (mid_.get_num_elems() != n * nrhs || mid_.get_executor() == nullptr) mid_ = array<V>(exec_, n * nrhs);
+            ::gko::preconditioner::detail::fill_isai_ctx(record_, n, nrhs, dynamic_cast<const Csr*>(ops[1].get()), dynamic_cast<const Csr*>(ops[0].get()), mid_.get_data());
+        } else {
+            ::gko::preconditioner::detail::fill_isai_ctx(record_, n, nrhs, dynamic_cast<const Csr*>(approximate_inverse_.get()), nullptr, nullptr);
+        }
+        fn = &gkomi_isai_apply_cb;
+        ctx = &record_;
+        return true;
+    }
+    // the inverse as a Csr (not for spd): what Ilu / Ic put into their two-SpMV record
+    const Csr* inverse_csr() const { return dynamic_cast<const Csr*>(approximate_inverse_.get()); }
+
+protected:
+    Isai(std::shared_ptr<const Executor> exec, dim<2> size) : LinOp(std::move(exec), size) {}
+    Isai(const Isai&) = default;
+    Isai(const Factory& f, std::shared_ptr<const LinOp> A) : LinOp(f.get_executor(), A->get_size())
+    {
+        generate_inverse(A.get(), f.skip_sorting_, f.sparsity_power_, f.excess_limit_, f.excess_solver_factory_);
+    }
+    void apply_impl(const LinOp* b, LinOp* x) const override { approximate_inverse_->apply(b, x); }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override { approximate_inverse_->apply(alpha, b, beta, x); }
+
+    // Isai::generate_inverse (isai.cpp:121-265)
+    void generate_inverse(const LinOp* input, bool skip_sorting, int power, size_type excess_limit, const std::shared_ptr<const LinOpFactory>& excess_solver_factory)
+    {
+        namespace fd = ::gko::factorization::detail;
+        using arrays = fd::csr_arrays<V, I>;
+        using view = fd::csr_view<V, I>;
+        using Dense = matrix::Dense<V>;
+        constexpr bool is_lower = Type == isai_type::lower, is_spd = Type == isai_type::spd;
+        constexpr bool is_tri = is_lower || Type == isai_type::upper;
+        if (power < 1) throw ValueMismatch(__FILE__, __LINE__, "Isai: sparsity_power must be at least 1");
+        fd::source<V, I> src(exec_, input, "isai::generate_inverse", "Isai", !skip_sorting);
+        const size_type n = src.n;
+        const view m(src.mtx);
+        auto copy_of = [&](view a) {
+            arrays c(exec_, a.n, static_cast<size_type>(a.nnz));
+            exec_->copy(a.n + 1, a.rp, c.rp.get_data());
+            exec_->copy(static_cast<size_type>(a.nnz), a.ci, c.ci.get_data());
+            exec_->copy(static_cast<size_type>(a.nnz), a.v, c.v.get_data());
+            return c;
+        };
+        // extend_sparsity (:87-118): square-and-multiply through csr::spgemm, as it is written there
+        auto extend = [&](view a) {
+            if (power == 1) return copy_of(a);
+            array<char> ws(exec_, gkomi_csr_spgemm_workspace_bytes(n, n));
+            arrays id_power = copy_of(a), acc = copy_of(a);
+            auto product = [&](const arrays& p, const arrays& q) {
+                arrays r = fd::spgemm(exec_, view(p), view(q), ws);
+                exec_->synchronize();  // before an operand is released
+                return r;
+            };
+            int i = power - 1;
+            while (i > 1) {
+                if (i % 2 != 0) {
+                    acc = product(id_power, acc);
+                    i--;
+                }
+                id_power = product(id_power, id_power);
+                i /= 2;
+            }
+            return product(id_power, acc);
+        };
+        arrays inv;
+        if (!is_spd) {
+            inv = extend(m);
+        } else {
+            arrays base = fd::split_l(exec_, m, false);
+            exec_->synchronize();
+            inv = power == 1 ? std::move(base) : extend(view(base));
+        }
+        array<I> rhs_ptrs(exec_, n + 1), nz_ptrs(exec_, n + 1);
+        {
+            array<char> ws(exec_, gkomi_isai_generate_workspace_bytes(n) + 8);
+            auto gen = is_tri ? gkomi_isai_generate_tri_inverse_f64_i32 : gkomi_isai_generate_general_inverse_f64_i32;
+            GKOMI_CALL(gen(nullptr, n, m.rp, m.ci, m.v, inv.rp.get_const_data(), inv.ci.get_const_data(), inv.v.get_data(), rhs_ptrs.get_data(), nz_ptrs.get_data(),
+                           is_tri ? (is_lower ? 1 : 0) : (is_spd ? 1 : 0), ws.get_data(), ws.get_num_elems()));
+            exec_->synchronize();
+        }
+        const auto host_rhs = rhs_ptrs.to_host(), host_nz = nz_ptrs.to_host();
+        const size_type total = static_cast<size_type>(host_rhs[n]);
+        const size_type lim = excess_limit == 0 ? total : excess_limit;
+        size_type block = 0;
+        while (total > 0 && block < n) {
+            const size_type start = block;
+            size_type e_dim = 0;
+            for (; e_dim < lim && block < n; e_dim = static_cast<size_type>(host_rhs[block] - host_rhs[start])) block++;
+            if (e_dim == 0) break;
+            const size_type e_nnz = static_cast<size_type>(host_nz[block] - host_nz[start]);
+            arrays sys(exec_, e_dim, e_nnz);
+            auto rhs = Dense::create(exec_, dim<2>(e_dim, 1));
+            auto sol = Dense::create(exec_, dim<2>(e_dim, 1));
+            GKOMI_CALL(gkomi_isai_generate_excess_system_f64_i32(nullptr, n, m.rp, m.ci, m.v, inv.rp.get_const_data(), inv.ci.get_const_data(), rhs_ptrs.get_const_data(),
+                                                                 nz_ptrs.get_const_data(), e_dim, e_nnz, sys.rp.get_data(), sys.ci.get_data(), sys.v.get_data(), rhs->get_values(), start,
+                                                                 block));
+            std::shared_ptr<const LinOp> sys_t = fd::transposed(exec_, view(sys)).to_csr();
+            std::shared_ptr<const LinOpFactory> solver_factory;
+            if (excess_solver_factory) {
+                solver_factory = excess_solver_factory;
+                sol->copy_from(rhs.get());
+            } else if (!is_tri) {
+                solver_factory = solver::Gmres<V>::build()
+                                     .with_preconditioner(Jacobi<V, I>::build().with_max_block_size(32u).on(exec_))
+                                     .with_criteria(stop::Iteration::build().with_max_iters(e_dim).on(exec_),
+                                                    stop::ResidualNorm<V>::build().with_baseline(stop::mode::rhs_norm).with_reduction_factor(1e-6).on(exec_))
+                                     .on(exec_);
+                sol->copy_from(rhs.get());
+            } else if (is_lower) {
+                solver_factory = solver::UpperTrs<V, I>::build().on(exec_);
+            } else {
+                solver_factory = solver::LowerTrs<V, I>::build().on(exec_);
+            }
+            solver_factory->generate_impl(sys_t)->apply(rhs.get(), sol.get());
+            if (is_spd) GKOMI_CALL(gkomi_isai_scale_excess_solution_f64_i32(nullptr, n, rhs_ptrs.get_const_data(), sol->get_values(), start, block));
+            GKOMI_CALL(gkomi_isai_scatter_excess_solution_f64_i32(nullptr, n, rhs_ptrs.get_const_data(), sol->get_const_values(), inv.rp.get_const_data(), inv.v.get_data(), start, block));
+            exec_->synchronize();  // the block's arrays leave scope
+        }
+        std::shared_ptr<Csr> inverse = std::move(inv).to_csr();
+        if (is_spd) {
+            approximate_inverse_ = share(Comp::create(share(inverse->transpose()), inverse));
+        } else {
+            approximate_inverse_ = inverse;
+        }
+    }
+    std::shared_ptr<const LinOp> approximate_inverse_;
+    mutable gkomi_isai_ctx record_{};
+    mutable array<V> mid_;
+};
+template <typename V = double, typename I = int32>
+using LowerIsai = Isai<isai_type::lower, V, I>;
+template <typename V = double, typename I = int32>
+using UpperIsai = Isai<isai_type::upper, V, I>;
+template <typename V = double, typename I = int32>
+using GeneralIsai = Isai<isai_type::general, V, I>;
+template <typename V = double, typename I = int32>
+using SpdIsai = Isai<isai_type::spd, V, I>;
+
+namespace detail {
+// What Ilu and Ic share: the two factors of whatever generates them, the solvers over them -- the triangular solvers
+// unless a factory for them is given (ilu.hpp:349-356, ic.hpp:320-328) --, and the apply through one intermediate vector.
 template <typename V, typename I>
 class two_solves : public LinOp, public Transposable {
 protected:
@@ -3365,13 +3623,45 @@ protected:
     // what a factorization's Factory generates of A, on this executor unless the factory has one
     template <class FactorizationFactory>
     auto generated(const FactorizationFactory& f, std::shared_ptr<const LinOp> A) const { return (f.exec_ ? f : *f.on(exec_)).generate(std::move(A)); }
-    void set_factors(std::shared_ptr<const matrix::Csr<V, I>> lower, std::shared_ptr<const matrix::Csr<V, I>> upper)
+    // upper_from_lower (Ic with an l_solver_factory, ic.hpp:327-328): the second solver is the conjugate transpose of
+    // the first instead of a solver generated from the upper factor
+    void set_factors(std::shared_ptr<const matrix::Csr<V, I>> lower, std::shared_ptr<const matrix::Csr<V, I>> upper,
+                     const std::shared_ptr<const LinOpFactory>& lower_solver_factory = nullptr, const std::shared_ptr<const LinOpFactory>& upper_solver_factory = nullptr,
+                     bool upper_from_lower = false)
     {
         lower_factor_ = std::move(lower);
         upper_factor_ = std::move(upper);
-        lower_solver_ = solver::LowerTrs<V, I>::build().on(exec_)->generate(lower_factor_);
-        upper_solver_ = solver::UpperTrs<V, I>::build().on(exec_)->generate(upper_factor_);
+        if (lower_solver_factory) {
+            lower_solver_ = share(lower_solver_factory->generate_impl(lower_factor_));
+        } else {
+            lower_solver_ = solver::LowerTrs<V, I>::build().on(exec_)->generate(lower_factor_);
+        }
+        if (upper_from_lower && lower_solver_factory) {
+            auto t = dynamic_cast<const Transposable*>(lower_solver_.get());
+            if (t == nullptr) GKO_NOT_SUPPORTED("Ic: the solver of l_solver_factory is not Transposable");
+            upper_solver_ = share(t->conj_transpose());
+        } else if (upper_solver_factory) {
+            upper_solver_ = share(upper_solver_factory->generate_impl(upper_factor_));
+        } else {
+            upper_solver_ = solver::UpperTrs<V, I>::build().on(exec_)->generate(upper_factor_);
+        }
     }
+    // both solvers LowerIsai / UpperIsai: the two-SpMV record of gkomi_isai_apply_cb
+    bool isai_callback(gkomi_apply_fn& fn, void*& ctx, size_type nrhs) const
+    {
+        if (!std::is_same<V, double>::value || !std::is_same<I, int32>::value) return false;
+        auto l = dynamic_cast<const LowerIsai<V, I>*>(lower_solver_.get());
+        auto u = dynamic_cast<const UpperIsai<V, I>*>(upper_solver_.get());
+        if (l == nullptr || u == nullptr || l->inverse_csr() == nullptr || u->inverse_csr() == nullptr) return false;
+        const size_type n = size_[0];
+        if (isai_mid_.get_num_elems() != n * nrhs || isai_mid_.get_executor() == nullptr) isai_mid_ = array<V>(exec_, n * nrhs);
+        fill_isai_ctx(isai_record_, n, nrhs, l->inverse_csr(), u->inverse_csr(), isai_mid_.get_data());
+        fn = &gkomi_isai_apply_cb;
+        ctx = &isai_record_;
+        return true;
+    }
+    mutable gkomi_isai_ctx isai_record_{};
+    mutable array<V> isai_mid_;
     void apply_impl(const LinOp* b, LinOp* x) const override
     {
         auto db = matrix::detail_fmt::dense(b);
@@ -3404,6 +3694,7 @@ public:
     bool native_callback(gkomi_apply_fn& fn, void*& ctx, size_type nrhs) const override
     {
         if (!std::is_same<V, double>::value || !std::is_same<I, int32>::value) return false;
+        if (this->isai_callback(fn, ctx, nrhs)) return true;
         auto l = dynamic_cast<const solver::LowerTrs<V, I>*>(lower_solver_.get());
         auto u = dynamic_cast<const solver::UpperTrs<V, I>*>(upper_solver_.get());
         if (l == nullptr || u == nullptr || u->has_unit_diagonal()) return false;
@@ -3447,16 +3738,20 @@ public:
         Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::Ilu<V, I>::Factory> f) { exact_ = std::move(f); return *this; }
         // the threshold ILU
         Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::ParIlut<V, I>::Factory> f) { ilut_ = std::move(f); return *this; }
+        // the solvers generated from the factors (ilu.hpp:349-356) instead of LowerTrs / UpperTrs, e.g. LowerIsai / UpperIsai
+        Factory& with_l_solver_factory(std::shared_ptr<const LinOpFactory> f) { l_solver_ = std::move(f); return *this; }
+        Factory& with_u_solver_factory(std::shared_ptr<const LinOpFactory> f) { u_solver_ = std::move(f); return *this; }
         std::unique_ptr<Ilu> generate(std::shared_ptr<const LinOp> A) const
         {
-            if (ilut_) return std::unique_ptr<Ilu>(new Ilu(this->exec_, *ilut_, std::move(A)));
-            if (exact_) return std::unique_ptr<Ilu>(new Ilu(this->exec_, *exact_, std::move(A)));
-            return std::unique_ptr<Ilu>(new Ilu(this->exec_, ::gko::factorization::ParIlu<V, I>::build().with_iterations(iterations_), std::move(A)));
+            if (ilut_) return std::unique_ptr<Ilu>(new Ilu(*this, *ilut_, std::move(A)));
+            if (exact_) return std::unique_ptr<Ilu>(new Ilu(*this, *exact_, std::move(A)));
+            return std::unique_ptr<Ilu>(new Ilu(*this, ::gko::factorization::ParIlu<V, I>::build().with_iterations(iterations_), std::move(A)));
         }
         std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
         size_type iterations_{0};
         std::shared_ptr<const typename ::gko::factorization::Ilu<V, I>::Factory> exact_;
         std::shared_ptr<const typename ::gko::factorization::ParIlut<V, I>::Factory> ilut_;
+        std::shared_ptr<const LinOpFactory> l_solver_, u_solver_;
     };
     static Factory build() { return Factory{}; }
     std::shared_ptr<const LinOp> get_l_solver() const { return lower_solver_; }
@@ -3473,22 +3768,23 @@ protected:
     Ilu(std::shared_ptr<const Executor> exec, dim<2> size) : base(std::move(exec), size) {}
     // a factorization factory that gives get_l_factor() / get_u_factor(): factorization::ParIlu, Ilu or ParIlut
     template <class FactorizationFactory>
-    Ilu(std::shared_ptr<const Executor> exec, const FactorizationFactory& f, std::shared_ptr<const LinOp> A) : base(std::move(exec), A->get_size())
+    Ilu(const Factory& own, const FactorizationFactory& f, std::shared_ptr<const LinOp> A) : base(own.get_executor(), A->get_size())
     {
         auto fact = this->generated(f, std::move(A));
-        this->set_factors(fact->get_l_factor(), fact->get_u_factor());
+        this->set_factors(fact->get_l_factor(), fact->get_u_factor(), own.l_solver_, own.u_solver_);
     }
     mutable gkomi_ilu_ctx record_{};
     mutable array<V> mid_;
     mutable array<char> tws_;
 };
 
-// Ic::apply = L^-1 then L^-H (ic.hpp: two triangular solves, like Ilu).  Not a native_preconditioner: a solver reaches
-// it through the generic callback.
+// Ic::apply = L^-1 then L^-H (ic.hpp: two triangular solves, like Ilu).  A solver reaches it through the generic
+// callback, except over LowerIsai, where both solvers are SpMVs and gkomi_isai_apply_cb runs them.
 template <typename V = double, typename I = int32>
-class Ic : public detail::two_solves<V, I> {
+class Ic : public detail::two_solves<V, I>, public ::gko::detail::native_preconditioner {
     using base = detail::two_solves<V, I>;
 public:
+    bool native_callback(gkomi_apply_fn& fn, void*& ctx, size_type nrhs) const override { return this->isai_callback(fn, ctx, nrhs); }
     // (L L^T)^-1 is symmetric: the transpose applies the same two solves
     std::unique_ptr<LinOp> transpose() const override { return std::unique_ptr<LinOp>(new Ic(*this)); }
     class Factory : public LinOpFactory {
@@ -3500,20 +3796,23 @@ public:
         Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::Ic<V, I>::Factory> f) { exact_ = std::move(f); return *this; }
         // the threshold IC
         Factory& with_factorization_factory(std::shared_ptr<const typename ::gko::factorization::ParIct<V, I>::Factory> f) { ict_ = std::move(f); return *this; }
+        // the solver generated from L (ic.hpp:320-328) instead of LowerTrs, e.g. LowerIsai; the second solver is then its conjugate transpose
+        Factory& with_l_solver_factory(std::shared_ptr<const LinOpFactory> f) { l_solver_ = std::move(f); return *this; }
         std::unique_ptr<Ic> generate(std::shared_ptr<const LinOp> A) const
         {
-            if (ict_) return std::unique_ptr<Ic>(new Ic(this->exec_, *ict_, std::move(A)));
+            if (ict_) return std::unique_ptr<Ic>(new Ic(*this, *ict_, std::move(A)));
             if (exact_) {
                 auto both = *exact_;
                 both.with_both_factors(true);  // the preconditioner needs L^T whatever the factory says
-                return std::unique_ptr<Ic>(new Ic(this->exec_, both, std::move(A)));
+                return std::unique_ptr<Ic>(new Ic(*this, both, std::move(A)));
             }
-            return std::unique_ptr<Ic>(new Ic(this->exec_, ::gko::factorization::ParIc<V, I>::build().with_iterations(iterations_), std::move(A)));
+            return std::unique_ptr<Ic>(new Ic(*this, ::gko::factorization::ParIc<V, I>::build().with_iterations(iterations_), std::move(A)));
         }
         std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
         size_type iterations_{0};
         std::shared_ptr<const typename ::gko::factorization::Ic<V, I>::Factory> exact_;
         std::shared_ptr<const typename ::gko::factorization::ParIct<V, I>::Factory> ict_;
+        std::shared_ptr<const LinOpFactory> l_solver_;
     };
     static Factory build() { return Factory{}; }
     std::shared_ptr<const LinOp> get_l_solver() const { return this->lower_solver_; }
@@ -3522,10 +3821,10 @@ protected:
     Ic(const Ic&) = default;
     // a factorization factory that gives get_l_factor() / get_lt_factor(): factorization::ParIc, Ic or ParIct
     template <class FactorizationFactory>
-    Ic(std::shared_ptr<const Executor> exec, const FactorizationFactory& f, std::shared_ptr<const LinOp> A) : base(std::move(exec), A->get_size())
+    Ic(const Factory& own, const FactorizationFactory& f, std::shared_ptr<const LinOp> A) : base(own.get_executor(), A->get_size())
     {
         auto fact = this->generated(f, std::move(A));
-        this->set_factors(fact->get_l_factor(), fact->get_lt_factor());
+        this->set_factors(fact->get_l_factor(), fact->get_lt_factor(), own.l_solver_, nullptr, true);
     }
 };
 }  // namespace preconditioner
