@@ -446,6 +446,52 @@ int gkomi_dense_row_gather_f64_i32(gkomi_stream_t s, int64_t nout,
                                    const double* in, int64_t in_stride,
                                    double* out, int64_t out_stride);
 
+/* ---- dense GEMM and transpose (core/matrix/dense_kernels.hpp:55-64, 225-234;
+ * csrc/dense_gemm.hip) ------------------------------------------------------
+ * dense::simple_apply / dense::apply (reference/matrix/dense_kernels.cpp:70-121):
+ * a is m x k, b is k x n, c is m x n, all row-major with int64 strides.
+ *   simple   (alpha == beta == NULL): c(i,j) = (+0.0) + a(i,0) b(0,j) + a(i,1) b(1,j) + ...
+ *            left to right; the chain starts from +0.0 (:75-79), not from the first
+ *            product, so a single product of -0.0 gives +0.0.
+ *   advanced (both device scalars): c(i,j) = c(i,j) * beta, then + (alpha a(i,l)) b(l,j)
+ *            for ascending l (:113-120).  beta == 0 still multiplies (:105-110): NaN
+ *            and Inf in c become NaN -- not BLAS behaviour, the reference's.  alpha * a
+ *            is rounded before it meets b.
+ * Product and sum are rounded separately, no FMA; the chain ends exactly at k (no
+ * padded +0.0 product, which would turn a -0.0 of c * beta into +0.0).  k == 0 gives
+ * c = +0.0 or c *= beta.  m == 0 or n == 0 returns 0 without a launch.  A stride below
+ * the column count or a negative size is GKOMI_EINVAL.  The padding of c is never
+ * written.  a and b must not alias c (the reference does not check this either).
+ * mode: 0 automatic, 1 ordered (always the reference's bits), 2 split.
+ *   split: k is cut into chunks of L = gkomi_dense_gemm_split_chunk() (a power of
+ *   two); each chunk's partial is the ordered chain from +0.0 over its part of k, and
+ *   the partials are added to c * beta (or +0.0) in ascending chunk order.  The order
+ *   is a function of (m, n, k) only.  Needs gkomi_dense_gemm_workspace_bytes(m, n, k,
+ *   mode) bytes of workspace (GKOMI_EWORKSPACE otherwise); ordered launches need none.
+ * gkomi_dense_gemm_plan: the kernel mode would run for this shape, a pure function of
+ * its arguments, on the host: 1 tile, 2 narrow (n <= 16, one thread per row of c),
+ * 3 split.  mode 1 never gives 3; mode 0 never gives 3 for k <= L.
+ * gkomi_dense_gemm_geometry: the tile kernel's tile (tile_m x tile_n, tile_k values of
+ * l per step), the narrow kernel's widest n, rows per workgroup and chunk of l. */
+int64_t gkomi_dense_gemm_split_chunk(void);
+int64_t gkomi_dense_gemm_plan(int64_t m, int64_t n, int64_t k, int mode);
+size_t gkomi_dense_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k, int mode);
+int gkomi_dense_gemm_geometry(int64_t* host_tile_m, int64_t* host_tile_n,
+                              int64_t* host_tile_k, int64_t* host_narrow_max_n,
+                              int64_t* host_narrow_rows, int64_t* host_narrow_k);
+int gkomi_dense_gemm_f64(gkomi_stream_t s, int64_t m, int64_t n, int64_t k,
+                         const double* a, int64_t a_stride, const double* b,
+                         int64_t b_stride, double* c, int64_t c_stride,
+                         const double* alpha, const double* beta, int mode,
+                         void* workspace, size_t workspace_bytes);
+/* dense::transpose / dense::conj_transpose (core/matrix/dense_kernels.hpp:225-234,
+ * reference/matrix/dense_kernels.cpp:813-836; the same for real values):
+ * out(j,i) = in(i,j), in is nrows x ncols, out ncols x nrows, any strides, the
+ * padding of out untouched.  in and out must not overlap. */
+int gkomi_dense_transpose_f64(gkomi_stream_t s, int64_t nrows, int64_t ncols,
+                              const double* in, int64_t in_stride, double* out,
+                              int64_t out_stride);
+
 /* ---- CG step kernels (core/solver/cg_kernels.hpp:54-80) ----------------- */
 /* stop_status: device uint8[nrhs] (array<stopping_status>) */
 int gkomi_cg_initialize_f64(gkomi_stream_t s, int64_t nrows, int64_t nrhs,
@@ -2004,6 +2050,20 @@ int gkomi_fbcsr_matrix_apply_cb(void* ctx, gkomi_stream_t s, int64_t nrhs,
                                 const double* alpha, const double* b,
                                 int64_t b_stride, const double* beta,
                                 double* c, int64_t c_stride);
+/* Dense (gkomi_dense_gemm_f64 with this matrix as a: dense::simple_apply / apply,
+ * core/matrix/dense_kernels.hpp:55-64, reference/matrix/dense_kernels.cpp:70-121).
+ * mode as there; workspace may be NULL / 0 for mode 1. */
+typedef struct gkomi_dense_ctx {
+    int64_t nrows, ncols, stride;
+    const double* vals;
+    int64_t mode;
+    void* workspace;
+    int64_t workspace_bytes;
+} gkomi_dense_ctx;
+int gkomi_dense_matrix_apply_cb(void* ctx, gkomi_stream_t s, int64_t nrhs,
+                                const double* alpha, const double* b,
+                                int64_t b_stride, const double* beta,
+                                double* c, int64_t c_stride);
 /* The solver drivers with the system matrix behind a callback (config 4 of
  * BASELINE.json runs GMRES on ELL / SELL-P).  Same loops, same arguments as the
  * CSR entry points; gkomi_cg_solve_op_f64 runs the reference kernel sequence,
@@ -2104,6 +2164,18 @@ int gkomi_cgs_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
                            double reduction_factor, int baseline,
                            int64_t check_every, void* workspace,
                            size_t workspace_bytes, double* host_info);
+/* gkomi_bicg_solve_f64_i32's loop (core/solver/bicg.cpp:117-232) with the system
+ * matrix and its transpose behind callbacks: a Dense and its Dense::transpose, or
+ * any other format and its transposed copy.  Workspace gkomi_krylov_workspace_bytes. */
+int gkomi_bicg_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+                            gkomi_matrix_apply_fn matrix, void* matrix_ctx,
+                            gkomi_matrix_apply_fn matrix_t, void* matrix_t_ctx,
+                            gkomi_apply_fn precond, void* precond_ctx,
+                            gkomi_apply_fn precond_t, void* precond_t_ctx,
+                            const double* b, double* x, int64_t max_iters,
+                            double reduction_factor, int baseline,
+                            int64_t check_every, void* workspace,
+                            size_t workspace_bytes, double* host_info);
 typedef struct gkomi_jacobi_ctx {
     int64_t n;               /* rows */
     int64_t nrhs;            /* columns of the vectors (stride == nrhs) */

@@ -1474,18 +1474,17 @@ extern "C" int gkomi_ir_initialize(gkomi_stream_t s, int64_t nrhs, uint8_t* stop
 // builds at the top of every apply); precond_t applies the transposed
 // preconditioner (NULL with precond == NULL: Identity; a symmetric
 // preconditioner passes the same callback twice).
-extern "C" int gkomi_bicg_solve_f64_i32(
-    gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t nnz, const int32_t* row_ptrs,
-    const int32_t* col_idxs, const double* vals, const int32_t* t_row_ptrs,
-    const int32_t* t_col_idxs, const double* t_vals, int spmv_strategy, int64_t max_row_nnz_hint,
-    gkomi_apply_fn precond, void* precond_ctx, gkomi_apply_fn precond_t, void* precond_t_ctx,
-    const double* b, double* x, int64_t max_iters, double reduction_factor, int baseline,
-    int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
+namespace {
+
+// At: the transposed system matrix, CSR arrays or an operator like A itself
+int bicg_solve_impl(const solve_request& req, const sysmat& At, gkomi_apply_fn precond_t, void* precond_t_ctx)
 {
-    if ((precond == nullptr) != (precond_t == nullptr)) return GKOMI_EINVAL;
-    const solve_request req{s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
-        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
-        host_info};
+    if ((req.precond == nullptr) != (precond_t == nullptr)) return GKOMI_EINVAL;
+    const gkomi_stream_t s = req.s;
+    const int64_t n = req.n, nrhs = req.nrhs;
+    const double* b = req.b;
+    double* x = req.x;
+    double* host_info = req.host_info;
     driver_common c;
     GKOMI_TRY(c.init(req, 0));
     double *sc = c.scalars, *r = c.vec(0), *z = c.vec(1), *p = c.vec(2), *q = c.vec(3), *r2 = c.vec(4), *z2 = c.vec(5),
@@ -1512,14 +1511,50 @@ extern "C" int gkomi_bicg_solve_f64_i32(
         GKOMI_TRY(gkomi_bicg_step_1_f64(s, n, nrhs, p, nrhs, z, nrhs, p2, nrhs, z2, nrhs, rho, prev_rho,
                                         c.stop_status));
         GKOMI_TRY(c.spmv(p, q));
-        GKOMI_TRY(gkomi_csr_spmv_f64_i32(s, n, n, nrhs, nnz, t_row_ptrs, t_col_idxs, t_vals, p2, nrhs,
-                                         q2, nrhs, nullptr, nullptr, spmv_strategy, -1));
+        if (At.is_csr()) {
+            GKOMI_TRY(gkomi_csr_spmv_f64_i32(s, n, n, nrhs, At.nnz, At.row_ptrs, At.col_idxs, At.vals, p2, nrhs,
+                                             q2, nrhs, nullptr, nullptr, At.strategy, -1));
+        } else {
+            GKOMI_TRY(At.apply(s, nrhs, nullptr, p2, nullptr, q2));
+        }
         GKOMI_TRY(c.dot(p2, q, beta));
         GKOMI_TRY(gkomi_bicg_step_2_f64(s, n, nrhs, x, nrhs, r, nrhs, r2, nrhs, p, nrhs, q, nrhs, q2,
                                         nrhs, beta, rho, c.stop_status));
         std::swap(prev_rho, rho);
     }
     return c.finish(c.stop_iter(), r, host_info);
+}
+
+}  // namespace
+
+extern "C" int gkomi_bicg_solve_f64_i32(
+    gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t nnz, const int32_t* row_ptrs,
+    const int32_t* col_idxs, const double* vals, const int32_t* t_row_ptrs,
+    const int32_t* t_col_idxs, const double* t_vals, int spmv_strategy, int64_t max_row_nnz_hint,
+    gkomi_apply_fn precond, void* precond_ctx, gkomi_apply_fn precond_t, void* precond_t_ctx,
+    const double* b, double* x, int64_t max_iters, double reduction_factor, int baseline,
+    int64_t check_every, void* workspace, size_t workspace_bytes, double* host_info)
+{
+    return bicg_solve_impl({s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, check_every, workspace, workspace_bytes,
+        host_info}, make_csr_sysmat(n, nnz, t_row_ptrs, t_col_idxs, t_vals, spmv_strategy, -1), precond_t, precond_t_ctx);
+}
+
+// the same loop with A and its transpose behind callbacks (any format: a Dense and its Dense::transpose, ...)
+extern "C" int gkomi_bicg_solve_op_f64(
+    gkomi_stream_t s, int64_t n, int64_t nrhs, gkomi_matrix_apply_fn matrix, void* matrix_ctx,
+    gkomi_matrix_apply_fn matrix_t, void* matrix_t_ctx, gkomi_apply_fn precond, void* precond_ctx,
+    gkomi_apply_fn precond_t, void* precond_t_ctx, const double* b, double* x, int64_t max_iters,
+    double reduction_factor, int baseline, int64_t check_every, void* workspace, size_t workspace_bytes,
+    double* host_info)
+{
+    if (matrix == nullptr || matrix_t == nullptr) return GKOMI_EINVAL;
+    sysmat At;  // (kept an operator also where it is the library's CSR callback: its record carries the strategy)
+    At.n = n;
+    At.op = matrix_t;
+    At.ctx = matrix_t_ctx;
+    return bicg_solve_impl({s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x, max_iters,
+        reduction_factor, baseline, check_every, workspace, workspace_bytes, host_info}, At, precond_t, precond_t_ctx);
 }
 
 // Ir::apply_dense_impl (core/solver/ir.cpp:186-277) with the caller's x as the

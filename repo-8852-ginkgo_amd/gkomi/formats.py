@@ -1,4 +1,4 @@
-"""gko::matrix::{Csr, Coo, Ell, Sellp, Hybrid, Fbcsr} over the C ABI for Python callers
+"""gko::matrix::{Csr, Coo, Ell, Sellp, Hybrid, Fbcsr, Dense} over the C ABI for Python callers
 (tests, bench, tools/benchmark_*.py): device arrays are torch tensors, every
 conversion and apply is a gkomi_* kernel -- no CPU fallback.  Conversions
 follow core/matrix/csr.cpp:257-405 (the sizes the reference reads back with
@@ -33,6 +33,8 @@ CooCtx = _ctx_type("CooCtx", [("nrows", _i64), ("ncols", _i64), ("nnz", _i64), (
                               ("vals", _ptr)])
 FbcsrCtx = _ctx_type("FbcsrCtx", [("nbrows", _i64), ("nbcols", _i64), ("bs", _i64), ("nbnz", _i64), ("row_ptrs", _ptr),
                                   ("col_idxs", _ptr), ("vals", _ptr)])
+DenseCtx = _ctx_type("DenseCtx", [("nrows", _i64), ("ncols", _i64), ("stride", _i64), ("vals", _ptr), ("mode", _i64),
+                                  ("workspace", _ptr), ("workspace_bytes", _i64)])
 HybridCtx = _ctx_type("HybridCtx", [("nrows", _i64), ("ncols", _i64), ("ell_num_stored_per_row", _i64),
                                     ("ell_stride", _i64), ("ell_col_idxs", _ptr), ("ell_vals", _ptr), ("coo_nnz", _i64),
                                     ("coo_row_idxs", _ptr), ("coo_col_idxs", _ptr), ("coo_vals", _ptr)])
@@ -578,6 +580,75 @@ class Fbcsr:
         self.gk.fbcsr_extract_diagonal_f64_i32(_stream(self.vals), self.nbrows, self.nbcols, self.bs, self.row_ptrs,
                                                self.col_idxs, self.vals, out)
         return out
+
+
+class Dense:
+    """gko::matrix::Dense<double> as an operator: a 2-d fp64 tensor of any row stride (unit column stride).
+    apply is dense::simple_apply / dense::apply in the reference's sum order (gkomi_dense_gemm_f64)."""
+    name = "dense"
+
+    def __init__(self, gk, values):
+        if not torch.is_tensor(values) or values.dim() != 2 or values.dtype != F64:
+            raise TypeError("Dense takes a 2-d float64 tensor")
+        if values.shape[1] > 1 and values.stride(1) != 1:
+            raise ValueError("Dense needs unit column stride")
+        if values.shape[0] > 1 and values.stride(0) < values.shape[1]:
+            raise ValueError("Dense needs a row stride of at least the column count")
+        self.gk, self.values = gk, values
+        self.nrows, self.ncols = int(values.shape[0]), int(values.shape[1])
+        self.stride = max(int(values.stride(0)), self.ncols) if self.nrows > 1 else max(self.ncols, 1)
+        self._ws = None
+
+    @classmethod
+    def from_host(cls, gk, values, device="cuda:0"):
+        return cls(gk, torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).to(device))
+
+    def storage_bytes(self):
+        return 8 * self.nrows * self.ncols
+
+    def _workspace(self, nrhs, mode):
+        nb = int(self.gk.dense_gemm_workspace_bytes(self.nrows, nrhs, self.ncols, mode))
+        if self._ws is None or self._ws.numel() < nb:
+            self._ws = torch.empty(max(nb, 8), dtype=U8, device=self.values.device)
+        return self._ws, nb
+
+    def apply(self, b, x, alpha=None, beta=None, mode=0):
+        """x = A b, or x = alpha A b + beta x; mode 0 automatic, 1 ordered, 2 split (include/gkomi.h)"""
+        if (alpha is None) != (beta is None):
+            raise ValueError("alpha and beta come together")
+        if mode not in (0, 1, 2):
+            raise ValueError("mode is 0 (automatic), 1 (ordered) or 2 (split)")
+        for name, t, rows in (("b", b, self.ncols), ("x", x, self.nrows)):
+            if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != F64:
+                raise TypeError(f"{name} must be a 2-d float64 tensor")
+            if t.shape[0] != rows:
+                raise ValueError(f"{name} has {t.shape[0]} rows, the operator needs {rows}")
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError(f"{name} needs unit column stride")
+        if b.shape[1] != x.shape[1]:
+            raise ValueError(f"b has {b.shape[1]} columns, x has {x.shape[1]}")
+        dv, n = self.values.device, int(b.shape[1])
+        row_stride = lambda t: max(int(t.stride(0)), n) if t.shape[0] > 1 else max(n, 1)
+        ws, nb = self._workspace(n, mode)
+        self.gk.dense_gemm_f64(_stream(self.values), self.nrows, n, self.ncols, self.values, self.stride, b, row_stride(b),
+                               x, row_stride(x), _device_scalar(dv, alpha), _device_scalar(dv, beta), mode, ws, nb)
+        return x
+
+    def transpose(self):
+        out = torch.empty((self.ncols, self.nrows), dtype=F64, device=self.values.device)
+        self.gk.dense_transpose_f64(_stream(self.values), self.nrows, self.ncols, self.values, self.stride, out,
+                                    max(self.nrows, 1))
+        return Dense(self.gk, out)
+
+    conj_transpose = transpose
+
+    def callback(self, mode=1, nrhs=1):
+        """the matrix behind gkomi_dense_matrix_apply_cb.  mode 1 (ordered): the reference's bits, no workspace;
+        for mode 0 / 2 the workspace made here covers applies to up to `nrhs` columns"""
+        nb = max(int(self.gk.dense_gemm_workspace_bytes(self.nrows, j, self.ncols, mode)) for j in range(1, nrhs + 1))
+        ws = torch.empty(max(nb, 8), dtype=U8, device=self.values.device)
+        ctx = DenseCtx(self.nrows, self.ncols, self.stride, self.values.data_ptr(), mode, ws.data_ptr(), nb)
+        return MatrixCallback(self.gk, "gkomi_dense_matrix_apply_cb", ctx, (self, ws))
 
 
 class Sellp:

@@ -116,6 +116,21 @@ def bicg_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=1000, reduc
     return _report(info, x2, b, n)
 
 
+def bicg_solve_op(gk, matrix, matrix_t, b, x=None, max_iters=1000, reduction=1e-10, baseline="rhs_norm", precond=None,
+                  precond_t=None, check_every=8):
+    """Bicg::apply on a system matrix in any format and its transpose (gkomi.formats objects: a Dense and its
+    transpose(), a Csr and its transposed copy): gkomi_bicg_solve_op_f64."""
+    n = matrix.nrows
+    b2, x2, nrhs = _operands(n, b, x, precond, precond_t)
+    cb, cbt = matrix.callback(), matrix_t.callback()
+    nbytes = gk.krylov_workspace_bytes(n, nrhs)
+    ws, info, stream = _workspace(nbytes, nrhs, b.device)
+    gk.bicg_solve_op_f64(stream, n, nrhs, cb.fn, cb.ctx_ptr, cbt.fn, cbt.ctx_ptr, *_callback(precond),
+                         *_callback(precond_t), b2, x2, max_iters, reduction, BASELINES[baseline], check_every, ws,
+                         nbytes, info)
+    return _report(info, x2, b, n)
+
+
 def ir_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, relaxation_factor=1.0, inner=None, max_iters=1000,
              reduction=1e-10, baseline="rhs_norm", strategy=0, max_row_nnz=-1):
     """Ir::apply with x as the initial guess; inner: None (Richardson) or a

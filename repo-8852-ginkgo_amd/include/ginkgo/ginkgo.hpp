@@ -719,11 +719,37 @@ protected:
     std::shared_ptr<const Executor> exec_;
 };
 
+// include/ginkgo/core/base/lin_op.hpp:433-455 (real values: conj_transpose == transpose)
+class Transposable {
+public:
+    virtual ~Transposable() = default;
+    virtual std::unique_ptr<LinOp> transpose() const = 0;
+    virtual std::unique_ptr<LinOp> conj_transpose() const { return this->transpose(); }
+};
+
+namespace detail {
+// dense::simple_apply / apply and dense::transpose (gkomi_dense_gemm_f64, gkomi_dense_transpose_f64); double only:
+// the reference executor arbitrates no float GEMM here
+inline void dense_gemm(std::shared_ptr<const Executor> exec, int64_t m, int64_t n, int64_t k, const double* a, int64_t a_stride,
+                       const double* b, int64_t b_stride, double* c, int64_t c_stride, const double* alpha, const double* beta)
+{
+    array<char> ws(exec, gkomi_dense_gemm_workspace_bytes(m, n, k, 0) + 8);
+    GKOMI_CALL(gkomi_dense_gemm_f64(nullptr, m, n, k, a, a_stride, b, b_stride, c, c_stride, alpha, beta, 0, ws.get_data(), ws.get_num_elems()));
+}
+inline void dense_gemm(std::shared_ptr<const Executor>, int64_t, int64_t, int64_t, const float*, int64_t, const float*, int64_t, float*,
+                       int64_t, const float*, const float*) { GKO_NOT_IMPLEMENTED; }
+inline void dense_transpose(int64_t nrows, int64_t ncols, const double* in, int64_t in_stride, double* out, int64_t out_stride)
+{
+    GKOMI_CALL(gkomi_dense_transpose_f64(nullptr, nrows, ncols, in, in_stride, out, out_stride));
+}
+inline void dense_transpose(int64_t, int64_t, const float*, int64_t, float*, int64_t) { GKO_NOT_IMPLEMENTED; }
+}  // namespace detail
+
 // ---- matrix formats -----------------------------------------------------------------
 namespace matrix {
 
 template <typename V = double>
-class Dense : public LinOp {
+class Dense : public LinOp, public Transposable {
 public:
     using value_type = V;
     static std::unique_ptr<Dense> create(std::shared_ptr<const Executor> exec, const dim<2>& size = dim<2>{}, size_type stride = 0)
@@ -827,6 +853,21 @@ public:
             data.nonzeros.push_back({static_cast<int32>(i), static_cast<int32>(j), host[i * stride_ + j]});
         }
     }
+    // core/matrix/dense.cpp:993-1030
+    std::unique_ptr<LinOp> transpose() const override
+    {
+        auto t = Dense::create(exec_, dim<2>(size_[1], size_[0]));
+        this->transpose(t.get());
+        return std::unique_ptr<LinOp>(std::move(t));
+    }
+    std::unique_ptr<LinOp> conj_transpose() const override { return this->transpose(); }
+    void transpose(Dense* output) const
+    {
+        kernel("dense::transpose");
+        if (output->get_size() != dim<2>(size_[1], size_[0])) throw DimensionMismatch(__FILE__, __LINE__, "transpose: output must be #columns x #rows");
+        ::gko::detail::dense_transpose(rows(), cols(), get_const_values(), stride_, output->get_values(), output->get_stride());
+    }
+    void conj_transpose(Dense* output) const { this->transpose(output); }
     int64_t rows() const { return static_cast<int64_t>(size_[0]); }
     int64_t cols() const { return static_cast<int64_t>(size_[1]); }
 protected:
@@ -836,8 +877,21 @@ protected:
     void kernel(const char* name) const { detail::require_device(exec_, name); }
     void same_size(const Dense* b) const { if (b->get_size() != size_) throw DimensionMismatch(__FILE__, __LINE__, "operands differ in size"); }
     void result_size(const Dense* r) const { if (r->get_size() != dim<2>(1, size_[1])) throw DimensionMismatch(__FILE__, __LINE__, "result must be 1 x #columns"); }
-    void apply_impl(const LinOp*, LinOp*) const override { GKO_NOT_IMPLEMENTED; }  // dense GEMM: off the hot path
-    void apply_impl(const LinOp*, const LinOp*, const LinOp*, LinOp*) const override { GKO_NOT_IMPLEMENTED; }
+    // core/matrix/dense.cpp:88-114: dense::simple_apply / dense::apply, the reference's sums (include/gkomi.h)
+    void apply_impl(const LinOp* b, LinOp* x) const override { gemm(nullptr, b, nullptr, x); }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
+    {
+        gemm(as<const Dense>(alpha), b, as<const Dense>(beta), x);
+    }
+    void gemm(const Dense* alpha, const LinOp* b, const Dense* beta, LinOp* x) const
+    {
+        kernel("dense::apply");
+        auto db = as<const Dense>(b);
+        auto dx = as<Dense>(x);
+        ::gko::detail::dense_gemm(exec_, rows(), dx->cols(), cols(), get_const_values(), stride_, db->get_const_values(), db->get_stride(),
+                                  dx->get_values(), dx->get_stride(), alpha ? alpha->get_const_values() : nullptr,
+                                  beta ? beta->get_const_values() : nullptr);
+    }
     array<V> values_;
     size_type stride_;
     template <typename>
@@ -2022,15 +2076,16 @@ inline void fill_csr_ctx(const matrix::Csr<double, int32>* c, gkomi_csr_ctx& csr
 }
 // The system matrix of a solver as (gkomi_matrix_apply_fn, context): Ell and
 // Sellp go by the library's own callbacks + records, which the fused drivers
-// recognise (SpMV with the dot-product epilogue, csrc/formats.hip), Fbcsr by its
-// own callback + record (no epilogue: the drivers follow it with their partials
-// kernel); every other LinOp goes through matrix_callback.
+// recognise (SpMV with the dot-product epilogue, csrc/formats.hip), Fbcsr and Dense
+// by their own callbacks + records (no epilogue: the drivers follow them with their
+// partials kernel); every other LinOp goes through matrix_callback.
 struct system_callback {
     matrix_callback generic;
     gkomi_csr_ctx csr{};
     gkomi_ell_ctx ell{};
     gkomi_sellp_ctx sellp{};
     gkomi_fbcsr_ctx fbcsr{};
+    gkomi_dense_ctx dense{};
     gkomi_matrix_apply_fn fn;
     void* ctx;
     system_callback(const LinOp* A, std::shared_ptr<const Executor> exec, size_type n)
@@ -2069,20 +2124,21 @@ struct system_callback {
             fbcsr.vals = fb->get_const_values();
             fn = &gkomi_fbcsr_matrix_apply_cb;
             ctx = &fbcsr;
+        } else if (auto d = dynamic_cast<const matrix::Dense<double>*>(A)) {
+            // ordered (mode 1): the reference's bits for any number of right-hand sides, and no workspace
+            dense.nrows = d->rows();
+            dense.ncols = d->cols();
+            dense.stride = static_cast<int64_t>(d->get_stride());
+            dense.vals = d->get_const_values();
+            dense.mode = 1;
+            fn = &gkomi_dense_matrix_apply_cb;
+            ctx = &dense;
         }
     }
     system_callback(const system_callback&) = delete;
     system_callback& operator=(const system_callback&) = delete;
 };
 }  // namespace detail
-
-// include/ginkgo/core/base/lin_op.hpp:433-455 (real values: conj_transpose == transpose)
-class Transposable {
-public:
-    virtual ~Transposable() = default;
-    virtual std::unique_ptr<LinOp> transpose() const = 0;
-    virtual std::unique_ptr<LinOp> conj_transpose() const { return this->transpose(); }
-};
 
 // include/ginkgo/core/base/types.hpp:257-400
 class precision_reduction {
@@ -2588,7 +2644,14 @@ protected:
             if (tr == nullptr) GKO_NOT_SUPPORTED("Bicg: the preconditioner must be Transposable");
             precond_t_ = std::shared_ptr<const LinOp>(tr->conj_transpose());
         }
-        At_ = as<const matrix::Csr<V, int32>>(this->A_.get())->transpose();
+        if (auto csr = dynamic_cast<const matrix::Csr<V, int32>*>(this->A_.get())) {
+            At_ = csr->transpose();
+        } else {
+            // any other Transposable system matrix (a Dense): both go to the driver as operators
+            auto tr = dynamic_cast<const Transposable*>(this->A_.get());
+            if (tr == nullptr) GKO_NOT_SUPPORTED("Bicg: the system matrix must be Transposable");
+            At_op_ = std::shared_ptr<const LinOp>(tr->conj_transpose());
+        }
     }
     using base::apply_impl;
     void apply_impl(const LinOp* b, LinOp* x) const override
@@ -2596,11 +2659,20 @@ protected:
         const auto& st = this->settings_;
         const bool pre = this->precond_ != nullptr;
         typename base::operands f(*this, b, x);
-        auto csr = as<const matrix::Csr<V, int32>>(this->A_.get());
         array<char> ws(this->exec_, gkomi_krylov_workspace_bytes(f.n, f.nrhs));
         ::gko::detail::linop_callback cb{this->precond_.get(), this->exec_, static_cast<size_type>(f.n), static_cast<size_type>(f.nrhs)};
         ::gko::detail::linop_callback cbt{precond_t_.get(), this->exec_, static_cast<size_type>(f.n), static_cast<size_type>(f.nrhs)};
         auto pfn = pre ? &::gko::detail::linop_callback::call : nullptr;
+        if (At_op_) {
+            ::gko::detail::system_callback sys{this->A_.get(), this->exec_, static_cast<size_type>(f.n)};
+            ::gko::detail::system_callback sys_t{At_op_.get(), this->exec_, static_cast<size_type>(f.n)};
+            GKOMI_CALL(gkomi_bicg_solve_op_f64(nullptr, f.n, f.nrhs, sys.fn, sys.ctx, sys_t.fn, sys_t.ctx, pfn, pre ? &cb : nullptr, pfn, pre ? &cbt : nullptr,
+                                               f.db->get_const_values(), f.dx->get_values(), st.max_iters, st.reduction_factor,
+                                               detail::baseline_code(st.baseline), 8, ws.get_data(), ws.get_num_elems(), f.info.data()));
+            f.report();
+            return;
+        }
+        auto csr = as<const matrix::Csr<V, int32>>(this->A_.get());
         GKOMI_CALL(gkomi_bicg_solve_f64_i32(nullptr, f.n, f.nrhs, csr->get_num_stored_elements(), csr->get_const_row_ptrs(), csr->get_const_col_idxs(), csr->get_const_values(),
                                             At_->get_const_row_ptrs(), At_->get_const_col_idxs(), At_->get_const_values(), csr->get_strategy()->get_code(), csr->get_max_row_nnz(),
                                             pfn, pre ? &cb : nullptr, pfn, pre ? &cbt : nullptr, f.db->get_const_values(), f.dx->get_values(), st.max_iters, st.reduction_factor,
@@ -2609,6 +2681,7 @@ protected:
     }
     std::shared_ptr<const LinOp> precond_t_;
     std::unique_ptr<matrix::Csr<V, int32>> At_;
+    std::shared_ptr<const LinOp> At_op_;
 };
 
 // Ir (include/ginkgo/core/solver/ir.hpp): x += relaxation_factor * solver(b - A x);

@@ -1,5 +1,6 @@
 // hip/matrix/dense_kernels.hip.cpp: the BLAS-1 kernels of the solver steps
-// (core/matrix/dense_kernels.hpp; reference/matrix/dense_kernels.cpp:127-447).
+// (core/matrix/dense_kernels.hpp; reference/matrix/dense_kernels.cpp:127-447), the dense GEMM
+// (simple_apply / apply, :70-121) and transpose / conj_transpose (:813-836).
 #include "../gkomi_bindings.hpp"
 
 namespace gko {
@@ -10,6 +11,40 @@ namespace dense {
 inline void ensure(array<char>& tmp, size_type need)
 {
     if (tmp.get_num_elems() < need) tmp.resize_and_reset(need);  // the caller-cached scratch (solver_boilerplate.hpp:61-66)
+}
+
+// c = a b in the reference's sum order; the automatic mode may cut a long k into chunks (include/gkomi.h)
+inline void gemm(std::shared_ptr<const HipExecutor> exec, const matrix::Dense<double>* alpha, const matrix::Dense<double>* a,
+                 const matrix::Dense<double>* b, const matrix::Dense<double>* beta, matrix::Dense<double>* c)
+{
+    const int64_t m = c->get_size()[0], n = c->get_size()[1], k = a->get_size()[1];
+    array<char> ws(exec, gkomi_dense_gemm_workspace_bytes(m, n, k, 0) + 8);
+    GKOMI_CALL(gkomi_dense_gemm_f64(GKOMI_NULL_STREAM, m, n, k, a->get_const_values(), a->get_stride(), b->get_const_values(),
+                                    b->get_stride(), c->get_values(), c->get_stride(), alpha ? alpha->get_const_values() : nullptr,
+                                    beta ? beta->get_const_values() : nullptr, 0, ws.get_data(), ws.get_num_elems()));
+}
+
+void simple_apply(std::shared_ptr<const HipExecutor> exec, const matrix::Dense<double>* a, const matrix::Dense<double>* b,
+                  matrix::Dense<double>* c)
+{
+    gemm(exec, nullptr, a, b, nullptr, c);
+}
+
+void apply(std::shared_ptr<const HipExecutor> exec, const matrix::Dense<double>* alpha, const matrix::Dense<double>* a,
+           const matrix::Dense<double>* b, const matrix::Dense<double>* beta, matrix::Dense<double>* c)
+{
+    gemm(exec, alpha, a, b, beta, c);
+}
+
+void transpose(std::shared_ptr<const HipExecutor> exec, const matrix::Dense<double>* orig, matrix::Dense<double>* trans)
+{
+    GKOMI_CALL(gkomi_dense_transpose_f64(GKOMI_NULL_STREAM, orig->get_size()[0], orig->get_size()[1], orig->get_const_values(),
+                                         orig->get_stride(), trans->get_values(), trans->get_stride()));
+}
+
+void conj_transpose(std::shared_ptr<const HipExecutor> exec, const matrix::Dense<double>* orig, matrix::Dense<double>* trans)
+{
+    transpose(exec, orig, trans);  // real values
 }
 
 void fill(std::shared_ptr<const HipExecutor> exec, matrix::Dense<double>* x, double value)
