@@ -2293,6 +2293,125 @@ int gkomi_gmres_solve_f64_i32(gkomi_stream_t s, int64_t n, int64_t nrhs,
                               int baseline, void* workspace,
                               size_t workspace_bytes, double* host_info);
 
+/* ---- CB-GMRES (core/solver/cb_gmres_kernels.hpp; semantics
+ *      reference/solver/cb_gmres_kernels.cpp; driver core/solver/cb_gmres.cpp:204-491)
+ * GMRES with a compressed Krylov basis.  `storage` follows
+ * solver::cb_gmres::storage_precision (include/ginkgo/core/solver/cb_gmres.hpp:88-95):
+ * 0 keep (double), 1 reduce1 (float), 2 reduce2 (half), 3 integer (int64), 4 ireduce1
+ * (int32), 5 ireduce2 (int16).  krylov_bases: (krylov_dim+1) x n x nrhs storage values,
+ * entry (k, row, col) at (k n + row) nrhs + col (accessor/reduced_row_major.hpp);
+ * scalars: (krylov_dim+1) x nrhs doubles, read and written by the integer storages only
+ * (accessor/scaled_reduced_row_major.hpp: value = double(stored) * scalar, stored =
+ * (storage)(value / scalar), truncating).  Half is written double -> float -> half with
+ * round-to-nearest-even, as the reference's device code does
+ * (core/base/extended_float.hpp:318).  All arithmetic is fp64.  Dense operands are
+ * contiguous (row stride nrhs): next_krylov_basis n x nrhs, givens_sin/cos krylov_dim x
+ * nrhs, residual_norm_collection and buffer (krylov_dim+1) x nrhs, arnoldi_norm 3 x nrhs,
+ * hessenberg (krylov_dim+1) x (krylov_dim nrhs) with h_stride = krylov_dim nrhs,
+ * hessenberg_iter = hessenberg + iter nrhs.  1 <= krylov_dim <= 4096, nrhs <= 65535 (the
+ * columns are a grid dimension); GKOMI_EINVAL otherwise.
+ * Sums over rows are two-stage in a fixed order (reproducible, not the reference's
+ * sequential order); everything else equals the reference bit for bit given equal
+ * inputs.  The sweeps move 16 bytes per lane when nrhs == 1, n * sizeof(storage) is a
+ * multiple of 16 and the pointers are 16-byte aligned; element by element otherwise. */
+size_t gkomi_cb_gmres_basis_bytes(int64_t n, int64_t nrhs, int64_t krylov_dim, int storage);
+/* device workspace of restart / finish_arnoldi / arnoldi (256-byte aligned) */
+size_t gkomi_cb_gmres_step_workspace_bytes(int64_t nrhs, int64_t krylov_dim);
+/* threads per workgroup, workgroups per column at most, consecutive rows one lane takes
+ * per trip, basis vectors per pass of the dots kernel */
+int gkomi_cb_gmres_geometry(int storage, int64_t* block_size, int64_t* block_cap,
+                            int64_t* elements_per_lane, int64_t* dot_batch);
+/* cb_gmres::initialize, reference/solver/cb_gmres_kernels.cpp:308-326 */
+int gkomi_cb_gmres_initialize_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+                                  int64_t krylov_dim, const double* b,
+                                  int64_t b_stride, double* residual,
+                                  int64_t r_stride, double* givens_sin,
+                                  double* givens_cos, uint8_t* stop_status);
+/* cb_gmres::restart, :331-395.  clear_rest != 0: vectors 1..krylov_dim are zeroed and
+ * their scalars set by write_scalar(1) as the reference does (:386-394; nothing reads them
+ * before arnoldi writes them).  arnoldi_norm row 2 is written for the integer storages. */
+int gkomi_cb_gmres_restart_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+                               int64_t krylov_dim, int storage,
+                               const double* residual, double* residual_norm,
+                               double* residual_norm_collection,
+                               double* arnoldi_norm, void* krylov_bases,
+                               double* scalars, double* next_krylov_basis,
+                               uint64_t* final_iter_nums, int clear_rest,
+                               void* workspace, size_t workspace_bytes);
+/* finish_arnoldi_CGS, :61-175: classical Gram-Schmidt against vectors 0..iter with up
+ * to two re-orthogonalisation passes (while norm_after < norm_before / sqrt(2)), then
+ * hessenberg_iter(iter+1) = norm, next /= norm, vector iter+1 = compress(next).  Seven
+ * launches, no look from the host.  arnoldi_norm rows 0, 1 and 2 as in the reference
+ * (row 2, max |next|, for every storage); num_reorth (device, one per column, may be
+ * NULL) receives the number of re-orthogonalisation passes of the columns that have
+ * not stopped.  Stopped columns: only arnoldi_norm row 0. */
+int gkomi_cb_gmres_finish_arnoldi_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+                                      int64_t krylov_dim, int storage,
+                                      double* next_krylov_basis,
+                                      void* krylov_bases, double* scalars,
+                                      double* hessenberg_iter, int64_t h_stride,
+                                      double* buffer_iter, double* arnoldi_norm,
+                                      int64_t iter, const uint8_t* stop_status,
+                                      uint64_t* num_reorth, void* workspace,
+                                      size_t workspace_bytes);
+/* givens_rotation + calculate_next_residual_norm, :200-256 (bit-identical) */
+int gkomi_cb_gmres_givens_f64(gkomi_stream_t s, int64_t nrhs, double* givens_sin,
+                              double* givens_cos, double* residual_norm,
+                              double* residual_norm_collection,
+                              double* hessenberg_iter, int64_t h_stride,
+                              int64_t iter, const uint8_t* stop_status);
+/* cb_gmres::arnoldi, :400-431: final_iter_nums += !stopped, finish_arnoldi, givens */
+int gkomi_cb_gmres_arnoldi_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+                               int64_t krylov_dim, int storage,
+                               double* next_krylov_basis, double* givens_sin,
+                               double* givens_cos, double* residual_norm,
+                               double* residual_norm_collection,
+                               void* krylov_bases, double* scalars,
+                               double* hessenberg_iter, int64_t h_stride,
+                               double* buffer_iter, double* arnoldi_norm,
+                               int64_t iter, uint64_t* final_iter_nums,
+                               const uint8_t* stop_status, uint64_t* num_reorth,
+                               void* workspace, size_t workspace_bytes);
+/* cb_gmres::solve_krylov, :436-449: y = hessenberg \ residual_norm_collection per
+ * column, before_preconditioner(i) = sum_j basis(j, i) y(j) with j ascending per
+ * element (bit-identical) */
+int gkomi_cb_gmres_solve_krylov_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+                                    int storage,
+                                    const double* residual_norm_collection,
+                                    const void* krylov_bases,
+                                    const double* scalars,
+                                    const double* hessenberg, int64_t h_stride,
+                                    double* y, double* before_preconditioner,
+                                    const uint64_t* final_iter_nums);
+/* CbGmres::apply_dense_impl (core/solver/cb_gmres.cpp:204-487) as the reference's kernel
+ * sequence, with Combined(Iteration(max_iters) [id 1], ResidualNorm(reduction, baseline)
+ * [id 2]) fed the implicit residual norm and the reference's forced-iteration logic
+ * (:315-383): a convergence detected at iteration 10 or later is reset, a restart with
+ * an explicit residual is forced, and only the next detection counts.  As there, the
+ * loop ends at the first check that changes a status without such a reset, whatever the
+ * other columns' state.  host_info: 3 + 2 nrhs doubles, as for
+ * gkomi_gmres_solve_f64_i32, then the number of forced resets; converged = every column
+ * has.  precond == NULL = Identity.  Workspace 16-byte aligned.  Blocks until done. */
+size_t gkomi_cb_gmres_workspace_bytes(int64_t n, int64_t nrhs, int64_t krylov_dim, int storage);
+int gkomi_cb_gmres_solve_f64_i32(gkomi_stream_t s, int64_t n, int64_t nrhs,
+                                 int64_t nnz, const int32_t* row_ptrs,
+                                 const int32_t* col_idxs, const double* vals,
+                                 int spmv_strategy, int64_t max_row_nnz_hint,
+                                 gkomi_apply_fn precond, void* precond_ctx,
+                                 const double* b, double* x, int64_t krylov_dim,
+                                 int storage, int64_t max_iters,
+                                 double reduction_factor, int baseline,
+                                 void* workspace, size_t workspace_bytes,
+                                 double* host_info);
+int gkomi_cb_gmres_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
+                                gkomi_matrix_apply_fn matrix, void* matrix_ctx,
+                                gkomi_apply_fn precond, void* precond_ctx,
+                                const double* b, double* x, int64_t krylov_dim,
+                                int storage, int64_t max_iters,
+                                double reduction_factor, int baseline,
+                                void* workspace, size_t workspace_bytes,
+                                double* host_info);
+
 /* IDR(s), core/solver/idr_kernels.hpp (semantics: reference/solver/idr_kernels.cpp;
  * initialize :134-189, step_1 :194-219, step_2 :224-244, step_3 :249-287 with
  * update_g_and_u :83-112 and solve_lower_triangular :60-80, compute_omega :292-313).

@@ -157,6 +157,37 @@ def gmres_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, krylov_dim=100, max_
     return _report(info, x2, b, n)
 
 
+CB_GMRES_STORAGES = {"keep": 0, "reduce1": 1, "reduce2": 2, "integer": 3, "ireduce1": 4, "ireduce2": 5}
+
+
+def cb_gmres_solve(gk, n, row_ptrs, col_idxs, vals, b, x=None, krylov_dim=100, storage="reduce1", max_iters=1000,
+                   reduction=1e-10, baseline="rhs_norm", strategy=0, max_row_nnz=-1, precond=None, matrix=None):
+    """CbGmres (GMRES with a compressed Krylov basis) with Combined(Iteration(max_iters), ResidualNorm(reduction,
+    baseline)).  storage: solver::cb_gmres::storage_precision by name -- the basis as double, float, half or scaled
+    int64 / int32 / int16; all arithmetic stays in double.  precond: None or a Preconditioner.  matrix: a
+    gkomi.formats object instead of the CSR arrays.  The result has `forced_resets` besides the usual entries: how often
+    a detected convergence was checked by a forced restart with an explicit residual."""
+    if storage not in CB_GMRES_STORAGES:
+        raise ValueError(f"storage must be one of {sorted(CB_GMRES_STORAGES)}, not {storage!r}")
+    if krylov_dim < 1:
+        raise ValueError("krylov_dim must be positive")
+    st = CB_GMRES_STORAGES[storage]
+    b2, x2, nrhs = _operands(n, b, x, precond)
+    nbytes = gk.cb_gmres_workspace_bytes(n, nrhs, krylov_dim, st)
+    ws, _, stream = _workspace(nbytes, nrhs, b.device)
+    info = np.zeros(3 + 2 * nrhs, dtype=np.float64)   # the usual record, then the number of forced resets
+    tail = (*_callback(precond), b2, x2, krylov_dim, st, max_iters, reduction, BASELINES[baseline], ws, nbytes, info)
+    if matrix is not None:
+        cb = matrix.callback()
+        gk.cb_gmres_solve_op_f64(stream, n, nrhs, cb.fn, cb.ctx_ptr, *tail)
+    else:
+        gk.cb_gmres_solve_f64_i32(stream, n, nrhs, int(vals.numel()), row_ptrs, col_idxs, vals, strategy, max_row_nnz,
+                                  *tail)
+    res = _report(info[:2 + 2 * nrhs], x2, b, n)
+    res["forced_resets"] = int(info[2 + 2 * nrhs])
+    return res
+
+
 def ir_mixed(gk, n, row_ptrs, col_idxs, vals, b, x=None, max_iters=100, reduction=1e-12, baseline="rhs_norm",
              inner_max_iters=100, inner_reduction=1e-2, inner_baseline="rhs_norm", relaxation_factor=1.0,
              strategy=0, max_row_nnz=-1):

@@ -2785,6 +2785,52 @@ protected:
     size_type krylov_dim_;
 };
 
+// CbGmres (include/ginkgo/core/solver/cb_gmres.hpp): GMRES with a compressed Krylov basis.  The enumerators follow
+// cb_gmres.hpp:88-95 and are the `storage` codes of gkomi_cb_gmres_*; for double: double, float, half, int64, int32, int16.
+namespace cb_gmres {
+enum class storage_precision { keep, reduce1, reduce2, integer, ireduce1, ireduce2 };
+}  // namespace cb_gmres
+
+template <typename V = double>
+class CbGmres : public detail::iterative_solver<CbGmres<V>> {
+    using base = detail::iterative_solver<CbGmres<V>>;
+    static_assert(std::is_same<V, double>::value, "CbGmres: double only");
+public:
+    class Factory : public detail::factory_base<CbGmres> {
+    public:
+        Factory& with_krylov_dim(size_type d) { krylov_dim_ = d; return *this; }
+        Factory& with_storage_precision(cb_gmres::storage_precision p) { storage_precision_ = p; return *this; }
+        size_type krylov_dim_{100};  // cb_gmres.hpp:186, 161-162
+        cb_gmres::storage_precision storage_precision_{cb_gmres::storage_precision::reduce1};
+    };
+    static Factory build() { return Factory{}; }
+    size_type get_krylov_dim() const noexcept { return krylov_dim_; }
+    cb_gmres::storage_precision get_storage_precision() const noexcept { return storage_precision_; }
+    // how often the last apply checked a detected convergence by a forced restart (cb_gmres.cpp:315-383)
+    int64_t get_last_forced_resets() const noexcept { return last_forced_resets_; }
+protected:
+    friend class detail::factory_base<CbGmres>;
+    CbGmres(const Factory* f, std::shared_ptr<const LinOp> A)
+        : base(f, std::move(A)), krylov_dim_(f->krylov_dim_), storage_precision_(f->storage_precision_) {}
+    using base::apply_impl;
+    void apply_impl(const LinOp* b, LinOp* x) const override
+    {
+        const auto& st = this->settings_;
+        typename base::frame f(*this, b, x);
+        const int storage = static_cast<int>(storage_precision_);
+        f.info.assign(3 + 2 * f.nrhs, 0.0);  // this driver's record ends with the number of forced resets
+        array<char> ws(this->exec_, gkomi_cb_gmres_workspace_bytes(f.n, f.nrhs, krylov_dim_, storage));
+        GKOMI_CALL(gkomi_cb_gmres_solve_op_f64(nullptr, f.n, f.nrhs, f.system.fn, f.system.ctx, f.precond.fn, f.precond.ctx, f.db->get_const_values(), f.dx->get_values(),
+                                               krylov_dim_, storage, st.max_iters, st.reduction_factor, detail::baseline_code(st.baseline), ws.get_data(), ws.get_num_elems(),
+                                               f.info.data()));
+        last_forced_resets_ = static_cast<int64_t>(f.info[2 + 2 * f.nrhs]);
+        f.report();
+    }
+    size_type krylov_dim_;
+    cb_gmres::storage_precision storage_precision_;
+    mutable int64_t last_forced_resets_{0};
+};
+
 // LowerTrs / UpperTrs (include/ginkgo/core/solver/triangular.hpp)
 template <bool Lower, typename V = double, typename I = int32>
 class Trs : public LinOp {
