@@ -18,6 +18,7 @@
 // operations (-ffp-contract=off), so everything that is not a cross-lane sum equals the
 // reference bit for bit given equal inputs.
 #include "internal.hpp"
+#include "krylov_driver.hpp"
 
 #include <hip/hip_fp16.h>
 
@@ -541,87 +542,6 @@ __global__ __launch_bounds__(256) void cb_restart_clear_kernel(int64_t n, int64_
     }
 }
 
-__global__ __launch_bounds__(256) void cb_initialize_kernel(int64_t n, int64_t nrhs, int64_t krylov_dim,
-                                                            const double* __restrict__ b, int64_t b_stride,
-                                                            double* __restrict__ residual, int64_t r_stride,
-                                                            double* __restrict__ gsin, double* __restrict__ gcos,
-                                                            uint8_t* __restrict__ stop_status)
-{
-    const int64_t gid = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x;
-    const int64_t step = static_cast<int64_t>(gridDim.x) * 256;
-    for (int64_t i = gid; i < krylov_dim * nrhs; i += step) {
-        gsin[i] = 0.0;
-        gcos[i] = 0.0;
-    }
-    for (int64_t i = gid; i < nrhs; i += step) stop_status[i] = 0;
-    for (int64_t i = gid; i < n * nrhs; i += step) {
-        const int64_t row = i / nrhs, col = i % nrhs;
-        residual[row * r_stride + col] = b[row * b_stride + col];
-    }
-}
-
-// givens_rotation + calculate_next_residual_norm (:179-256), one thread per column, the
-// reference's operations in its order; bump: arnoldi's final_iter_nums update (:418-422)
-__global__ __launch_bounds__(256) void cb_givens_kernel(int64_t nrhs, double* __restrict__ gsin,
-                                                        double* __restrict__ gcos, double* __restrict__ residual_norm,
-                                                        double* __restrict__ rnc, double* __restrict__ hess,
-                                                        int64_t h_stride, int64_t iter,
-                                                        uint64_t* __restrict__ final_iter_nums, int bump,
-                                                        const uint8_t* __restrict__ stop_status)
-{
-    for (int64_t i = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x; i < nrhs;
-         i += static_cast<int64_t>(gridDim.x) * 256) {
-        if (status_has_stopped(stop_status[i])) continue;
-        if (bump) final_iter_nums[i]++;
-        for (int64_t j = 0; j < iter; ++j) {
-            const double c = gcos[j * nrhs + i], s = gsin[j * nrhs + i];
-            const double h0 = hess[j * h_stride + i], h1 = hess[(j + 1) * h_stride + i];
-            const double temp = c * h0 + s * h1;
-            hess[(j + 1) * h_stride + i] = -s * h0 + c * h1;
-            hess[j * h_stride + i] = temp;
-        }
-        const double this_h = hess[iter * h_stride + i];
-        const double next_h = hess[(iter + 1) * h_stride + i];
-        double c, s;
-        if (this_h == 0.0) {
-            c = 0.0;
-            s = 1.0;
-        } else {
-            const double scale = fabs(this_h) + fabs(next_h);
-            const double hyp = scale * sqrt(fabs(this_h / scale) * fabs(this_h / scale) +
-                                            fabs(next_h / scale) * fabs(next_h / scale));
-            c = this_h / hyp;
-            s = next_h / hyp;
-        }
-        gcos[iter * nrhs + i] = c;
-        gsin[iter * nrhs + i] = s;
-        hess[iter * h_stride + i] = c * this_h + s * next_h;
-        hess[(iter + 1) * h_stride + i] = 0.0;
-        const double r = rnc[iter * nrhs + i];
-        const double next_r = -s * r;
-        rnc[(iter + 1) * nrhs + i] = next_r;
-        rnc[iter * nrhs + i] = c * r;
-        residual_norm[i] = fabs(next_r);
-    }
-}
-
-// solve_upper_triangular (:259-279): one thread per column
-__global__ __launch_bounds__(256) void cb_solve_triangular_kernel(int64_t nrhs, const double* __restrict__ rnc,
-                                                                  const double* __restrict__ hessenberg,
-                                                                  int64_t h_stride, double* __restrict__ y,
-                                                                  const uint64_t* __restrict__ final_iter_nums)
-{
-    for (int64_t k = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x; k < nrhs;
-         k += static_cast<int64_t>(gridDim.x) * 256) {
-        const int64_t m = static_cast<int64_t>(final_iter_nums[k]);
-        for (int64_t i = m - 1; i >= 0; --i) {
-            double temp = rnc[i * nrhs + k];
-            for (int64_t j = i + 1; j < m; ++j) temp -= hessenberg[i * h_stride + j * nrhs + k] * y[j * nrhs + k];
-            y[i * nrhs + k] = temp / hessenberg[i * h_stride + i * nrhs + k];
-        }
-    }
-}
-
 // calculate_qy (:282-302): each lane owns its rows and adds the vectors in index order
 template <class S, bool Vec>
 __global__ __launch_bounds__(cb_block) void cb_qy_kernel(int64_t n, int64_t nrhs, const S* __restrict__ basis,
@@ -765,12 +685,8 @@ extern "C" int gkomi_cb_gmres_initialize_f64(gkomi_stream_t s, int64_t n, int64_
                                              int64_t r_stride, double* givens_sin, double* givens_cos,
                                              uint8_t* stop_status)
 {
-    if (n < 0 || nrhs < 0 || krylov_dim < 0) return GKOMI_EINVAL;
-    if (nrhs == 0) return GKOMI_SUCCESS;
-    const int64_t work = std::max<int64_t>(n * nrhs, krylov_dim * nrhs);
-    hipLaunchKernelGGL(cb_initialize_kernel, dim3(grid_for(work, 256)), dim3(256), 0, to_stream(s), n, nrhs,
-                       krylov_dim, b, b_stride, residual, r_stride, givens_sin, givens_cos, stop_status);
-    return check_launch();
+    return gmres_initialize_launch(s, n, nrhs, krylov_dim, b, b_stride, residual, r_stride, givens_sin, givens_cos,
+                                   stop_status);
 }
 
 extern "C" int gkomi_cb_gmres_restart_f64(gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t krylov_dim,
@@ -846,26 +762,13 @@ extern "C" int gkomi_cb_gmres_finish_arnoldi_f64(gkomi_stream_t s, int64_t n, in
     });
 }
 
-static int givens_launch(gkomi_stream_t s, int64_t nrhs, double* givens_sin, double* givens_cos,
-                         double* residual_norm, double* residual_norm_collection, double* hessenberg_iter,
-                         int64_t h_stride, int64_t iter, uint64_t* final_iter_nums, int bump,
-                         const uint8_t* stop_status)
-{
-    if (nrhs < 0 || iter < 0) return GKOMI_EINVAL;
-    if (nrhs == 0) return GKOMI_SUCCESS;
-    hipLaunchKernelGGL(cb_givens_kernel, dim3(grid_for(nrhs, 256)), dim3(256), 0, to_stream(s), nrhs, givens_sin,
-                       givens_cos, residual_norm, residual_norm_collection, hessenberg_iter, h_stride, iter,
-                       final_iter_nums, bump, stop_status);
-    return check_launch();
-}
-
 extern "C" int gkomi_cb_gmres_givens_f64(gkomi_stream_t s, int64_t nrhs, double* givens_sin, double* givens_cos,
                                          double* residual_norm, double* residual_norm_collection,
                                          double* hessenberg_iter, int64_t h_stride, int64_t iter,
                                          const uint8_t* stop_status)
 {
-    return givens_launch(s, nrhs, givens_sin, givens_cos, residual_norm, residual_norm_collection, hessenberg_iter,
-                         h_stride, iter, nullptr, 0, stop_status);
+    return gmres_givens_launch(s, nrhs, givens_sin, givens_cos, residual_norm, residual_norm_collection,
+                               hessenberg_iter, h_stride, iter, nullptr, stop_status);
 }
 
 extern "C" int gkomi_cb_gmres_arnoldi_f64(gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t krylov_dim,
@@ -880,8 +783,8 @@ extern "C" int gkomi_cb_gmres_arnoldi_f64(gkomi_stream_t s, int64_t n, int64_t n
     GKOMI_TRY(gkomi_cb_gmres_finish_arnoldi_f64(s, n, nrhs, krylov_dim, storage, next_krylov_basis, krylov_bases,
                                                 scalars, hessenberg_iter, h_stride, buffer_iter, arnoldi_norm, iter,
                                                 stop_status, num_reorth, workspace, workspace_bytes));
-    return givens_launch(s, nrhs, givens_sin, givens_cos, residual_norm, residual_norm_collection, hessenberg_iter,
-                         h_stride, iter, final_iter_nums, 1, stop_status);
+    return gmres_givens_launch(s, nrhs, givens_sin, givens_cos, residual_norm, residual_norm_collection,
+                               hessenberg_iter, h_stride, iter, final_iter_nums, stop_status);
 }
 
 extern "C" int gkomi_cb_gmres_solve_krylov_f64(gkomi_stream_t s, int64_t n, int64_t nrhs, int storage,
@@ -892,10 +795,11 @@ extern "C" int gkomi_cb_gmres_solve_krylov_f64(gkomi_stream_t s, int64_t n, int6
 {
     if (n < 0 || nrhs < 0 || nrhs > cb_max_nrhs || storage_size(storage) == 0) return GKOMI_EINVAL;
     if (nrhs == 0) return GKOMI_SUCCESS;
+    // every column (the statuses are finalized by now); the restart length is at most the columns of a Hessenberg row
+    GKOMI_TRY(gmres_solve_triangular_launch(s, nrhs, h_stride / nrhs, residual_norm_collection, hessenberg, h_stride, y,
+                                            final_iter_nums, nullptr));
+    if (n == 0) return GKOMI_SUCCESS;
     hipStream_t stream = to_stream(s);
-    hipLaunchKernelGGL(cb_solve_triangular_kernel, dim3(grid_for(nrhs, 256)), dim3(256), 0, stream, nrhs,
-                       residual_norm_collection, hessenberg, h_stride, y, final_iter_nums);
-    if (n == 0) return check_launch();
     const bool vec = vector_path(n, nrhs, storage, krylov_bases, before_preconditioner, before_preconditioner);
     const dim3 grid(sweep_blocks(n, storage), static_cast<unsigned>(nrhs));
     return dispatch_storage(storage, vec, [&](auto tag, auto vtag) {
@@ -910,83 +814,77 @@ extern "C" int gkomi_cb_gmres_solve_krylov_f64(gkomi_stream_t s, int64_t n, int6
 namespace {
 
 struct cb_layout {
-    size_t residual, next, pv, before, after, basis, scalars, hess, buffer, gsin, gcos, rnc, y, arnoldi_norm, small,
-        fin, red, step, total;
+    // 5 vectors (residual, next, pv, before, after); tau is the implicit residual norm, of the scalars row 0 is
+    // final_iter_nums and rows 1-3 are arnoldi_norm
+    solver_layout base;
+    size_t basis, scalars, hess, buffer, gsin, gcos, rnc, y, step, total;
 };
 
 cb_layout make_cb_layout(int64_t n, int64_t nrhs, int64_t d, int storage)
 {
     cb_layout l{};
-    const size_t vec = align256(sizeof(double) * static_cast<size_t>(n) * nrhs);
-    size_t off = 0;
-    l.residual = off; off += vec;
-    l.next = off; off += vec;
-    l.pv = off; off += vec;
-    l.before = off; off += vec;
-    l.after = off; off += vec;
-    l.basis = off; off += align256(gkomi_cb_gmres_basis_bytes(n, nrhs, d, storage));
-    l.scalars = off; off += align256(sizeof(double) * static_cast<size_t>((d + 1) * nrhs));
-    l.hess = off; off += align256(sizeof(double) * static_cast<size_t>((d + 1) * d * nrhs));
-    l.buffer = off; off += align256(sizeof(double) * static_cast<size_t>((d + 1) * nrhs));
-    l.gsin = off; off += align256(sizeof(double) * static_cast<size_t>(d * nrhs));
-    l.gcos = off; off += align256(sizeof(double) * static_cast<size_t>(d * nrhs));
-    l.rnc = off; off += align256(sizeof(double) * static_cast<size_t>((d + 1) * nrhs));
-    l.y = off; off += align256(sizeof(double) * static_cast<size_t>(d * nrhs));
-    l.arnoldi_norm = off; off += align256(sizeof(double) * 3 * static_cast<size_t>(nrhs));
-    // residual_norm, orig_tau, one, neg_one (nrhs each), then stop_status + flags
-    l.small = off; off += align256(sizeof(double) * 4 * static_cast<size_t>(nrhs) + nrhs + 16);
-    l.fin = off; off += align256(sizeof(uint64_t) * static_cast<size_t>(nrhs));
-    l.red = off; off += align256(gkomi_dense_reduction_workspace_bytes(n, nrhs) + 8);
-    l.step = off; off += step_workspace_bytes(nrhs, d);
+    l.base = make_solver_layout(n, nrhs, 5);
+    size_t off = l.base.total;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += align256(bytes);
+        return at;
+    };
+    const size_t row = sizeof(double) * static_cast<size_t>(nrhs);
+    l.basis = take(gkomi_cb_gmres_basis_bytes(n, nrhs, d, storage));
+    l.scalars = take(row * (d + 1));
+    l.hess = take(row * (d + 1) * d);
+    l.buffer = take(row * (d + 1));
+    l.gsin = take(row * d);
+    l.gcos = take(row * d);
+    l.rnc = take(row * (d + 1));
+    l.y = take(row * d);
+    l.step = take(step_workspace_bytes(nrhs, d));
     l.total = off;
     return l;
 }
 
+struct cb_gmres_params {
+    int64_t krylov_dim;
+    int storage;
+};
+
 // CbGmres::apply_dense_impl (core/solver/cb_gmres.cpp:204-487) as the reference's kernel
-// sequence.  The host looks at the two flags of the criterion once per check, and at the
-// statuses when one of them is set, which is where the reference looks (:336-344).
-int cb_gmres_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, gkomi_apply_fn precond,
-                        void* precond_ctx, const double* b, double* x, int64_t krylov_dim, int storage,
-                        int64_t max_iters, double reduction_factor, int baseline, void* workspace,
-                        size_t workspace_bytes, double* host_info)
+// sequence.  Of the shared frame the criterion is not used: it is handed the implicit residual norm (c.tau), sets
+// finalized, and the host looks at its two flags once per check and at the statuses when one of them is set, which
+// is where the reference looks (:336-344) and what the forced iterations hang on.
+int cb_gmres_solve_impl(const solve_request& req, const cb_gmres_params& prm)
 {
-    if (n < 0 || nrhs <= 0 || nrhs > cb_max_nrhs || krylov_dim <= 0 || krylov_dim > cb_max_krylov_dim || max_iters < 0) {
+    const gkomi_stream_t s = req.s;
+    const int64_t n = req.n, nrhs = req.nrhs, krylov_dim = prm.krylov_dim;
+    const int storage = prm.storage;
+    if (n < 0 || nrhs <= 0 || nrhs > cb_max_nrhs || krylov_dim <= 0 || krylov_dim > cb_max_krylov_dim ||
+        req.max_iters < 0 || req.baseline < 0 || req.baseline > 2 || storage_size(storage) == 0) {
         return GKOMI_EINVAL;
     }
-    if (baseline < 0 || baseline > 2 || storage_size(storage) == 0) return GKOMI_EINVAL;
     const cb_layout l = make_cb_layout(n, nrhs, krylov_dim, storage);
-    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
-    if (!aligned16(workspace)) return GKOMI_EINVAL;
-    sysmat A = A_;
-    A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * nrhs * 6 +
-                       static_cast<int64_t>(gkomi_cb_gmres_basis_bytes(n, nrhs, krylov_dim, storage)));
-    hipStream_t stream = to_stream(s);
-    char* ws = static_cast<char*>(workspace);
-    auto D = [&](size_t off) { return reinterpret_cast<double*>(ws + off); };
-    double *residual = D(l.residual), *next = D(l.next), *pv = D(l.pv), *before = D(l.before), *after = D(l.after);
-    void* basis = ws + l.basis;
+    driver_common c;
+    GKOMI_TRY(c.init(req, 0, l.base, l.total));
+    if (!aligned16(req.workspace)) return GKOMI_EINVAL;
+    c.residual_id = 2;
+    c.A.note_working_set(static_cast<int64_t>(sizeof(double)) * n * nrhs * 6 +
+                         static_cast<int64_t>(gkomi_cb_gmres_basis_bytes(n, nrhs, krylov_dim, storage)));
+    hipStream_t stream = c.stream;
+    auto D = [&](size_t at) { return reinterpret_cast<double*>(c.ws + at); };
+    double *residual = c.vec(0), *next = c.vec(1), *pv = c.vec(2), *before = c.vec(3), *after = c.vec(4);
+    void* basis = c.ws + l.basis;
     double *scalars = D(l.scalars), *hess = D(l.hess), *buffer = D(l.buffer), *gsin = D(l.gsin), *gcos = D(l.gcos);
-    double *rnc = D(l.rnc), *y = D(l.y), *arnoldi_norm = D(l.arnoldi_norm);
-    double* small = D(l.small);
-    double *residual_norm = small, *orig_tau = small + nrhs, *one = small + 2 * nrhs, *neg_one = small + 3 * nrhs;
-    uint8_t* stop_status = reinterpret_cast<uint8_t*>(small + 4 * nrhs);
-    uint8_t* dev_flags = stop_status + nrhs + (8 - nrhs % 8) % 8;
-    uint64_t* final_iter_nums = reinterpret_cast<uint64_t*>(ws + l.fin);
-    void* red = ws + l.red;
-    const size_t red_bytes = gkomi_dense_reduction_workspace_bytes(n, nrhs) + 8;
-    void* step_ws = ws + l.step;
+    double *rnc = D(l.rnc), *y = D(l.y);
+    double *residual_norm = c.tau, *arnoldi_norm = c.scalars + nrhs;
+    uint64_t* final_iter_nums = reinterpret_cast<uint64_t*>(c.scalars);
+    uint8_t* stop_status = c.stop_status;
+    void* step_ws = c.ws + l.step;
     const size_t step_bytes = step_workspace_bytes(nrhs, krylov_dim);
     const int64_t h_stride = krylov_dim * nrhs;
-    constexpr uint8_t id_iteration = 1, id_residual = 2;
 
-    auto apply_precond = [&](const double* in, double* out) -> int {
-        if (precond == nullptr) return gkomi_dense_copy_f64(s, n, nrhs, in, nrhs, out, nrhs);
-        return precond(precond_ctx, s, in, out);
-    };
     auto residual_and_restart = [&]() -> int {
-        // residual = b - A x; restart (cb_gmres.cpp:280-287 / 405-414)
-        GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, b, nrhs, residual, nrhs));
-        GKOMI_TRY(A.apply(s, nrhs, neg_one, x, one, residual));
+        // residual = b - A x; restart, which takes the norm itself (cb_gmres.cpp:280-287 / 405-414)
+        GKOMI_TRY(c.residual(req, residual));
         return gkomi_cb_gmres_restart_f64(s, n, nrhs, krylov_dim, storage, residual, residual_norm, rnc, arnoldi_norm,
                                           basis, scalars, next, final_iter_nums, 0, step_ws, step_bytes);
     };
@@ -994,23 +892,16 @@ int cb_gmres_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat&
         // x += M^-1 V y (:392-402 / 475-484)
         GKOMI_TRY(gkomi_cb_gmres_solve_krylov_f64(s, n, nrhs, storage, rnc, basis, scalars, hess, h_stride, y, before,
                                                   final_iter_nums));
-        GKOMI_TRY(apply_precond(before, after));
-        return gkomi_dense_add_scaled_f64(s, n, nrhs, one, 1, after, nrhs, x, nrhs);
+        GKOMI_TRY(c.apply_precond(before, after));
+        return gkomi_dense_add_scaled_f64(s, n, nrhs, c.one, 1, after, nrhs, req.x, nrhs);
     };
 
-    GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, one, nrhs, 1.0));
-    GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, neg_one, nrhs, -1.0));
+    GKOMI_TRY(c.fill_ones());
     GKOMI_TRY(gkomi_dense_fill_f64(s, krylov_dim + 1, h_stride, hess, h_stride, 0.0));
     GKOMI_TRY(gkomi_dense_fill_f64(s, krylov_dim + 1, nrhs, scalars, nrhs, 1.0));
-    GKOMI_TRY(gkomi_cb_gmres_initialize_f64(s, n, nrhs, krylov_dim, b, nrhs, residual, nrhs, gsin, gcos, stop_status));
+    GKOMI_TRY(gmres_initialize_launch(s, n, nrhs, krylov_dim, req.b, nrhs, residual, nrhs, gsin, gcos, stop_status));
     GKOMI_TRY(residual_and_restart());
-    if (baseline == 0) {
-        GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, b, nrhs, orig_tau, red, red_bytes));
-    } else if (baseline == 1) {
-        GKOMI_TRY(gkomi_dense_copy_f64(s, 1, nrhs, residual_norm, nrhs, orig_tau, nrhs));
-    } else {
-        GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, orig_tau, nrhs, 1.0));
-    }
+    GKOMI_TRY(c.baseline(req, residual, residual_norm));
 
     long long total_iter = -1;
     int64_t restart_iter = 0;
@@ -1029,12 +920,12 @@ int cb_gmres_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat&
         } else {
             // Combined(Iteration, ResidualNorm).check(RelativeStoppingId, true, ...): set_finalized
             uint8_t flags[2] = {0, 0};  // all stopped, one changed
-            if (total_iter >= max_iters) {
-                GKOMI_TRY(gkomi_set_all_statuses(s, nrhs, id_iteration, 1, stop_status));
+            if (total_iter >= c.max_iters) {
+                GKOMI_TRY(gkomi_set_all_statuses(s, nrhs, c.iteration_id, 1, stop_status));
                 flags[0] = flags[1] = 1;
             } else {
-                GKOMI_TRY(gkomi_residual_norm_f64(s, nrhs, residual_norm, orig_tau, reduction_factor, id_residual, 1,
-                                                  stop_status, dev_flags, flags));
+                GKOMI_TRY(gkomi_residual_norm_f64(s, nrhs, residual_norm, c.orig_tau, c.reduction, c.residual_id, 1,
+                                                  stop_status, c.dev_flags, flags));
             }
             if (flags[0] || flags[1]) {
                 GKOMI_TRY(static_cast<int>(hipMemcpyAsync(host_status.data(), stop_status, nrhs,
@@ -1073,8 +964,8 @@ int cb_gmres_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat&
             GKOMI_TRY(residual_and_restart());
             restart_iter = 0;
         }
-        GKOMI_TRY(apply_precond(next, pv));
-        GKOMI_TRY(A.apply(s, nrhs, nullptr, pv, nullptr, next));
+        GKOMI_TRY(c.apply_precond(next, pv));
+        GKOMI_TRY(c.spmv(pv, next));
         GKOMI_TRY(gkomi_cb_gmres_arnoldi_f64(s, n, nrhs, krylov_dim, storage, next, gsin, gcos, residual_norm, rnc,
                                              basis, scalars, hess + nrhs * restart_iter, h_stride, buffer,
                                              arnoldi_norm, restart_iter, final_iter_nums, stop_status, nullptr,
@@ -1082,21 +973,10 @@ int cb_gmres_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat&
         restart_iter++;
     }
     GKOMI_TRY(update_solution());
-    if (host_info != nullptr) {
-        for (int64_t j = 0; j < nrhs; ++j) {
-            GKOMI_TRY(static_cast<int>(hipMemcpyAsync(host_info + 2 + 2 * j, residual_norm + j, sizeof(double),
-                                                      hipMemcpyDeviceToHost, stream)));
-            GKOMI_TRY(static_cast<int>(hipMemcpyAsync(host_info + 3 + 2 * j, orig_tau + j, sizeof(double),
-                                                      hipMemcpyDeviceToHost, stream)));
-        }
-        int converged = 1;
-        for (int64_t j = 0; j < nrhs; ++j) converged &= (host_status[j] & GKOMI_STATUS_CONVERGED) != 0;
-        host_info[0] = static_cast<double>(total_iter);
-        host_info[1] = static_cast<double>(converged);
-        host_info[2 + 2 * nrhs] = static_cast<double>(forced_resets);
-    }
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-    return precond_status(precond, precond_ctx, s);
+    c.converged = 1;
+    for (int64_t j = 0; j < nrhs; ++j) c.converged &= (host_status[j] & GKOMI_STATUS_CONVERGED) != 0;
+    if (req.host_info != nullptr) req.host_info[2 + 2 * nrhs] = static_cast<double>(forced_resets);
+    return c.report(total_iter, req.host_info);
 }
 
 }  // namespace
@@ -1114,10 +994,9 @@ extern "C" int gkomi_cb_gmres_solve_f64_i32(gkomi_stream_t s, int64_t n, int64_t
                                             int storage, int64_t max_iters, double reduction_factor, int baseline,
                                             void* workspace, size_t workspace_bytes, double* host_info)
 {
-    return cb_gmres_solve_impl(s, n, nrhs,
-                               make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
-                               precond, precond_ctx, b, x, krylov_dim, storage, max_iters, reduction_factor, baseline,
-                               workspace, workspace_bytes, host_info);
+    return cb_gmres_solve_impl({s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, 1, workspace, workspace_bytes, host_info},
+        {krylov_dim, storage});
 }
 
 extern "C" int gkomi_cb_gmres_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs, gkomi_matrix_apply_fn matrix,
@@ -1127,7 +1006,7 @@ extern "C" int gkomi_cb_gmres_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t 
                                            size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return cb_gmres_solve_impl(s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x,
-                               krylov_dim, storage, max_iters, reduction_factor, baseline, workspace, workspace_bytes,
-                               host_info);
+    return cb_gmres_solve_impl({s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, 1, workspace, workspace_bytes, host_info},
+        {krylov_dim, storage});
 }

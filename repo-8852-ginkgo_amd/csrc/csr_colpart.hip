@@ -43,7 +43,6 @@ struct device_buffer {
     }
 };
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct colpart_layout {
     size_t row_ptrs, cols, vals, perm, srow, partial, total;
@@ -54,12 +53,12 @@ colpart_layout make_layout(int64_t nrows, int64_t nnz, int64_t nb, int64_t tile)
     colpart_layout l{};
     const size_t vrows = static_cast<size_t>(nb * nrows);
     size_t off = 0;
-    l.vals = off; off += align_up(sizeof(double) * static_cast<size_t>(nnz + 2), 256);
-    l.partial = off; off += align_up(sizeof(double) * (vrows + 1), 256);
-    l.cols = off; off += align_up(sizeof(int32_t) * static_cast<size_t>(nnz + 2), 256);
-    l.perm = off; off += align_up(sizeof(uint32_t) * static_cast<size_t>(nnz + 2), 256);
-    l.row_ptrs = off; off += align_up(sizeof(int32_t) * (vrows + 1), 256);
-    l.srow = off; off += align_up(sizeof(int32_t) * static_cast<size_t>(gkomi_csr_srow_entries(nnz, tile)), 256);
+    l.vals = off; off += align256(sizeof(double) * static_cast<size_t>(nnz + 2));
+    l.partial = off; off += align256(sizeof(double) * (vrows + 1));
+    l.cols = off; off += align256(sizeof(int32_t) * static_cast<size_t>(nnz + 2));
+    l.perm = off; off += align256(sizeof(uint32_t) * static_cast<size_t>(nnz + 2));
+    l.row_ptrs = off; off += align256(sizeof(int32_t) * (vrows + 1));
+    l.srow = off; off += align256(sizeof(int32_t) * static_cast<size_t>(gkomi_csr_srow_entries(nnz, tile)));
     l.total = off;
     return l;
 }

@@ -27,7 +27,6 @@
 namespace gkomi {
 namespace {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // out[0] = sum a[0..na) (+ sum b[0..nb)), fixed order, one workgroup; out[1]
 // likewise from a2 when given.  The operand of the all-reduce.
@@ -139,7 +138,7 @@ extern "C" size_t gkomi_dist_nonlocal_rows_workspace_bytes(int64_t n_local)
 {
     if (n_local < 0) return 0;
     const size_t scan_bytes = scan_workspace_bytes(n_local + 1);
-    return 2 * align_up(sizeof(int32_t) * (n_local + 1), 256) + align_up(scan_bytes, 256) + 256;
+    return 2 * align256(sizeof(int32_t) * (n_local + 1)) + align256(scan_bytes) + 256;
 }
 
 // rows of the non-local block (CSR over all n_local rows) that have entries:
@@ -156,7 +155,7 @@ extern "C" int gkomi_dist_nonlocal_rows_i32(gkomi_stream_t s, int64_t n_local, c
     }
     hipStream_t stream = to_stream(s);
     char* ws = static_cast<char*>(workspace);
-    const size_t vec = align_up(sizeof(int32_t) * (n_local + 1), 256);
+    const size_t vec = align256(sizeof(int32_t) * (n_local + 1));
     int32_t* flag = reinterpret_cast<int32_t*>(ws);
     int32_t* pos = reinterpret_cast<int32_t*>(ws + vec);
     void* tmp = ws + 2 * vec;
@@ -233,21 +232,21 @@ struct dist_layout {
 dist_layout make_dist_layout(int64_t n, int64_t nl_rows)
 {
     dist_layout l{};
-    const size_t vec = align_up(sizeof(double) * static_cast<size_t>(n > 0 ? n : 1), 256);
+    const size_t vec = align256(sizeof(double) * static_cast<size_t>(n > 0 ? n : 1));
     size_t off = 0;
     l.r = off; off += vec;
     l.z = off; off += vec;
     l.p = off; off += vec;
     l.q = off; off += vec;
     l.scalars = off; off += 256;
-    l.part_a = off; off += align_up(sizeof(double) * max_parts, 256);
-    l.part_b = off; off += align_up(sizeof(double) * max_parts, 256);
+    l.part_a = off; off += align256(sizeof(double) * max_parts);
+    l.part_b = off; off += align256(sizeof(double) * max_parts);
     // the local block's SpMV + dot launch: the row-cut kernel leaves a partial per 256 rows, the nonzero-split one per tile
-    l.part_c = off; off += align_up(sizeof(double) * (spmv_dot_partials_room(n) + 1), 256);
-    l.part_d = off; off += align_up(sizeof(double) * (static_cast<size_t>(ceildiv(nl_rows, 256)) + 1), 256);
+    l.part_c = off; off += align256(sizeof(double) * (spmv_dot_partials_room(n) + 1));
+    l.part_d = off; off += align256(sizeof(double) * (static_cast<size_t>(ceildiv(nl_rows, 256)) + 1));
     l.red_a = off; off += 256;
     l.red_b = off; off += 256;
-    l.red = off; off += align_up(gkomi_dense_reduction_workspace_bytes(n, 1) + 8, 256);
+    l.red = off; off += align256(gkomi_dense_reduction_workspace_bytes(n, 1) + 8);
     l.small = off; off += 256;
     l.total = off;
     return l;

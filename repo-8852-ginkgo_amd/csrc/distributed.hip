@@ -169,7 +169,6 @@ __global__ __launch_bounds__(block) void vector_build_local_kernel(
     }
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct dist_layout {
     size_t local_pos, nonlocal_pos, keys, sorted, unique_pos, unique_keys, scan, sort_tmp, total;
@@ -181,16 +180,16 @@ dist_layout make_layout(int64_t nnz)
     dist_layout l{};
     const size_t n1 = static_cast<size_t>(nnz) + 1;
     size_t off = 0;
-    l.local_pos = off; off += align_up(8 * n1, 256);
-    l.nonlocal_pos = off; off += align_up(8 * n1, 256);
-    l.keys = off; off += align_up(8 * n1, 256);
-    l.sorted = off; off += align_up(8 * n1, 256);
-    l.unique_pos = off; off += align_up(8 * n1, 256);
-    l.unique_keys = off; off += align_up(8 * n1, 256);
-    l.scan = off; off += align_up(gkomi_prefix_sum_workspace_bytes(nnz + 1) + 8, 256);
+    l.local_pos = off; off += align256(8 * n1);
+    l.nonlocal_pos = off; off += align256(8 * n1);
+    l.keys = off; off += align256(8 * n1);
+    l.sorted = off; off += align256(8 * n1);
+    l.unique_pos = off; off += align256(8 * n1);
+    l.unique_keys = off; off += align256(8 * n1);
+    l.scan = off; off += align256(gkomi_prefix_sum_workspace_bytes(nnz + 1) + 8);
     const size_t tmp = nnz > 0 ? radix_sort_workspace_bytes(nnz, sizeof(uint64_t), false) : 0;
     l.sort_tmp_bytes = tmp;
-    l.sort_tmp = off; off += align_up(tmp + 8, 256);
+    l.sort_tmp = off; off += align256(tmp + 8);
     l.total = off;
     return l;
 }

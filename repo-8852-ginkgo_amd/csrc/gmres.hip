@@ -10,6 +10,7 @@
 // side exactly like the reference loops -> bit-identical given equal inputs.
 // HBM: step k moves (5k+8) n values (core/solver/gmres.cpp:217-222).
 #include "cg_persistent.hpp"
+#include "krylov_driver.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -20,6 +21,29 @@
 
 namespace gkomi {
 namespace {
+
+// ---- what the environment switches: the tests' hooks and the A/B switches of tools/, not product settings ----
+inline const char* env(const char* name)
+{
+    const char* e = std::getenv(name);
+    return e != nullptr ? e : "";
+}
+// GKOMI_GMRES_PERSISTENT=0: no single-launch Arnoldi step (read once per process)
+inline bool env_persistent()
+{
+    static const bool on = env("GKOMI_GMRES_PERSISTENT")[0] != '0';
+    return on;
+}
+// GKOMI_GMRES_ARNOLDI=sweep: one meeting per basis vector (gmres_arnoldi_persistent_kernel) instead of one per block
+inline bool env_blocked_sweep() { return std::string(env("GKOMI_GMRES_ARNOLDI")) != "sweep"; }
+// GKOMI_GMRES_SOLVE_KRYLOV=generic: one column is back-substituted by the generic kernel too (bit-identity of the two)
+inline bool env_solve_krylov_from_lds() { return std::string(env("GKOMI_GMRES_SOLVE_KRYLOV")) != "generic"; }
+// GKOMI_MEET_MAX_POLLS: how long a meeting waits
+inline long long env_meet_max_polls()
+{
+    const char* e = env("GKOMI_MEET_MAX_POLLS");
+    return e[0] != 0 ? std::max(1ll, atoll(e)) : 1ll << 22;
+}
 
 constexpr int block = 256;
 
@@ -58,7 +82,9 @@ __global__ __launch_bounds__(block) void gmres_restart_kernel(
     }
 }
 
-// the reference's loop body for right-hand side i (common_gmres_kernels.cpp hessenberg_qr)
+// the reference's loop body for right-hand side i (common_gmres_kernels.cpp hessenberg_qr; the same operations in
+// the same order are cb_gmres_kernels.cpp:179-256, where arnoldi counts the iteration and givens alone does not:
+// final_iter_nums == nullptr)
 __device__ __forceinline__ void hessenberg_qr_column(
     int64_t i, int64_t nrhs, double* __restrict__ gsin, double* __restrict__ gcos,
     double* __restrict__ residual_norm, double* __restrict__ rnc, double* __restrict__ hess,
@@ -66,7 +92,7 @@ __device__ __forceinline__ void hessenberg_qr_column(
     const uint8_t* __restrict__ stop_status)
 {
     if (status_has_stopped(stop_status[i])) return;
-    final_iter_nums[i]++;
+    if (final_iter_nums != nullptr) final_iter_nums[i]++;
     for (int64_t j = 0; j < iter; ++j) {
         const double c = gcos[j * nrhs + i], s = gsin[j * nrhs + i];
         const double h0 = hess[j * h_stride + i], h1 = hess[(j + 1) * h_stride + i];
@@ -119,7 +145,7 @@ __global__ __launch_bounds__(block) void gmres_solve_krylov_kernel(
 {
     for (int64_t k = blockIdx.x * static_cast<int64_t>(block) + threadIdx.x; k < nrhs;
          k += static_cast<int64_t>(gridDim.x) * block) {
-        if (stop_status[k] & GKOMI_STATUS_FINALIZED) continue;
+        if (stop_status != nullptr && (stop_status[k] & GKOMI_STATUS_FINALIZED)) continue;
         const int64_t m = static_cast<int64_t>(final_iter_nums[k]);
         for (int64_t i = m - 1; i >= 0; --i) {
             double temp = rnc[i * nrhs + k];
@@ -141,7 +167,7 @@ __global__ __launch_bounds__(256) void gmres_solve_krylov_single_kernel(
 {
     __shared__ double lh[solve_krylov_max * solve_krylov_max];
     __shared__ double ly[solve_krylov_max];
-    if (stop_status[0] & GKOMI_STATUS_FINALIZED) return;
+    if (stop_status != nullptr && (stop_status[0] & GKOMI_STATUS_FINALIZED)) return;
     const int m = static_cast<int>(final_iter_nums[0]);
     for (int e = threadIdx.x; e < m * m; e += 256) {
         const int i = e / m, j = e % m;
@@ -192,8 +218,6 @@ __global__ __launch_bounds__(block) void gmres_finalize_status_kernel(
         }
     }
 }
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---- fused modified Gram-Schmidt (single right-hand side) ---------------------
 // The reference's Arnoldi step (core/solver/gmres.cpp:300-319) is, per basis
@@ -390,9 +414,6 @@ __global__ __launch_bounds__(arnoldi_block) void gmres_arnoldi_scale_scalar_kern
 // (core/solver/gmres.cpp:300-319); the partial sums are grouped per workgroup.
 // A meeting that times out leaves next_k untouched (w is written at the very
 // end) and raises ctl->overrun: the driver sees it at its next poll.
-struct gmres_stop_record {
-    long long iter;
-};
 
 // what follows the sweep in the reference's iteration, done by one thread of workgroup 0 instead
 // of three more launches: the Givens update of the new Hessenberg column, then -- for the NEXT
@@ -408,7 +429,7 @@ struct gmres_iteration_tail {
     const double* orig_tau;
     double goal;
     uint8_t* flags;
-    gmres_stop_record* record;
+    stop_record* record;  // (krylov_driver.hpp; the phase stays 0)
     long long next_iter;
     int restart_iter;
     host_watch_line* watch;  // the host's view of the solve (internal.hpp), or nullptr
@@ -687,48 +708,89 @@ __global__ __launch_bounds__(arn_block) void gmres_arnoldi_blocked_kernel(
 
 // first iteration at which every column had stopped (-1 until then): the
 // criterion runs on the device at every iteration, the host looks every
-// `gmres_check_every` iterations and before every restart
+// `gmres_check_every` iterations (the request's check_every) and before every restart
 constexpr int64_t gmres_check_every = 4;
 
 __global__ void gmres_record_stop_kernel(const uint8_t* __restrict__ flags, long long iter,
-                                         gmres_stop_record* record, host_watch_line* watch)
+                                         stop_record* record, host_watch_line* watch)
 {
     if (flags[0] && record->iter < 0) record->iter = iter;
     host_watch_publish(watch, iter, record->iter);
 }
 
 struct gmres_layout {
-    size_t residual, pv, before, after, kb, hess, gsin, gcos, rnc, y, small, fin, red, partials, pcg_ctl, pcg_slots,
-        total;
+    // 4 vectors (residual, pv, before, after); tau is the implicit residual norm, row 0 of the scalars is
+    // final_iter_nums, and the two partial arrays of the fused Gram-Schmidt lie in the partials of the fused drivers
+    solver_layout base;
+    size_t kb, hess, gsin, gcos, rnc, y, pcg_ctl, pcg_slots, total;
 };
 
 gmres_layout make_layout(int64_t n, int64_t nrhs, int64_t d)
 {
+    static_assert(3 * fused_vec_max_parts >= 2 * arnoldi_max_blocks, "the partials of the fused Gram-Schmidt");
     gmres_layout l{};
-    const size_t vec = align_up(sizeof(double) * static_cast<size_t>(n) * nrhs, 256);
-    size_t off = 0;
-    l.residual = off; off += vec;
-    l.pv = off; off += vec;
-    l.before = off; off += vec;
-    l.after = off; off += vec;
-    l.kb = off; off += align_up(sizeof(double) * static_cast<size_t>(n) * nrhs * (d + 1), 256);
-    l.hess = off; off += align_up(sizeof(double) * static_cast<size_t>((d + 1) * d * nrhs), 256);
-    l.gsin = off; off += align_up(sizeof(double) * static_cast<size_t>(d * nrhs), 256);
-    l.gcos = off; off += align_up(sizeof(double) * static_cast<size_t>(d * nrhs), 256);
-    l.rnc = off; off += align_up(sizeof(double) * static_cast<size_t>((d + 1) * nrhs), 256);
-    l.y = off; off += align_up(sizeof(double) * static_cast<size_t>(d * nrhs), 256);
-    // residual_norm, orig_tau, one, neg_one (nrhs each), then stop_status + flags
-    l.small = off; off += align_up(sizeof(double) * 4 * static_cast<size_t>(nrhs) + nrhs + 48, 256);
-    l.fin = off; off += align_up(sizeof(uint64_t) * static_cast<size_t>(nrhs), 256);
-    l.red = off; off += align_up(gkomi_dense_reduction_workspace_bytes(n, nrhs) + 8, 256);
-    l.partials = off; off += align_up(sizeof(double) * 2 * arnoldi_max_blocks, 256);
-    l.pcg_ctl = off; off += align_up(sizeof(pcg_control), 256);
-    l.pcg_slots = off; off += align_up(sizeof(pcg_slot) * 2 * (max_parts + pcg_copies) * pcg_default_stride, 256);
-    l.total = off;
+    l.base = make_solver_layout(n, nrhs, 4);
+    size_t off = l.base.total;
+    auto take = [&](int64_t rows) {
+        const size_t at = off;
+        off += align256(sizeof(double) * static_cast<size_t>(rows * nrhs));
+        return at;
+    };
+    l.kb = take(n * (d + 1));
+    l.hess = take((d + 1) * d);
+    l.gsin = take(d);
+    l.gcos = take(d);
+    l.rnc = take(d + 1);
+    l.y = take(d);
+    l.pcg_ctl = off;
+    l.pcg_slots = l.pcg_ctl + align256(sizeof(pcg_control));
+    l.total = l.pcg_slots + align256(sizeof(pcg_slot) * 2 * (max_parts + pcg_copies) * pcg_default_stride);
     return l;
 }
 
 }  // namespace
+
+int gmres_initialize_launch(gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t krylov_dim, const double* b,
+                            int64_t b_stride, double* residual, int64_t r_stride, double* gsin, double* gcos,
+                            uint8_t* stop_status)
+{
+    if (n < 0 || nrhs < 0 || krylov_dim < 0) return GKOMI_EINVAL;
+    if (nrhs == 0) return GKOMI_SUCCESS;
+    const int64_t work = std::max<int64_t>(n * nrhs, krylov_dim * nrhs);
+    hipLaunchKernelGGL(gmres_initialize_kernel, dim3(grid_for(work, block)), dim3(block), 0,
+                       to_stream(s), n, nrhs, krylov_dim, b, b_stride, residual, r_stride,
+                       gsin, gcos, stop_status);
+    return check_launch();
+}
+
+int gmres_givens_launch(gkomi_stream_t s, int64_t nrhs, double* gsin, double* gcos, double* residual_norm, double* rnc,
+                        double* hess_iter, int64_t h_stride, int64_t iter, uint64_t* final_iter_nums,
+                        const uint8_t* stop_status)
+{
+    if (nrhs < 0 || iter < 0) return GKOMI_EINVAL;
+    if (nrhs == 0) return GKOMI_SUCCESS;
+    hipLaunchKernelGGL(gmres_hessenberg_qr_kernel, dim3(grid_for(nrhs, block)), dim3(block), 0,
+                       to_stream(s), nrhs, gsin, gcos, residual_norm, rnc, hess_iter, h_stride, iter,
+                       final_iter_nums, stop_status);
+    return check_launch();
+}
+
+int gmres_solve_triangular_launch(gkomi_stream_t s, int64_t nrhs, int64_t krylov_dim, const double* rnc,
+                                  const double* hessenberg, int64_t h_stride, double* y,
+                                  const uint64_t* final_iter_nums, const uint8_t* stop_status)
+{
+    if (nrhs < 0) return GKOMI_EINVAL;
+    if (nrhs == 0) return GKOMI_SUCCESS;
+    if (nrhs == 1 && krylov_dim <= solve_krylov_max && env_solve_krylov_from_lds()) {
+        hipLaunchKernelGGL(gmres_solve_krylov_single_kernel, dim3(1), dim3(256), 0, to_stream(s), rnc, hessenberg,
+                           h_stride, y, final_iter_nums, stop_status);
+    } else {
+        hipLaunchKernelGGL(gmres_solve_krylov_kernel, dim3(grid_for(nrhs, block)), dim3(block), 0,
+                           to_stream(s), nrhs, rnc, hessenberg, h_stride, y, final_iter_nums, stop_status);
+    }
+    return check_launch();
+}
+
 }  // namespace gkomi
 
 using namespace gkomi;
@@ -738,13 +800,8 @@ extern "C" int gkomi_gmres_initialize_f64(gkomi_stream_t s, int64_t n, int64_t n
                                           double* residual, int64_t r_stride, double* givens_sin,
                                           double* givens_cos, uint8_t* stop_status)
 {
-    if (n < 0 || nrhs < 0 || krylov_dim < 0) return GKOMI_EINVAL;
-    if (nrhs == 0) return GKOMI_SUCCESS;
-    const int64_t work = std::max<int64_t>(n * nrhs, krylov_dim * nrhs);
-    hipLaunchKernelGGL(gmres_initialize_kernel, dim3(grid_for(work, block)), dim3(block), 0,
-                       to_stream(s), n, nrhs, krylov_dim, b, b_stride, residual, r_stride,
-                       givens_sin, givens_cos, stop_status);
-    return check_launch();
+    return gmres_initialize_launch(s, n, nrhs, krylov_dim, b, b_stride, residual, r_stride, givens_sin, givens_cos,
+                                   stop_status);
 }
 
 extern "C" int gkomi_gmres_restart_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
@@ -761,6 +818,7 @@ extern "C" int gkomi_gmres_restart_f64(gkomi_stream_t s, int64_t n, int64_t nrhs
     return check_launch();
 }
 
+// (the two pointers that the shared launches take as optional are not optional here)
 extern "C" int gkomi_gmres_hessenberg_qr_f64(gkomi_stream_t s, int64_t nrhs, double* givens_sin,
                                              double* givens_cos, double* residual_norm,
                                              double* residual_norm_collection,
@@ -768,41 +826,21 @@ extern "C" int gkomi_gmres_hessenberg_qr_f64(gkomi_stream_t s, int64_t nrhs, dou
                                              int64_t iter, uint64_t* final_iter_nums,
                                              const uint8_t* stop_status)
 {
-    if (nrhs < 0 || iter < 0) return GKOMI_EINVAL;
-    if (nrhs == 0) return GKOMI_SUCCESS;
-    hipLaunchKernelGGL(gmres_hessenberg_qr_kernel, dim3(grid_for(nrhs, block)), dim3(block), 0,
-                       to_stream(s), nrhs, givens_sin, givens_cos, residual_norm,
-                       residual_norm_collection, hessenberg_iter, h_stride, iter, final_iter_nums,
-                       stop_status);
-    return check_launch();
+    if (nrhs > 0 && (final_iter_nums == nullptr || stop_status == nullptr)) return GKOMI_EINVAL;
+    return gmres_givens_launch(s, nrhs, givens_sin, givens_cos, residual_norm, residual_norm_collection,
+                               hessenberg_iter, h_stride, iter, final_iter_nums, stop_status);
 }
 
+// (not told the restart length: the most columns a Hessenberg row of that stride holds)
 extern "C" int gkomi_gmres_solve_krylov_f64(gkomi_stream_t s, int64_t nrhs,
                                             const double* residual_norm_collection,
                                             const double* hessenberg, int64_t h_stride, double* y,
                                             const uint64_t* final_iter_nums,
                                             const uint8_t* stop_status)
 {
-    if (nrhs < 0) return GKOMI_EINVAL;
-    if (nrhs == 0) return GKOMI_SUCCESS;
-    hipLaunchKernelGGL(gmres_solve_krylov_kernel, dim3(grid_for(nrhs, block)), dim3(block), 0,
-                       to_stream(s), nrhs, residual_norm_collection, hessenberg, h_stride, y,
-                       final_iter_nums, stop_status);
-    return check_launch();
-}
-
-// the driver's call: it knows the restart length, so the one-column case goes through LDS
-static int solve_krylov_launch(gkomi_stream_t s, int64_t nrhs, int64_t krylov_dim, const double* rnc,
-                               const double* hessenberg, int64_t h_stride, double* y,
-                               const uint64_t* final_iter_nums, const uint8_t* stop_status)
-{
-    const char* e = std::getenv("GKOMI_GMRES_SOLVE_KRYLOV");  // "generic": the test's switch (bit-identity of the two)
-    if (nrhs == 1 && krylov_dim <= solve_krylov_max && (e == nullptr || std::string(e) != "generic")) {
-        hipLaunchKernelGGL(gmres_solve_krylov_single_kernel, dim3(1), dim3(256), 0, to_stream(s), rnc, hessenberg,
-                           h_stride, y, final_iter_nums, stop_status);
-        return check_launch();
-    }
-    return gkomi_gmres_solve_krylov_f64(s, nrhs, rnc, hessenberg, h_stride, y, final_iter_nums, stop_status);
+    if (nrhs > 0 && stop_status == nullptr) return GKOMI_EINVAL;
+    return gmres_solve_triangular_launch(s, nrhs, nrhs > 0 ? h_stride / nrhs : 0, residual_norm_collection,
+                                         hessenberg, h_stride, y, final_iter_nums, stop_status);
 }
 
 extern "C" int gkomi_gmres_multi_axpy_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
@@ -837,225 +875,42 @@ std::atomic<int64_t> gmres_meeting_fallbacks{0};
 extern "C" int64_t gkomi_gmres_meeting_fallbacks(void) { return gmres_meeting_fallbacks.load(); }
 
 namespace {
-int gmres_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_, gkomi_apply_fn precond,
-                     void* precond_ctx, const double* b, double* x, int64_t krylov_dim,
-                     int64_t max_iters, double reduction_factor, int baseline, void* workspace,
-                     size_t workspace_bytes, double* host_info, bool allow_persistent = true)
+
+struct gmres_params {
+    int64_t krylov_dim;
+    bool meetings = true;  // false: the solve after a meeting has timed out, one launch per sum
+};
+
+// ---- the Arnoldi step of one iteration, three ways: next_k = A M^-1 v_k comes in, orthonormal to v_0 .. v_k it goes
+// out, with column restart_iter of the Hessenberg matrix in hess_iter ----------------------------------------------
+
+// what the single-launch step needs besides the vectors
+struct single_launch {
+    int cus;
+    int chunk, rows;  // of the sweep with one meeting per basis vector: rows per workgroup and per thread
+    pcg_control* ctl;
+    pcg_slot* slots;
+    long long meeting, max_polls;
+    bool blocked_sweep, nt_basis;
+};
+
+// One workgroup per CU, w in registers (gmres_arnoldi_blocked_kernel, or gmres_arnoldi_persistent_kernel); the
+// Givens update and the criterion of the next iteration are part of the launch (tail).
+int arnoldi_single_launch(hipStream_t stream, single_launch& sl, int64_t n, double* next_k, const double* kb, int steps,
+                          double* hess_iter, int64_t h_stride, const gmres_iteration_tail& tail)
 {
-    // what this solve moves between two applies of A decides how A is read (internal.hpp)
-    sysmat A = A_;
-    // What stays in the Infinity Cache between two uses (measured on the 108^3 system, 310 MB of basis, 106 MB of
-    // matrix; profiles/r03_arnoldi_blocked.md): when matrix + basis do not fit, the basis is read with nontemporal
-    // loads (it is the larger stream and every vector of it is read once per iteration) and the matrix keeps the
-    // cache -- 30.9 -> 28.7 ms without a preconditioner; behind a preconditioner (its factors or blocks are streams the
-    // driver knows nothing about) the matrix streams as well -- 43.8 -> 42.0 ms with ParILU.
-    const int64_t vec_bytes = static_cast<int64_t>(sizeof(double)) * n * nrhs;
-    const bool nt_basis = A.is_csr() && A.storage_bytes() + vec_bytes * (krylov_dim + 6) > infinity_cache_bytes;
-    A.note_working_set(nt_basis ? vec_bytes * 6 + (precond != nullptr ? infinity_cache_bytes : 0)
-                                : vec_bytes * (krylov_dim + 6));
-    if (n < 0 || nrhs <= 0 || krylov_dim <= 0 || max_iters < 0) return GKOMI_EINVAL;
-    if (baseline < 0 || baseline > 2) return GKOMI_EINVAL;
-    const gmres_layout l = make_layout(n, nrhs, krylov_dim);
-    if (workspace == nullptr || workspace_bytes < l.total) return GKOMI_EWORKSPACE;
-    hipStream_t stream = to_stream(s);
-    char* ws = static_cast<char*>(workspace);
-    auto D = [&](size_t off) { return reinterpret_cast<double*>(ws + off); };
-    double *residual = D(l.residual), *pv = D(l.pv), *before = D(l.before), *after = D(l.after);
-    double *kb = D(l.kb), *hess = D(l.hess), *gsin = D(l.gsin), *gcos = D(l.gcos);
-    double *rnc = D(l.rnc), *y = D(l.y);
-    double* small = D(l.small);
-    double *residual_norm = small, *orig_tau = small + nrhs, *one = small + 2 * nrhs,
-           *neg_one = small + 3 * nrhs;
-    uint8_t* stop_status = reinterpret_cast<uint8_t*>(small + 4 * nrhs);
-    uint8_t* dev_flags = stop_status + nrhs + (8 - nrhs % 8) % 8;
-    uint64_t* final_iter_nums = reinterpret_cast<uint64_t*>(ws + l.fin);
-    void* red = ws + l.red;
-    const size_t red_bytes = gkomi_dense_reduction_workspace_bytes(n, nrhs) + 8;
-    const int64_t h_stride = krylov_dim * nrhs;
-    constexpr uint8_t id_iteration = 1, id_residual = 2;
-
-    auto apply_precond = [&](const double* in, double* out) -> int {
-        if (precond == nullptr) return gkomi_dense_copy_f64(s, n, nrhs, in, nrhs, out, nrhs);
-        return precond(precond_ctx, s, in, out);
-    };
-    auto residual_and_restart = [&]() -> int {
-        // residual = b - A x; residual_norm; restart (gmres.cpp:184-195 / 260-275)
-        GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, b, nrhs, residual, nrhs));
-        GKOMI_TRY(A.apply(s, nrhs, neg_one, x, one, residual));
-        GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, residual, nrhs, residual_norm, red,
-                                                red_bytes));
-        return gkomi_gmres_restart_f64(s, n, nrhs, residual, nrhs, residual_norm, rnc, kb, nrhs,
-                                       final_iter_nums);
-    };
-    auto update_solution = [&](int64_t) -> int {
-        GKOMI_TRY(solve_krylov_launch(s, nrhs, krylov_dim, rnc, hess, h_stride, y, final_iter_nums,
-                                               stop_status));
-        GKOMI_TRY(gkomi_gmres_multi_axpy_f64(s, n, nrhs, kb, nrhs, y, before, nrhs,
-                                             final_iter_nums, stop_status));
-        GKOMI_TRY(apply_precond(before, after));
-        return gkomi_dense_add_scaled_f64(s, n, nrhs, one, 1, after, nrhs, x, nrhs);
-    };
-
-    GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, one, nrhs, 1.0));
-    GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, neg_one, nrhs, -1.0));
-    GKOMI_TRY(gkomi_dense_fill_f64(s, krylov_dim + 1, h_stride, hess, h_stride, 0.0));
-    GKOMI_TRY(gkomi_gmres_initialize_f64(s, n, nrhs, krylov_dim, b, nrhs, residual, nrhs, gsin,
-                                         gcos, stop_status));
-    GKOMI_TRY(residual_and_restart());
-    if (baseline == 0) {
-        GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, b, nrhs, orig_tau, red, red_bytes));
-    } else if (baseline == 1) {
-        GKOMI_TRY(gkomi_dense_copy_f64(s, 1, nrhs, residual_norm, nrhs, orig_tau, nrhs));
-    } else {
-        GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, orig_tau, nrhs, 1.0));
-    }
-
-    long long total_iter = -1;
-    int64_t restart_iter = 0;
-    int converged = 0;
-    // The criterion is evaluated on the device at every iteration, exactly where
-    // the reference evaluates it; stopped columns are frozen by their statuses
-    // (final_iter_nums, residual_norm, the Givens data no longer change), so the
-    // iterations the host lets run before it looks change nothing in x.
-    gmres_stop_record* record = reinterpret_cast<gmres_stop_record*>(dev_flags + 8);
-    gmres_stop_record host_record{-1};
-    GKOMI_TRY(static_cast<int>(hipMemcpyAsync(record, &host_record, sizeof(host_record), hipMemcpyHostToDevice, stream)));
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-    int64_t unpolled = 0;
-    // one launch per Arnoldi step (gmres_arnoldi_persistent_kernel) when w fits the register files
-    static const bool persistent_on = [] {
-        const char* e = std::getenv("GKOMI_GMRES_PERSISTENT");
-        return e == nullptr || e[0] != '0';
-    }();
-    // GKOMI_GMRES_ARNOLDI=sweep: one meeting per basis vector (gmres_arnoldi_persistent_kernel) instead of one per
-    // block of them -- the A/B switch of tools/, not a product setting
-    const bool blocked_sweep = [] {
-        const char* e = std::getenv("GKOMI_GMRES_ARNOLDI");
-        return e == nullptr || std::string(e) != "sweep";
-    }();
-    static const int cus = device_cu_count();
-    pcg_control* pctl = reinterpret_cast<pcg_control*>(ws + l.pcg_ctl);
-    pcg_slot* pslots = reinterpret_cast<pcg_slot*>(ws + l.pcg_slots);
-    // (an even chunk of an even n: the blocked sweep loads pairs of rows)
-    const int pchunk = cus > 0 ? static_cast<int>(ceildiv(n, cus) + (n % 2 == 0 ? ceildiv(n, cus) % 2 : 0)) : 0;
-    const int prows = static_cast<int>(ceildiv(pchunk, pcg_block));
-    bool persistent = allow_persistent && persistent_on && nrhs == 1 && cus >= 8 && cus <= max_parts &&
-                      n >= 64 * static_cast<int64_t>(cus) && n <= INT32_MAX && prows <= pcg_max_rows_per_thread &&
-                      persistent_try_acquire();
-    struct release_guard {
-        bool held;
-        ~release_guard() { if (held) persistent_release(); }
-    } release{persistent};
-    long long meeting = 0;
-    bool criterion_done = false;
-    host_watch watch;  // the device reports the iteration it has reached into pinned host memory
-    pcg_control host_ctl{};
-    if (persistent) {
-        hipLaunchKernelGGL(pcg_clear_kernel, dim3(1), dim3(256), 0, stream, pslots, pcg_default_stride,
-                           2 * (cus + pcg_copies), pctl);
-    }
-    auto poll = [&]() -> int {
-        unpolled = 0;
-        GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&host_record, record, sizeof(host_record), hipMemcpyDeviceToHost, stream)));
-        if (persistent) {
-            GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&host_ctl, pctl, sizeof(unsigned int), hipMemcpyDeviceToHost, stream)));
-        }
-        return static_cast<int>(hipStreamSynchronize(stream));
-    };
-    // A meeting of the single-launch Arnoldi step timed out (workgroups not resident together?): the
-    // launches since then returned early, so the Hessenberg column, the Givens terms, the residual norms
-    // and the stop record may be stale or unwritten.  Nothing of the current restart cycle is used: x
-    // still holds the solution of the last COMPLETED restart (only update_solution writes x, and every
-    // path to it passes a poll) -- solve again from there with one launch per sum.  Checked right after
-    // every poll, before update_solution and before the stop / max_iters exits (ADVICE round 2).
-    auto solve_again_without_meetings = [&]() -> int {
-        gmres_meeting_fallbacks.fetch_add(1);
-        release.held = false;
-        persistent_release();
-        const long long done = std::max<long long>(total_iter - restart_iter, 0);
-        const int err = gmres_solve_impl(s, n, nrhs, A, precond, precond_ctx, b, x, krylov_dim,
-                                         std::max<int64_t>(max_iters - done, 0), reduction_factor, baseline,
-                                         workspace, workspace_bytes, host_info, false);
-        if (host_info != nullptr) host_info[0] += static_cast<double>(done);
-        return err;
-    };
-    const long long meet_max_polls = [] {
-        const char* e = std::getenv("GKOMI_MEET_MAX_POLLS");  // test hook: how long a meeting waits
-        return e != nullptr && e[0] != 0 ? std::max(1ll, atoll(e)) : 1ll << 22;
-    }();
-    while (true) {
-        ++total_iter;
-        bool stop = false;
-        if (total_iter >= max_iters) {
-            GKOMI_TRY(poll());  // converged during the iterations not looked at yet?
-            if (persistent && host_ctl.overrun != 0) return solve_again_without_meetings();
-            if (host_record.iter >= 0) {
-                converged = 1;
-                total_iter = host_record.iter;
-            } else {
-                GKOMI_TRY(gkomi_set_all_statuses(s, nrhs, id_iteration, 0, stop_status));
-            }
-            stop = true;
-        } else {
-            // the criterion gets residual_norm directly (gmres.cpp:240-246), not finalized; the
-            // single-launch Arnoldi step of the iteration before has already evaluated it
-            if (!criterion_done) {
-                GKOMI_TRY(gkomi_residual_norm_f64(s, nrhs, residual_norm, orig_tau, reduction_factor,
-                                                  id_residual, 0, stop_status, dev_flags, nullptr));
-                hipLaunchKernelGGL(gmres_record_stop_kernel, dim3(1), dim3(1), 0, stream, dev_flags, total_iter,
-                                   record, watch.dev);
-            }
-            criterion_done = false;
-            ++unpolled;
-            bool look = false;  // a blocking look at device memory
-            if (watch.dev != nullptr) {
-                // the device tells the host how far it is (host_watch): before a restart the host needs the
-                // criterion of THIS iteration, otherwise it only keeps within host_watch_lag iterations
-                const long long target = restart_iter == krylov_dim ? total_iter : total_iter - host_watch_lag;
-                if (target >= 0) {
-                    if (watch.wait(stream, target)) {
-                        host_record.iter = watch.stop_iter();
-                    } else {
-                        look = true;  // nothing to see and the stream has drained: a meeting timed out
-                        watch.dev = nullptr;                 // (or the stores do not reach this host)
-                    }
-                }
-            } else {
-                look = unpolled >= gmres_check_every || restart_iter == krylov_dim;
-            }
-            if (look) {
-                GKOMI_TRY(poll());
-                if (persistent && host_ctl.overrun != 0) return solve_again_without_meetings();
-            }
-            if (host_record.iter >= 0) {
-                stop = true;
-                converged = 1;
-                total_iter = host_record.iter;
-            }
-        }
-        if (stop) break;
-        if (restart_iter == krylov_dim) {
-            GKOMI_TRY(update_solution(restart_iter));
-            GKOMI_TRY(residual_and_restart());
-            restart_iter = 0;
-        }
-        double* this_k = kb + n * nrhs * restart_iter;
-        double* next_k = kb + n * nrhs * (restart_iter + 1);
-        // Identity preconditioner: matrix::Identity::apply copies this_k -- the SpMV reads it in place
-        if (precond != nullptr) GKOMI_TRY(apply_precond(this_k, pv));
-        double* hess_iter = hess + nrhs * restart_iter;
-        GKOMI_TRY(A.apply(s, nrhs, nullptr, precond != nullptr ? pv : this_k, nullptr, next_k));
-        if (persistent) {
-            const int steps = static_cast<int>(restart_iter + 1);
-            const gmres_iteration_tail tail{gsin, gcos, residual_norm, rnc, final_iter_nums, stop_status, orig_tau,
-                                            reduction_factor, dev_flags, record, total_iter + 1,
-                                            static_cast<int>(restart_iter), watch.dev};
-            // pairs of rows per lane of the blocked sweep's 512-thread workgroups (prows <= 8 above: at most 8)
-            const int64_t per = ceildiv(n, cus - 1);  // workgroup 0 serves the meetings
-            const int bchunk = static_cast<int>(per + (n % 2 == 0 ? per % 2 : 0));
-            const int bpairs = static_cast<int>(ceildiv(bchunk, 2 * arn_block));
-            const bool wide = n % 2 == 0 && bchunk % 2 == 0;
-            if (blocked_sweep && cus <= arn_block && bpairs <= 8) {  // (workgroup 0 keeps cus x values of a meeting in LDS)
+    const int cus = sl.cus, pchunk = sl.chunk;
+    pcg_control* pctl = sl.ctl;
+    pcg_slot* pslots = sl.slots;
+    long long& meeting = sl.meeting;
+    const long long meet_max_polls = sl.max_polls;
+    const bool nt_basis = sl.nt_basis;
+    // pairs of rows per lane of the blocked sweep's 512-thread workgroups (rows <= 8: at most 8)
+    const int64_t per = ceildiv(n, cus - 1);  // workgroup 0 serves the meetings
+    const int bchunk = static_cast<int>(per + (n % 2 == 0 ? per % 2 : 0));
+    const int bpairs = static_cast<int>(ceildiv(bchunk, 2 * arn_block));
+    const bool wide = n % 2 == 0 && bchunk % 2 == 0;
+    if (sl.blocked_sweep && cus <= arn_block && bpairs <= 8) {  // (workgroup 0 keeps cus x values of a meeting in LDS)
 #define GKOMI_ARNB(R2, B)                                                                                     \
     do {                                                                                                      \
         if (wide) {                                                                                           \
@@ -1069,97 +924,272 @@ int gmres_solve_impl(gkomi_stream_t s, int64_t n, int64_t nrhs, const sysmat& A_
         }                                                                                                     \
         meeting += (steps + (B) - 1) / (B) + 1;                                                               \
     } while (0)
-                // block sizes measured on the 108^3 system (5 pairs per lane): 3 vectors 31.1 ms per solve, 4 (spills
-                // seven registers) 32.2, 2 32.7 -- the sweep is bound by the basis' bytes, not by its meetings
-                if (bpairs <= 1) {
-                    GKOMI_ARNB(1, 4);
-                } else if (bpairs <= 3) {
-                    GKOMI_ARNB(3, 4);
-                } else if (bpairs <= 5) {
-                    GKOMI_ARNB(5, 3);
-                } else {
-                    GKOMI_ARNB(8, 2);
-                }
+        // block sizes measured on the 108^3 system (5 pairs per lane): 3 vectors 31.1 ms per solve, 4 (spills
+        // seven registers) 32.2, 2 32.7 -- the sweep is bound by the basis' bytes, not by its meetings
+        if (bpairs <= 1) {
+            GKOMI_ARNB(1, 4);
+        } else if (bpairs <= 3) {
+            GKOMI_ARNB(3, 4);
+        } else if (bpairs <= 5) {
+            GKOMI_ARNB(5, 3);
+        } else {
+            GKOMI_ARNB(8, 2);
+        }
 #undef GKOMI_ARNB
-            } else {
+    } else {
 #define GKOMI_ARN(R)                                                                                  \
     hipLaunchKernelGGL(gmres_arnoldi_persistent_kernel<R>, dim3(cus), dim3(pcg_block), 0, stream,     \
                        static_cast<int>(n), pchunk, next_k, kb, steps, hess_iter, h_stride, pslots,   \
                        pcg_default_stride, 1, pctl, meeting, meet_max_polls, tail)
-                if (prows <= 1) {
-                    GKOMI_ARN(1);
-                } else if (prows <= 2) {
-                    GKOMI_ARN(2);
-                } else if (prows <= 4) {
-                    GKOMI_ARN(4);
-                } else {
-                    GKOMI_ARN(8);
-                }
-#undef GKOMI_ARN
-                meeting += steps + 1;
-            }
-            criterion_done = true;
-            GKOMI_TRY(check_launch());
-            restart_iter++;
-            continue;  // the Givens update is part of the launch
-        } else if (nrhs == 1 && n > 0) {
-            // fused modified Gram-Schmidt: one pass over next_k per basis vector
-            const int blocks = static_cast<int>(
-                std::min<int64_t>(arnoldi_max_blocks, std::max<int64_t>(1, ceildiv(n / 2 + 1, arnoldi_block))));
-            double* partial[2] = {D(l.partials), D(l.partials) + arnoldi_max_blocks};
-            for (int64_t i = 0; i <= restart_iter + 1; ++i) {
-                const double* prev = i > 0 ? kb + n * (i - 1) : nullptr;
-                const double* with = i <= restart_iter ? kb + n * i : nullptr;
-                double* h_prev = i > 0 ? hess_iter + (i - 1) * h_stride : nullptr;
-                if (n % 2 == 0) {
-                    hipLaunchKernelGGL(gmres_arnoldi_step_kernel, dim3(blocks), dim3(arnoldi_block), 0,
-                                       stream, n, next_k, prev, with, partial[(i + 1) & 1], blocks,
-                                       h_prev, partial[i & 1]);
-                } else {
-                    hipLaunchKernelGGL(gmres_arnoldi_step_scalar_kernel, dim3(blocks), dim3(arnoldi_block), 0,
-                                       stream, n, next_k, prev, with, partial[(i + 1) & 1], blocks,
-                                       h_prev, partial[i & 1]);
-                }
-            }
-            double* hn = hess_iter + (restart_iter + 1) * h_stride;
-            if (n % 2 == 0) {
-                hipLaunchKernelGGL(gmres_arnoldi_scale_kernel, dim3(blocks), dim3(arnoldi_block), 0,
-                                   stream, n, next_k, partial[(restart_iter + 1) & 1], blocks, hn);
-            } else {
-                hipLaunchKernelGGL(gmres_arnoldi_scale_scalar_kernel, dim3(blocks), dim3(arnoldi_block), 0,
-                                   stream, n, next_k, partial[(restart_iter + 1) & 1], blocks, hn);
-            }
-            GKOMI_TRY(check_launch());
+        if (sl.rows <= 1) {
+            GKOMI_ARN(1);
+        } else if (sl.rows <= 2) {
+            GKOMI_ARN(2);
+        } else if (sl.rows <= 4) {
+            GKOMI_ARN(4);
         } else {
-            for (int64_t i = 0; i <= restart_iter; ++i) {
-                double* h = hess_iter + i * h_stride;
-                const double* basis = kb + n * nrhs * i;
-                GKOMI_TRY(gkomi_dense_compute_dot_f64(s, n, nrhs, next_k, nrhs, basis, nrhs, h, red,
-                                                      red_bytes));
-                GKOMI_TRY(gkomi_dense_sub_scaled_f64(s, n, nrhs, h, nrhs, basis, nrhs, next_k, nrhs));
-            }
-            double* hn = hess_iter + (restart_iter + 1) * h_stride;
-            GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, next_k, nrhs, hn, red, red_bytes));
-            GKOMI_TRY(gkomi_dense_inv_scale_f64(s, n, nrhs, hn, nrhs, next_k, nrhs));
+            GKOMI_ARN(8);
         }
-        GKOMI_TRY(gkomi_gmres_hessenberg_qr_f64(s, nrhs, gsin, gcos, residual_norm, rnc, hess_iter,
-                                                h_stride, restart_iter, final_iter_nums,
-                                                stop_status));
+#undef GKOMI_ARN
+        meeting += steps + 1;
+    }
+    return check_launch();
+}
+
+// One right-hand side, a launch per basis vector: the fused modified Gram-Schmidt, one pass over next_k per basis
+// vector.  partials: 2 x arnoldi_max_blocks doubles.
+int arnoldi_fused_gram_schmidt(hipStream_t stream, int64_t n, double* next_k, const double* kb, int64_t restart_iter,
+                               double* hess_iter, int64_t h_stride, double* partials)
+{
+    const int blocks = static_cast<int>(
+        std::min<int64_t>(arnoldi_max_blocks, std::max<int64_t>(1, ceildiv(n / 2 + 1, arnoldi_block))));
+    double* partial[2] = {partials, partials + arnoldi_max_blocks};
+    for (int64_t i = 0; i <= restart_iter + 1; ++i) {
+        const double* prev = i > 0 ? kb + n * (i - 1) : nullptr;
+        const double* with = i <= restart_iter ? kb + n * i : nullptr;
+        double* h_prev = i > 0 ? hess_iter + (i - 1) * h_stride : nullptr;
+        if (n % 2 == 0) {
+            hipLaunchKernelGGL(gmres_arnoldi_step_kernel, dim3(blocks), dim3(arnoldi_block), 0,
+                               stream, n, next_k, prev, with, partial[(i + 1) & 1], blocks,
+                               h_prev, partial[i & 1]);
+        } else {
+            hipLaunchKernelGGL(gmres_arnoldi_step_scalar_kernel, dim3(blocks), dim3(arnoldi_block), 0,
+                               stream, n, next_k, prev, with, partial[(i + 1) & 1], blocks,
+                               h_prev, partial[i & 1]);
+        }
+    }
+    double* hn = hess_iter + (restart_iter + 1) * h_stride;
+    if (n % 2 == 0) {
+        hipLaunchKernelGGL(gmres_arnoldi_scale_kernel, dim3(blocks), dim3(arnoldi_block), 0,
+                           stream, n, next_k, partial[(restart_iter + 1) & 1], blocks, hn);
+    } else {
+        hipLaunchKernelGGL(gmres_arnoldi_scale_scalar_kernel, dim3(blocks), dim3(arnoldi_block), 0,
+                           stream, n, next_k, partial[(restart_iter + 1) & 1], blocks, hn);
+    }
+    return check_launch();
+}
+
+// Several right-hand sides: the reference's sequence (core/solver/gmres.cpp:300-319)
+int arnoldi_reference(const driver_common& c, double* next_k, const double* kb, int64_t restart_iter, double* hess_iter,
+                      int64_t h_stride)
+{
+    const int64_t n = c.n, nrhs = c.nrhs;
+    for (int64_t i = 0; i <= restart_iter; ++i) {
+        double* h = hess_iter + i * h_stride;
+        const double* basis = kb + n * nrhs * i;
+        GKOMI_TRY(c.dot(next_k, basis, h));
+        GKOMI_TRY(gkomi_dense_sub_scaled_f64(c.s, n, nrhs, h, nrhs, basis, nrhs, next_k, nrhs));
+    }
+    double* hn = hess_iter + (restart_iter + 1) * h_stride;
+    GKOMI_TRY(gkomi_dense_compute_norm2_f64(c.s, n, nrhs, next_k, nrhs, hn, c.red, c.red_bytes));
+    return gkomi_dense_inv_scale_f64(c.s, n, nrhs, hn, nrhs, next_k, nrhs);
+}
+
+// Gmres::apply_dense_impl.  Of the shared frame the criterion is not used: it is handed the implicit residual norm
+// (c.tau) directly, not finalized (gmres.cpp:240-246), the single-launch Arnoldi step evaluates it itself, and the
+// host follows it through the watch line.
+int gmres_solve_impl(const solve_request& req, const gmres_params& prm)
+{
+    const gkomi_stream_t s = req.s;
+    const int64_t n = req.n, nrhs = req.nrhs, krylov_dim = prm.krylov_dim;
+    if (n < 0 || nrhs <= 0 || krylov_dim <= 0 || req.max_iters < 0 || req.baseline < 0 || req.baseline > 2) {
+        return GKOMI_EINVAL;
+    }
+    const gmres_layout l = make_layout(n, nrhs, krylov_dim);
+    driver_common c;
+    GKOMI_TRY(c.init(req, 0, l.base, l.total));
+    c.residual_id = 2;
+    // What stays in the Infinity Cache between two uses (measured on the 108^3 system, 310 MB of basis, 106 MB of
+    // matrix; profiles/r03_arnoldi_blocked.md): when matrix + basis do not fit, the basis is read with nontemporal
+    // loads (it is the larger stream and every vector of it is read once per iteration) and the matrix keeps the
+    // cache -- 30.9 -> 28.7 ms without a preconditioner; behind a preconditioner (its factors or blocks are streams the
+    // driver knows nothing about) the matrix streams as well -- 43.8 -> 42.0 ms with ParILU.
+    const int64_t vec_bytes = static_cast<int64_t>(sizeof(double)) * n * nrhs;
+    const bool nt_basis = c.A.is_csr() && c.A.storage_bytes() + vec_bytes * (krylov_dim + 6) > infinity_cache_bytes;
+    c.A.note_working_set(nt_basis ? vec_bytes * 6 + (c.precond != nullptr ? infinity_cache_bytes : 0)
+                                  : vec_bytes * (krylov_dim + 6));
+    hipStream_t stream = c.stream;
+    auto D = [&](size_t at) { return reinterpret_cast<double*>(c.ws + at); };
+    double *residual = c.vec(0), *pv = c.vec(1), *before = c.vec(2), *after = c.vec(3);
+    double *kb = D(l.kb), *hess = D(l.hess), *gsin = D(l.gsin), *gcos = D(l.gcos), *rnc = D(l.rnc), *y = D(l.y);
+    double* residual_norm = c.tau;
+    uint64_t* final_iter_nums = reinterpret_cast<uint64_t*>(c.scalars);
+    const int64_t h_stride = krylov_dim * nrhs;
+
+    auto residual_and_restart = [&]() -> int {
+        // residual = b - A x; residual_norm; restart (gmres.cpp:184-195 / 260-275)
+        GKOMI_TRY(c.residual(req, residual));
+        GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, residual, nrhs, residual_norm, c.red, c.red_bytes));
+        return gkomi_gmres_restart_f64(s, n, nrhs, residual, nrhs, residual_norm, rnc, kb, nrhs, final_iter_nums);
+    };
+    auto update_solution = [&]() -> int {
+        GKOMI_TRY(gmres_solve_triangular_launch(s, nrhs, krylov_dim, rnc, hess, h_stride, y, final_iter_nums,
+                                                c.stop_status));
+        GKOMI_TRY(gkomi_gmres_multi_axpy_f64(s, n, nrhs, kb, nrhs, y, before, nrhs, final_iter_nums, c.stop_status));
+        GKOMI_TRY(c.apply_precond(before, after));
+        return gkomi_dense_add_scaled_f64(s, n, nrhs, c.one, 1, after, nrhs, req.x, nrhs);
+    };
+
+    GKOMI_TRY(c.fill_ones());
+    GKOMI_TRY(gkomi_dense_fill_f64(s, krylov_dim + 1, h_stride, hess, h_stride, 0.0));
+    GKOMI_TRY(gmres_initialize_launch(s, n, nrhs, krylov_dim, req.b, nrhs, residual, nrhs, gsin, gcos, c.stop_status));
+    GKOMI_TRY(residual_and_restart());
+    GKOMI_TRY(c.baseline(req, residual, residual_norm));
+
+    long long total_iter = -1;
+    int64_t restart_iter = 0;
+    // The criterion is evaluated on the device at every iteration, exactly where
+    // the reference evaluates it; stopped columns are frozen by their statuses
+    // (final_iter_nums, residual_norm, the Givens data no longer change), so the
+    // iterations the host lets run before it looks change nothing in x.  c.record: the first iteration at which
+    // every column had stopped.
+    //
+    // One launch per Arnoldi step (arnoldi_single_launch) when w fits the register files:
+    static const int cus = device_cu_count();
+    // (an even chunk of an even n: the blocked sweep loads pairs of rows)
+    const int pchunk = cus > 0 ? static_cast<int>(ceildiv(n, cus) + (n % 2 == 0 ? ceildiv(n, cus) % 2 : 0)) : 0;
+    single_launch sl{cus, pchunk, static_cast<int>(ceildiv(pchunk, pcg_block)),
+                     reinterpret_cast<pcg_control*>(c.ws + l.pcg_ctl), reinterpret_cast<pcg_slot*>(c.ws + l.pcg_slots),
+                     0, env_meet_max_polls(), env_blocked_sweep(), nt_basis};
+    bool persistent = prm.meetings && env_persistent() && nrhs == 1 && cus >= 8 && cus <= max_parts &&
+                      n >= 64 * static_cast<int64_t>(cus) && n <= INT32_MAX && sl.rows <= pcg_max_rows_per_thread &&
+                      persistent_try_acquire();
+    struct release_guard {
+        bool held;
+        ~release_guard() { if (held) persistent_release(); }
+    } release{persistent};
+    bool criterion_done = false;
+    host_watch watch;  // the device reports the iteration it has reached into pinned host memory
+    pcg_control host_ctl{};
+    if (persistent) {
+        hipLaunchKernelGGL(pcg_clear_kernel, dim3(1), dim3(256), 0, stream, sl.slots, pcg_default_stride,
+                           2 * (cus + pcg_copies), sl.ctl);
+    }
+    auto poll = [&]() -> int {
+        if (persistent) {
+            GKOMI_TRY(static_cast<int>(hipMemcpyAsync(&host_ctl, sl.ctl, sizeof(unsigned int), hipMemcpyDeviceToHost, stream)));
+        }
+        return c.poll();
+    };
+    // A meeting of the single-launch Arnoldi step timed out (workgroups not resident together?): the
+    // launches since then returned early, so the Hessenberg column, the Givens terms, the residual norms
+    // and the stop record may be stale or unwritten.  Nothing of the current restart cycle is used: x
+    // still holds the solution of the last COMPLETED restart (only update_solution writes x, and every
+    // path to it passes a poll) -- solve again from there with one launch per sum.  Checked right after
+    // every poll, before update_solution and before the stop / max_iters exits (ADVICE round 2).
+    auto solve_again_without_meetings = [&]() -> int {
+        gmres_meeting_fallbacks.fetch_add(1);
+        release.held = false;
+        persistent_release();
+        const long long done = std::max<long long>(total_iter - restart_iter, 0);
+        solve_request again = req;
+        again.max_iters = std::max<int64_t>(req.max_iters - done, 0);
+        const int err = gmres_solve_impl(again, {krylov_dim, false});
+        if (req.host_info != nullptr) req.host_info[0] += static_cast<double>(done);
+        return err;
+    };
+    while (true) {
+        ++total_iter;
+        bool stop = false;
+        if (total_iter >= c.max_iters) {
+            GKOMI_TRY(poll());  // converged during the iterations not looked at yet?
+            if (persistent && host_ctl.overrun != 0) return solve_again_without_meetings();
+            if (c.host_record.iter >= 0) {
+                c.converged = 1;
+                total_iter = c.host_record.iter;
+            } else {
+                GKOMI_TRY(gkomi_set_all_statuses(s, nrhs, c.iteration_id, 0, c.stop_status));
+            }
+            stop = true;
+        } else {
+            // the single-launch Arnoldi step of the iteration before has already evaluated the criterion
+            if (!criterion_done) {
+                GKOMI_TRY(gkomi_residual_norm_f64(s, nrhs, residual_norm, c.orig_tau, c.reduction, c.residual_id, 0,
+                                                  c.stop_status, c.dev_flags, nullptr));
+                hipLaunchKernelGGL(gmres_record_stop_kernel, dim3(1), dim3(1), 0, stream, c.dev_flags, total_iter,
+                                   c.record, watch.dev);
+            }
+            criterion_done = false;
+            ++c.unpolled;
+            bool look = false;  // a blocking look at device memory
+            if (watch.dev != nullptr) {
+                // the device tells the host how far it is (host_watch): before a restart the host needs the
+                // criterion of THIS iteration, otherwise it only keeps within host_watch_lag iterations
+                const long long target = restart_iter == krylov_dim ? total_iter : total_iter - host_watch_lag;
+                if (target >= 0) {
+                    if (watch.wait(stream, target)) {
+                        c.host_record.iter = watch.stop_iter();
+                    } else {
+                        look = true;  // nothing to see and the stream has drained: a meeting timed out
+                        watch.dev = nullptr;                 // (or the stores do not reach this host)
+                    }
+                }
+            } else {
+                look = c.unpolled >= c.check_every || restart_iter == krylov_dim;
+            }
+            if (look) {
+                GKOMI_TRY(poll());
+                if (persistent && host_ctl.overrun != 0) return solve_again_without_meetings();
+            }
+            if (c.host_record.iter >= 0) {
+                stop = true;
+                c.converged = 1;
+                total_iter = c.host_record.iter;
+            }
+        }
+        if (stop) break;
+        if (restart_iter == krylov_dim) {
+            GKOMI_TRY(update_solution());
+            GKOMI_TRY(residual_and_restart());
+            restart_iter = 0;
+        }
+        double* this_k = kb + n * nrhs * restart_iter;
+        double* next_k = kb + n * nrhs * (restart_iter + 1);
+        // Identity preconditioner: matrix::Identity::apply copies this_k -- the SpMV reads it in place
+        if (c.precond != nullptr) GKOMI_TRY(c.apply_precond(this_k, pv));
+        double* hess_iter = hess + nrhs * restart_iter;
+        GKOMI_TRY(c.spmv(c.precond != nullptr ? pv : this_k, next_k));
+        if (persistent) {
+            const gmres_iteration_tail tail{gsin, gcos, residual_norm, rnc, final_iter_nums, c.stop_status, c.orig_tau,
+                                            c.reduction, c.dev_flags, c.record, total_iter + 1,
+                                            static_cast<int>(restart_iter), watch.dev};
+            GKOMI_TRY(arnoldi_single_launch(stream, sl, n, next_k, kb, static_cast<int>(restart_iter + 1), hess_iter,
+                                            h_stride, tail));
+            criterion_done = true;  // and the Givens update is part of the launch
+        } else {
+            if (nrhs == 1 && n > 0) {
+                GKOMI_TRY(arnoldi_fused_gram_schmidt(stream, n, next_k, kb, restart_iter, hess_iter, h_stride,
+                                                     D(l.base.parts)));
+            } else {
+                GKOMI_TRY(arnoldi_reference(c, next_k, kb, restart_iter, hess_iter, h_stride));
+            }
+            GKOMI_TRY(gmres_givens_launch(s, nrhs, gsin, gcos, residual_norm, rnc, hess_iter, h_stride, restart_iter,
+                                          final_iter_nums, c.stop_status));
+        }
         restart_iter++;
     }
-    GKOMI_TRY(update_solution(restart_iter));
-    if (host_info != nullptr) {
-        for (int64_t j = 0; j < nrhs; ++j) {
-            GKOMI_TRY(static_cast<int>(hipMemcpyAsync(host_info + 2 + 2 * j, residual_norm + j,
-                                                      sizeof(double), hipMemcpyDeviceToHost, stream)));
-            GKOMI_TRY(static_cast<int>(hipMemcpyAsync(host_info + 3 + 2 * j, orig_tau + j,
-                                                      sizeof(double), hipMemcpyDeviceToHost, stream)));
-        }
-        host_info[0] = static_cast<double>(total_iter);
-        host_info[1] = static_cast<double>(converged);
-    }
-    GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
-    return precond_status(precond, precond_ctx, s);
+    GKOMI_TRY(update_solution());
+    return c.report(total_iter, req.host_info);
 }
 }  // namespace
 
@@ -1170,10 +1200,9 @@ extern "C" int gkomi_gmres_solve_f64_i32(
     int64_t max_iters, double reduction_factor, int baseline, void* workspace,
     size_t workspace_bytes, double* host_info)
 {
-    return gmres_solve_impl(s, n, nrhs,
-                            make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
-                            precond, precond_ctx, b, x, krylov_dim, max_iters, reduction_factor, baseline,
-                            workspace, workspace_bytes, host_info);
+    return gmres_solve_impl({s, n, nrhs, make_csr_sysmat(n, nnz, row_ptrs, col_idxs, vals, spmv_strategy, max_row_nnz_hint),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, gmres_check_every, workspace, workspace_bytes,
+        host_info}, {krylov_dim});
 }
 
 extern "C" int gkomi_gmres_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrhs,
@@ -1184,7 +1213,7 @@ extern "C" int gkomi_gmres_solve_op_f64(gkomi_stream_t s, int64_t n, int64_t nrh
                                         size_t workspace_bytes, double* host_info)
 {
     if (matrix == nullptr) return GKOMI_EINVAL;
-    return gmres_solve_impl(s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx), precond, precond_ctx, b, x,
-                            krylov_dim, max_iters, reduction_factor, baseline, workspace, workspace_bytes,
-                            host_info);
+    return gmres_solve_impl({s, n, nrhs, make_op_sysmat(n, matrix, matrix_ctx),
+        precond, precond_ctx, b, x, max_iters, reduction_factor, baseline, gmres_check_every, workspace, workspace_bytes,
+        host_info}, {krylov_dim});
 }

@@ -347,6 +347,20 @@ int trs_iota(hipStream_t stream, int64_t n, int32_t* rows);
 // level_start[l] = first position of level l in level order, level_start[nlevels] = n
 int trs_level_starts(hipStream_t stream, int64_t n, int64_t nlevels, const int32_t* level_sorted, int32_t* level_start);
 
+// ---- the small kernels of gmres.hip, shared with CB-GMRES (cb_gmres.hip) -----------------------------------
+// what gkomi_gmres_initialize_f64 runs
+int gmres_initialize_launch(gkomi_stream_t s, int64_t n, int64_t nrhs, int64_t krylov_dim, const double* b,
+                            int64_t b_stride, double* residual, int64_t r_stride, double* gsin, double* gcos,
+                            uint8_t* stop_status);
+// the Givens update of Hessenberg column `iter`; final_iter_nums == nullptr: the columns' iterations are not counted
+int gmres_givens_launch(gkomi_stream_t s, int64_t nrhs, double* gsin, double* gcos, double* residual_norm, double* rnc,
+                        double* hess_iter, int64_t h_stride, int64_t iter, uint64_t* final_iter_nums,
+                        const uint8_t* stop_status);
+// y = hessenberg \ rnc; stop_status == nullptr: every column, else finalized columns are skipped.  One column of a
+// restart length up to 64 is solved out of LDS (the same bits); krylov_dim may be an upper bound.
+int gmres_solve_triangular_launch(gkomi_stream_t s, int64_t nrhs, int64_t krylov_dim, const double* rnc,
+                                  const double* hessenberg, int64_t h_stride, double* y,
+                                  const uint64_t* final_iter_nums, const uint8_t* stop_status);
 
 // ---- shared by the exact factorizations (ilu.hip) and the direct solver's setup (lu.hip) ---------------
 // compute_lu on an analysed workspace of gkomi_ilu_analyse_i32: what gkomi_ilu_compute_lu_f64_i32 runs

@@ -1,7 +1,8 @@
-// Host side of the Krylov drivers (cg_solver.hip: CG; krylov.hip: BiCGSTAB, FCG, CGS, BiCG, IR; idr.hip: IDR(s)): what
-// a caller asks for, the workspace layout, what every reference-sequence driver shares (r = b - A x, the baseline norm,
-// the deferred criterion), and what the fused single-rhs drivers share on the host.  Included by the sources that hold
-// a driver; everything is file-local.
+// Host side of the Krylov drivers (cg_solver.hip: CG; krylov.hip: BiCGSTAB, FCG, CGS, BiCG, IR; idr.hip: IDR(s);
+// gmres.hip: GMRES; cb_gmres.hip: CB-GMRES): what a caller asks for, the workspace layout, what every
+// reference-sequence driver shares (r = b - A x, the baseline norm, the deferred criterion, the report), and what the
+// fused single-rhs drivers share on the host.  Included by the sources that hold a driver; everything is file-local.
+// The GMRES family takes the frame without check(): its criterion is handed the implicit residual norm (`tau`).
 #pragma once
 #include <algorithm>
 
@@ -157,21 +158,35 @@ struct driver_common {
     {
         return gkomi_dense_compute_dot_f64(s, n, nrhs, a, nrhs, b2, nrhs, result, red, red_bytes);
     }
-    int start(const solve_request& req, double* r)
+    int fill_ones() const
     {
-        const double *b = req.b, *x = req.x;
-        const int baseline = req.baseline;
         GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, one, nrhs, 1.0));
-        GKOMI_TRY(gkomi_dense_fill_f64(s, 1, nrhs, neg_one, nrhs, -1.0));
-        // r = b - A x (r already holds b)
-        GKOMI_TRY(A.apply(s, nrhs, neg_one, x, one, r));
-        if (baseline == 0) {
-            return gkomi_dense_compute_norm2_f64(s, n, nrhs, b, nrhs, orig_tau, red, red_bytes);
+        return gkomi_dense_fill_f64(s, 1, nrhs, neg_one, nrhs, -1.0);
+    }
+    // r = b - A x
+    int residual(const solve_request& req, double* r) const
+    {
+        GKOMI_TRY(gkomi_dense_copy_f64(s, n, nrhs, req.b, nrhs, r, nrhs));
+        return A.apply(s, nrhs, neg_one, req.x, one, r);
+    }
+    // orig_tau; r_norm: the norm of r where the driver has it already (the GMRES family), else nullptr
+    int baseline(const solve_request& req, const double* r, const double* r_norm) const
+    {
+        if (req.baseline == 0) {
+            return gkomi_dense_compute_norm2_f64(s, n, nrhs, req.b, nrhs, orig_tau, red, red_bytes);
         }
-        if (baseline == 1) {
+        if (req.baseline == 1) {
+            if (r_norm != nullptr) return gkomi_dense_copy_f64(s, 1, nrhs, r_norm, nrhs, orig_tau, nrhs);
             return gkomi_dense_compute_norm2_f64(s, n, nrhs, r, nrhs, orig_tau, red, red_bytes);
         }
         return gkomi_dense_fill_f64(s, 1, nrhs, orig_tau, nrhs, 1.0);
+    }
+    int start(const solve_request& req, double* r)
+    {
+        GKOMI_TRY(fill_ones());
+        // r = b - A x (r already holds b)
+        GKOMI_TRY(A.apply(s, nrhs, neg_one, req.x, one, r));
+        return baseline(req, r, nullptr);
     }
     stop_record* record = nullptr;  // device
     int64_t check_every = 1;
@@ -221,11 +236,10 @@ struct driver_common {
         return 0;
     }
     int64_t stop_iter() const { return static_cast<int64_t>(host_record.iter); }
-    int finish(int64_t iter, const double* residual, double* host_info)
+    // host_info = {iterations, converged, (tau, orig_tau) per column}; the wait; the preconditioner's health
+    int report(int64_t iter, double* host_info) const
     {
         if (host_info != nullptr) {
-            // report the norm of the final residual
-            GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, residual, nrhs, tau, red, red_bytes));
             for (int64_t j = 0; j < nrhs; ++j) {
                 GKOMI_TRY(static_cast<int>(hipMemcpyAsync(host_info + 2 + 2 * j, tau + j,
                                                           sizeof(double), hipMemcpyDeviceToHost, stream)));
@@ -237,6 +251,12 @@ struct driver_common {
         }
         GKOMI_TRY(static_cast<int>(hipStreamSynchronize(stream)));
         return precond_status(precond, precond_ctx, s);
+    }
+    int finish(int64_t iter, const double* residual, double* host_info)
+    {
+        // report the norm of the final residual
+        if (host_info != nullptr) GKOMI_TRY(gkomi_dense_compute_norm2_f64(s, n, nrhs, residual, nrhs, tau, red, red_bytes));
+        return report(iter, host_info);
     }
 };
 

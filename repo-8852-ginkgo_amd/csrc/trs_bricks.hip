@@ -108,7 +108,6 @@ struct brick_header {
 };
 static_assert(sizeof(brick_header) <= 256, "the plan header has 256 bytes");
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct brick_layout {
     size_t perm, diag, rdiag, cols, vals, brick_row_begin, brick_step_ptr, step_begin, brick_ext_begin, ext_col,
@@ -120,13 +119,13 @@ brick_layout make_layout(const gkomi_trs_bricks& h)
     brick_layout l{};
     const size_t n = static_cast<size_t>(h.n > 0 ? h.n : 1);
     const size_t nb = static_cast<size_t>(h.nbricks);
-    auto ints = [](size_t count) { return align_up(sizeof(int32_t) * (count > 0 ? count : 1), 256); };
+    auto ints = [](size_t count) { return align256(sizeof(int32_t) * (count > 0 ? count : 1)); };
     size_t off = 256;
     l.perm = off; off += ints(n);
-    l.diag = off; off += align_up(sizeof(double) * n, 256);
-    l.rdiag = off; off += align_up(sizeof(double) * n, 256);
+    l.diag = off; off += align256(sizeof(double) * n);
+    l.rdiag = off; off += align256(sizeof(double) * n);
     l.cols = off; off += ints(n * h.width);
-    l.vals = off; off += align_up(sizeof(double) * n * h.width, 256);
+    l.vals = off; off += align256(sizeof(double) * n * h.width);
     l.brick_row_begin = off; off += ints(nb + 1);
     l.brick_step_ptr = off; off += ints(nb + 1);
     l.step_begin = off; off += ints(static_cast<size_t>(h.n_step_begin));
@@ -139,8 +138,8 @@ brick_layout make_layout(const gkomi_trs_bricks& h)
     l.inv_local = off; off += ints(n);
     l.ext_row_off = off; off += ints(n);
     l.stamps = off; off += std::max<size_t>(8 * 1024, 64 * nb);  // tools only: shader-clock stamps
-    l.image_off = off; off += align_up(sizeof(int64_t) * (nb + 1), 256);
-    l.image = off; off += align_up(static_cast<size_t>(h.image_bytes), 256);
+    l.image_off = off; off += align256(sizeof(int64_t) * (nb + 1));
+    l.image = off; off += align256(static_cast<size_t>(h.image_bytes));
     l.total = off;
     return l;
 }
@@ -1437,7 +1436,7 @@ int analyse_device(gkomi_trs_bricks& h, hipStream_t stream, const int32_t* rp, c
         h.n_pred_idx = static_cast<int64_t>(h.pred_idx.size());
         h.image_bytes = h.image_off.empty() ? 0 : h.image_off.back();
         // the index arrays, in device memory owned by the handle
-        auto ints = [](size_t count) { return align_up(sizeof(int32_t) * (count > 0 ? count : 1), 256); };
+        auto ints = [](size_t count) { return align256(sizeof(int32_t) * (count > 0 ? count : 1)); };
         size_t off = 0;
         h.dev_perm = off; off += ints(n);
         h.dev_row_rank = off; off += ints(n);

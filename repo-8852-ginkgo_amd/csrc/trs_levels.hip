@@ -74,21 +74,20 @@ struct plan_layout {
     size_t perm, slice_off, scout, diag, xp, cols, vals, level_start, total;
 };
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 plan_layout make_plan_layout(int64_t nslices, int64_t entries)
 {
     plan_layout l{};
     size_t off = 256;
-    l.perm = off; off += align_up(sizeof(int32_t) * nslices * slice, 256);
-    l.slice_off = off; off += align_up(sizeof(int32_t) * (nslices + 1), 256);
-    l.scout = off; off += align_up(sizeof(int32_t) * 2 * (nslices + 1), 256);
-    l.diag = off; off += align_up(sizeof(double) * nslices * slice, 256);
-    l.xp = off; off += align_up(sizeof(double) * nslices * slice, 256);
-    l.cols = off; off += align_up(sizeof(int32_t) * entries, 256);
-    l.vals = off; off += align_up(sizeof(double) * entries, 256);
+    l.perm = off; off += align256(sizeof(int32_t) * nslices * slice);
+    l.slice_off = off; off += align256(sizeof(int32_t) * (nslices + 1));
+    l.scout = off; off += align256(sizeof(int32_t) * 2 * (nslices + 1));
+    l.diag = off; off += align256(sizeof(double) * nslices * slice);
+    l.xp = off; off += align256(sizeof(double) * nslices * slice);
+    l.cols = off; off += align256(sizeof(int32_t) * entries);
+    l.vals = off; off += align256(sizeof(double) * entries);
     // first position of every level (nlevels + 1 <= rows + 1 entries): the single-workgroup solve of small factors
-    l.level_start = off; off += align_up(sizeof(int32_t) * (nslices * slice + 1), 256);
+    l.level_start = off; off += align256(sizeof(int32_t) * (nslices * slice + 1));
     l.total = off;
     return l;
 }
@@ -103,19 +102,19 @@ symbolic_layout make_symbolic_layout(int64_t n)
 {
     symbolic_layout l{};
     const int64_t nslices = ceildiv(n, slice);
-    const size_t vec = align_up(sizeof(int32_t) * static_cast<size_t>(n > 0 ? n : 1), 256);
+    const size_t vec = align256(sizeof(int32_t) * static_cast<size_t>(n > 0 ? n : 1));
     size_t off = 0;
     l.level = off; off += vec;
     l.level_sorted = off; off += vec;
     l.rows = off; off += vec;
     l.perm = off; off += vec;
     l.cnt = off; off += vec;
-    l.slice_len = off; off += align_up(sizeof(int32_t) * (nslices + 1), 256);
-    l.slice_off = off; off += align_up(sizeof(int32_t) * (nslices + 1), 256);
+    l.slice_len = off; off += align256(sizeof(int32_t) * (nslices + 1));
+    l.slice_off = off; off += align256(sizeof(int32_t) * (nslices + 1));
     l.flags = off; off += 256;
     const size_t sort_bytes = radix_sort_workspace_bytes(n > 0 ? n : 1, sizeof(uint32_t), true);
     const size_t scan_bytes = scan_workspace_bytes(nslices + 1);
-    l.tmp_bytes = align_up(sort_bytes > scan_bytes ? sort_bytes : scan_bytes, 256) + 256;
+    l.tmp_bytes = align256(sort_bytes > scan_bytes ? sort_bytes : scan_bytes) + 256;
     l.tmp = off; off += l.tmp_bytes;
     l.total = off;
     return l;
