@@ -2509,6 +2509,56 @@ int gkomi_idr_fused_step_3_f64(gkomi_stream_t s, int64_t n, int64_t subspace_dim
     double* m, const double* f_in, double* f_out, double* residual, double* x,
     void* workspace, size_t workspace_bytes);
 
+/* ---- Multigrid (core/solver/multigrid_kernels.hpp) ---------------------- */
+/* multigrid::kcycle_step_1 / kcycle_step_2 / kcycle_check_stop, semantics =
+ * reference/solver/multigrid_kernels.cpp:53-119.  alpha, rho, gamma, beta, zeta,
+ * old_norm, new_norm: 1 x nrhs device rows; v, g, d, e: nrows x nrhs, row-major
+ * with a stride >= nrhs.
+ *  step_1: temp = alpha / rho per column; where temp is finite g -= temp v and
+ *          e *= temp; d = e is written either way.
+ *  step_2: scalar_d = zeta / (beta - gamma gamma / rho), scalar_e = 1 - gamma /
+ *          alpha scalar_d; where both are finite e = scalar_e e + scalar_d d.
+ *  check_stop: *is_stop_device = 1 unless new_norm > rel_tol old_norm in some
+ *          column (one device byte: the reference hands a bool& back, the caller
+ *          reads the byte when it needs the answer).
+ * Elementwise, every expression in the reference's order: bit for bit. */
+int gkomi_multigrid_kcycle_step_1_f64(gkomi_stream_t s, int64_t nrows, int64_t nrhs,
+    const double* alpha, const double* rho, const double* v, int64_t v_stride,
+    double* g, int64_t g_stride, double* d, int64_t d_stride, double* e,
+    int64_t e_stride);
+int gkomi_multigrid_kcycle_step_2_f64(gkomi_stream_t s, int64_t nrows, int64_t nrhs,
+    const double* alpha, const double* rho, const double* gamma, const double* beta,
+    const double* zeta, const double* d, int64_t d_stride, double* e,
+    int64_t e_stride);
+int gkomi_multigrid_kcycle_check_stop_f64(gkomi_stream_t s, int64_t nrhs,
+    const double* old_norm, const double* new_norm, double rel_tol,
+    uint8_t* is_stop_device);
+/* The smoother build_smoother makes (include/ginkgo/core/solver/ir.hpp:314-350):
+ * `sweeps` iterations of solver::Ir (core/solver/ir.cpp:186-276) over a scalar
+ * preconditioner::Jacobi with an Iteration criterion, on a Csr<double, int32> and
+ * one right-hand side, one launch per sweep instead of copy + csr::advanced_spmv +
+ * jacobi::scalar_apply:
+ *     x <- 1 x + (relax (b - A x)) inv_diag
+ * with the residual of a row formed as t = 1 b_i, t += (-1 val_k) x[col_k] over the
+ * stored entries left to right (reference/matrix/csr_kernels.cpp:115-127) and the
+ * update as beta x_i + (alpha t) inv_diag_i (reference/preconditioner/
+ * jacobi_kernels.cpp:573-578), no FMA: bit for bit what the three calls (with a
+ * bit-exact SpMV strategy) and the reference executor give, for any row length,
+ * unsorted rows and repeated columns included.  inv_diag = the output of
+ * gkomi_jacobi_invert_diagonal_f64.  zero_guess != 0: initial_guess_mode::zero --
+ * x on entry is ignored and the first sweep takes b as the residual, no product
+ * with A (ir.cpp:208-214).  The result is in x for any `sweeps` (0 leaves x, or
+ * zeros with zero_guess); a provided guess and an odd count cost one device copy
+ * of x on top.  Nothing blocks.  workspace: gkomi_multigrid_jacobi_sweeps_
+ * workspace_bytes(n) bytes that overlap neither x nor b.  GKOMI_EINVAL before any
+ * launch: nrhs != 1, a negative size, a missing, short or overlapping workspace. */
+size_t gkomi_multigrid_jacobi_sweeps_workspace_bytes(int64_t n);
+int gkomi_multigrid_jacobi_sweeps_f64_i32(gkomi_stream_t s, int64_t n, int64_t nrhs,
+    int64_t nnz, const int32_t* row_ptrs, const int32_t* col_idxs,
+    const double* vals, const double* inv_diag, double relax, const double* b,
+    double* x, int64_t sweeps, int zero_guess, void* workspace,
+    size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

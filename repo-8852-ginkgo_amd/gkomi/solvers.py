@@ -1242,3 +1242,561 @@ class Direct:
         flag = ctypes.c_int(0)
         self.gk.trs_check_overrun(torch.cuda.current_stream().cuda_stream, self.trs_workspace, ctypes.addressof(flag))
         return bool(flag.value)
+
+
+# ---- Multigrid ---------------------------------------------------------------------------------------------------
+# solver::Multigrid over multigrid::MultigridLevel objects (core/solver/multigrid.cpp), multigrid::FixedCoarsening
+# (core/multigrid/fixed_coarsening.cpp) and the smoother build_smoother makes (include/ginkgo/core/solver/ir.hpp:314-350).
+# The recursion runs on the host and only queues work; the one look at the device is the residual norm of a
+# ResidualNorm criterion between two cycles.
+
+CSR_SPLIT = 4            # GKOMI_CSR_SPLIT: the bit-exact nonzero-split SpMV
+MG_CYCLES = ("v", "f", "w")
+MG_MID_CASES = ("both", "post_smoother", "pre_smoother", "standalone")
+INITIAL_GUESS_MODES = ("zero", "rhs", "provided")
+
+
+# The fused sweep walks a row with one lane.  profiles/multigrid_probe.md: at least as fast as the three-call sequence up
+# to the Galerkin coarse matrix of the 1024 x 1024 Poisson problem (524 288 rows, 1 571 840 nonzeros: 13.4 against 24.2 us),
+# slower on the 1024 x 1024 matrix itself (5 238 784 nonzeros: 34.9 against 29.0 us).  No size in between was measured,
+# so the default takes the fused path up to the largest size at which it was seen to win.
+MG_FUSED_MAX_NNZ = 1571840
+
+
+def _mg_fused(fused, nnz):
+    """fused: True / False as given; None: GKOMI_MG_FUSED=0 turns the fused Jacobi sweep off and =1 on for every size
+    (A/B runs), otherwise the measured size rule.  Either path gives the same bits."""
+    import os
+    if fused is not None:
+        return bool(fused)
+    env = os.environ.get("GKOMI_MG_FUSED", "")
+    if env in ("0", "1"):
+        return env == "1"
+    return nnz <= MG_FUSED_MAX_NNZ
+
+
+class _Scalars:
+    """the 1 x 1 device scalars a cycle needs (the reference's one_list / neg_one_list), made once"""
+
+    def __init__(self, dv):
+        self.dv = dv
+        self._vals = {}
+
+    def get(self, value):
+        value = float(value)
+        if value not in self._vals:
+            self._vals[value] = torch.tensor([value], dtype=torch.float64, device=self.dv)
+        return self._vals[value]
+
+
+def _csr_apply(a, b, x, alpha=None, beta=None):
+    """x = A b, or x = alpha A b + beta x with device scalars, through the matrix's own strategy and srow; unlike
+    Csr.apply nothing is uploaded per call"""
+    s = torch.cuda.current_stream().cuda_stream
+    strategy, srow = a.strategy & ~(3 << 29), a.srow()
+    if srow is None and (strategy & 0xff) == CSR_SPLIT:
+        strategy = (strategy & ~0xff) | 1    # no srow (fewer than two nonzeros): the row-cut streaming kernel, bit-exact too
+    a.gk.csr_spmv_srow_f64_i32(s, a.nrows, a.ncols, b.shape[1], a.nnz, a.row_ptrs, a.col_idxs, a.vals, b, b.stride(0), x,
+                               x.stride(0), alpha, beta, strategy | a.gather_flags(), a.max_row_nnz(), srow, a.srow_tile)
+    return x
+
+
+class MultigridLevel:
+    """multigrid::MultigridLevel (include/ginkgo/core/multigrid/multigrid_level.hpp): the fine, restrict, coarse and
+    prolong operators of one level, each a gkomi.formats.Csr (.triple(op) gives (row_ptrs, col_idxs, vals)); as a
+    LinOp it is their composition: apply(b, x[, alpha, beta])."""
+
+    def __init__(self, fine, restrict, coarse, prolong):
+        self.fine, self.restrict, self.coarse, self.prolong = fine, restrict, coarse, prolong
+
+    def get_fine_op(self):
+        return self.fine
+
+    def get_restrict_op(self):
+        return self.restrict
+
+    def get_coarse_op(self):
+        return self.coarse
+
+    def get_prolong_op(self):
+        return self.prolong
+
+    @staticmethod
+    def triple(op):
+        return op.row_ptrs, op.col_idxs, op.vals
+
+    def apply(self, b, x, alpha=None, beta=None):
+        """the level as a LinOp is its composition prolong(coarse(restrict(b)))
+        (include/ginkgo/core/multigrid/multigrid_level.hpp:101-105); alpha and beta act on the last factor"""
+        dv, nrhs = b.device, b.shape[1]
+        t1 = torch.zeros((self.restrict.nrows, nrhs), dtype=torch.float64, device=dv)
+        t2 = torch.zeros_like(t1)
+        self.restrict.apply(b, t1)
+        self.coarse.apply(t1, t2)
+        return self.prolong.apply(t2, x, alpha, beta)
+
+
+def fixed_coarsening(gk, n, row_ptrs, col_idxs, vals, coarse_rows, skip_sorting=False, strategy=0):
+    """multigrid::FixedCoarsening::generate (core/multigrid/fixed_coarsening.cpp:69-118): the fine matrix sorted unless
+    skipped, R = the selection matrix of coarse_rows (values 1, col_idxs = coarse_rows, row_ptrs = 0..m), P = R^T by
+    csr::transpose, A_c = R (A P) by two csr::spgemm; all four carry `strategy` as the reference hands the fine
+    matrix's strategy on.  coarse_rows: an int32 device tensor or a sequence.  -> MultigridLevel"""
+    dv = vals.device
+    s = torch.cuda.current_stream().cuda_stream
+    n = int(n)
+    if not torch.is_tensor(coarse_rows):
+        coarse_rows = torch.from_numpy(np.ascontiguousarray(coarse_rows, dtype=np.int32)).to(dv)
+    m = int(coarse_rows.numel())
+    if m <= 0:
+        raise ValueError("coarse_rows must hold at least one row")
+    ci, v = _sorted_copy(gk, n, row_ptrs, col_idxs, vals, skip_sorting)
+    fine = Csr(gk, n, n, row_ptrs, ci, v, strategy)
+    restrict = Csr(gk, m, n, torch.arange(m + 1, dtype=torch.int32, device=dv),
+                   coarse_rows.to(device=dv, dtype=torch.int32).clone(), torch.ones(m, dtype=torch.float64, device=dv),
+                   strategy)
+    tb = gk.csr_transpose_workspace_bytes(n)
+    prp = torch.zeros(n + 1, dtype=torch.int32, device=dv)
+    pc, pv = _empty_csr(n, m, dv)
+    gk.csr_transpose_f64_i32(s, m, n, m, restrict.row_ptrs, restrict.col_idxs, restrict.vals, prp, pc, pv, _bytes(tb, dv), tb)
+    prolong = Csr(gk, n, m, prp, pc, pv, strategy)
+    coarse = restrict.spgemm(fine.spgemm(prolong))
+    return MultigridLevel(fine, restrict, coarse, prolong)
+
+
+class JacobiSmoother:
+    """build_smoother(Jacobi with max_block_size 1, iterations, relaxation) generated on a Csr: `iterations` sweeps
+    x <- 1 x + (relaxation (b - A x)) inv_diag of Ir with an Iteration criterion.  One right-hand side with unit
+    stride goes through gkomi_multigrid_jacobi_sweeps_f64_i32 (one launch per sweep) where _mg_fused says so (fused
+    True / False, GKOMI_MG_FUSED, or the measured size rule); anything else through copy + csr::advanced_spmv +
+    jacobi::scalar_apply.
+    Both give the same bits.  apply(b, x, zero=False): zero = initial_guess_mode::zero."""
+    uses_initial_guess = True
+    accepts_zero_guess = True
+
+    def __init__(self, gk, matrix, iterations=1, relaxation=0.9, fused=None, inv_diag=None):
+        self.gk, self.matrix, self.iterations, self.relaxation = gk, matrix, int(iterations), float(relaxation)
+        self.fused = _mg_fused(fused, matrix.nnz)
+        dv = matrix.vals.device
+        s = torch.cuda.current_stream().cuda_stream
+        n = matrix.nrows
+        if inv_diag is None:    # else: the inverted diagonal of a generated scalar Jacobi
+            diag = torch.zeros(max(n, 1), dtype=torch.float64, device=dv)[:n]
+            inv_diag = torch.zeros_like(diag)
+            gk.csr_extract_diagonal_f64_i32(s, n, matrix.row_ptrs, matrix.col_idxs, matrix.vals, diag)
+            gk.jacobi_invert_diagonal_f64(s, n, diag, inv_diag)
+        self.inv_diag = inv_diag
+        self.ws_bytes = int(gk.multigrid_jacobi_sweeps_workspace_bytes(n))
+        self.ws = _bytes(self.ws_bytes, dv)
+        self.scalars = _Scalars(dv)
+        self._residual = None
+
+    def apply(self, b, x, zero=False):
+        gk, a, n = self.gk, self.matrix, self.matrix.nrows
+        s = torch.cuda.current_stream().cuda_stream
+        if self.fused and b.shape[1] == 1 and b.stride(0) == 1 and x.stride(0) == 1:
+            gk.multigrid_jacobi_sweeps_f64_i32(s, n, 1, a.nnz, a.row_ptrs, a.col_idxs, a.vals, self.inv_diag, self.relaxation,
+                                               b, x, self.iterations, int(bool(zero)), self.ws, self.ws_bytes)
+            return x
+        nrhs = b.shape[1]
+        if zero:
+            gk.dense_fill_f64(s, n, nrhs, x, x.stride(0), 0.0)
+        if self._residual is None or self._residual.shape != (n, nrhs):
+            self._residual = torch.zeros((n, nrhs), dtype=torch.float64, device=b.device)
+        r = self._residual
+        one, neg_one, relax = self.scalars.get(1.0), self.scalars.get(-1.0), self.scalars.get(self.relaxation)
+        for it in range(self.iterations):
+            src = b
+            if not (it == 0 and zero):
+                gk.dense_copy_f64(s, n, nrhs, b, b.stride(0), r, r.stride(0))
+                _csr_apply(a, x, r, neg_one, one)
+                src = r
+            gk.jacobi_scalar_apply_f64(s, n, nrhs, self.inv_diag, relax, src, src.stride(0), one, x, x.stride(0))
+        return x
+
+
+def jacobi_smoother(gk, matrix, iterations=1, relaxation=0.9, fused=None):
+    """a factory product: the JacobiSmoother of a gkomi.formats.Csr"""
+    return JacobiSmoother(gk, matrix, iterations, relaxation, fused)
+
+
+class _IrSmoother:
+    """build_smoother around a solver that takes no initial guess (multigrid.cpp:148-155): Ir with an Iteration
+    criterion; per iteration r = b - A x, then x = 1 x + relaxation solver(r) as the advanced apply of a solver
+    composes it: the solve into a temporary, then add_scaled.  (A scalar Jacobi, whose advanced apply rounds
+    differently, never gets here: Multigrid hands it to JacobiSmoother.)"""
+    uses_initial_guess = True
+    accepts_zero_guess = True
+
+    def __init__(self, gk, matrix, inner, iterations, relaxation):
+        self.gk, self.matrix, self.inner, self.iterations = gk, matrix, inner, int(iterations)
+        self.scalars = _Scalars(matrix.vals.device)
+        self.relaxation = float(relaxation)
+        self._r = self._z = None
+
+    def apply(self, b, x, zero=False):
+        gk, a, n, nrhs = self.gk, self.matrix, self.matrix.nrows, b.shape[1]
+        s = torch.cuda.current_stream().cuda_stream
+        if zero:
+            gk.dense_fill_f64(s, n, nrhs, x, x.stride(0), 0.0)
+        if self._r is None or self._r.shape != (n, nrhs):
+            self._r = torch.zeros((n, nrhs), dtype=torch.float64, device=b.device)
+            self._z = torch.zeros_like(self._r)
+        one, neg_one, relax = self.scalars.get(1.0), self.scalars.get(-1.0), self.scalars.get(self.relaxation)
+        for it in range(self.iterations):
+            src = b
+            if not (it == 0 and zero):
+                gk.dense_copy_f64(s, n, nrhs, b, b.stride(0), self._r, nrhs)
+                _csr_apply(a, x, self._r, neg_one, one)
+                src = self._r
+            _apply_op(self.inner, src, self._z)
+            gk.dense_add_scaled_f64(s, n, nrhs, relax, 1, self._z, nrhs, x, x.stride(0))
+        return x
+
+
+def _apply_op(op, b, x):
+    """a smoother / solver slot holds an object with apply(b, x) or a callable (b, x)"""
+    return op.apply(b, x) if hasattr(op, "apply") else op(b, x)
+
+
+class _PythonCallback:
+    """a gkomi_apply_fn whose body is a Python apply(b, x): what makes a Multigrid usable as precond= of the solver
+    drivers (they call it with device pointers to contiguous n x nrhs vectors on the stream they run on)"""
+
+    class _View:
+        def __init__(self, ptr, n, nrhs):
+            self.__cuda_array_interface__ = {"shape": (n, nrhs), "typestr": "<f8", "data": (int(ptr), False),
+                                             "version": 2, "strides": None}
+
+    class _Record(ctypes.Structure):
+        """what _check_precond reads: a Python callback sees bare pointers, so it serves the one column count it
+        was made for and a solve with another is refused before any launch"""
+        _fields_ = [("nrhs", ctypes.c_int64)]
+
+    def __init__(self, apply, n, nrhs=1):
+        self.n, self.nrhs = int(n), int(nrhs)
+        self.ctx = self._Record(self.nrhs)
+        self.error = None
+
+        def call(ctx, stream, in_ptr, out_ptr):
+            try:
+                b = torch.as_tensor(self._View(in_ptr, self.n, self.nrhs), device="cuda")
+                x = torch.as_tensor(self._View(out_ptr, self.n, self.nrhs), device="cuda")
+                apply(b, x)
+                return 0
+            except Exception as e:  # noqa: BLE001 - must not unwind through the C driver; the solve fails with EINVAL
+                import traceback
+                traceback.print_exc()
+                self.error = e
+                return -1
+        self._keep = APPLY_FN(call)
+        self.fn = ctypes.cast(self._keep, ctypes.c_void_p).value
+        self.ctx_ptr = None
+
+
+class Multigrid:
+    """solver::Multigrid with the reference's factory parameters (include/ginkgo/core/solver/multigrid.hpp:218-400),
+    generated on a gkomi.formats.Csr.
+
+    mg_level: callables matrix -> MultigridLevel (fixed_coarsening_factory below), chosen per level by level_selector
+    (default: the only one, or the level's index).  pre_ / mid_ / post_smoother: lists of length 0 (no smoother), 1
+    (for all levels) or len(mg_level) of callables matrix -> smoother, None = no smoother at that level; a product
+    whose uses_initial_guess is not True is wrapped like build_smoother does, with smoother_iters and smoother_relax.
+    coarsest_solver: list of callables matrix -> solver (apply(b, x) or a callable (b, x)); empty or None: Identity.
+    criteria: max_iters cycles and, with reduction, ResidualNorm(reduction, baseline) checked before each cycle.
+    fused: False sends a scalar-Jacobi smoother through the three-call sequence instead of the fused sweep, True the
+    other way at every size (None: GKOMI_MG_FUSED, else the measured size rule of MG_FUSED_MAX_NNZ); trace: a list that receives (what, level) for every smoother, restriction, prolongation
+    and coarsest solve, in call order.
+
+    apply(b, x, initial_guess=None) -> dict(x, iterations, converged, residual_norm, baseline_norm);
+    apply_advanced(alpha, b, beta, x): x = alpha MG(b) + beta x on a clone (multigrid.cpp:615-643); solve = apply.
+    As precond= of cg_solve, krylov_solve, gmres_solve and solve_op it is applied through callback()."""
+
+    def __init__(self, gk, matrix, mg_level, pre_smoother=(), mid_smoother=(), post_smoother=(), post_uses_pre=True,
+                 mid_case="standalone", max_levels=10, min_coarse_rows=64, coarsest_solver=(), cycle="v",
+                 smoother_relax=0.9, smoother_iters=1, default_initial_guess="provided", max_iters=1, reduction=None,
+                 baseline="rhs_norm", level_selector=None, solver_selector=None, fused=None, trace=None):
+        self.fused = fused
+        if cycle not in MG_CYCLES or mid_case not in MG_MID_CASES or default_initial_guess not in INITIAL_GUESS_MODES:
+            raise ValueError("cycle, mid_case or default_initial_guess")
+        mg_level, coarsest_solver = list(mg_level), list(coarsest_solver)
+        pre_smoother, mid_smoother, post_smoother = list(pre_smoother), list(mid_smoother), list(post_smoother)
+        # validate (multigrid.cpp:711-748)
+        if len(mg_level) == 0 or any(f is None for f in mg_level):
+            raise ValueError("mg_level needs at least one factory and no null entry")
+        for checked, lst, what in ((True, pre_smoother, "pre_smoother"), (not post_uses_pre, post_smoother, "post_smoother"),
+                                   (mid_case == "standalone", mid_smoother, "mid_smoother")):
+            if checked and len(lst) > 1 and len(lst) != len(mg_level):
+                raise ValueError(f"{what}: {len(lst)} entries for {len(mg_level)} mg_level entries (0, 1 or as many)")
+        self.gk, self.matrix, self.mid_case, self.trace = gk, matrix, mid_case, trace
+        self.max_iters, self.reduction, self.baseline = int(max_iters), reduction, baseline
+        self.default_initial_guess = default_initial_guess
+        self.smoother_relax, self.smoother_iters = smoother_relax, smoother_iters
+        self._cycle = cycle
+        if level_selector is None:
+            level_selector = (lambda level, m: 0) if len(mg_level) == 1 else (lambda level, m: level)
+        if solver_selector is None:
+            solver_selector = lambda level, m: 0
+        # generate (multigrid.cpp:491-574)
+        self.mg_level_list, self.pre_smoother_list, self.mid_smoother_list, self.post_smoother_list = [], [], [], []
+        m, level = matrix, 0
+        while level < max_levels and m.nrows > min_coarse_rows:
+            index = level_selector(level, m)
+            lvl = mg_level[index](m)
+            if lvl.get_coarse_op().nrows == m.nrows:
+                break    # the level does not reduce the dimension
+            self._handle_list(index, lvl.get_fine_op(), pre_smoother, self.pre_smoother_list)
+            if mid_case == "standalone":
+                self._handle_list(index, lvl.get_fine_op(), mid_smoother, self.mid_smoother_list)
+            if not post_uses_pre:
+                self._handle_list(index, lvl.get_fine_op(), post_smoother, self.post_smoother_list)
+            self.mg_level_list.append(lvl)
+            m = lvl.get_coarse_op()
+            level += 1
+        if post_uses_pre:
+            self.post_smoother_list = self.pre_smoother_list
+        if level == 0:
+            raise ValueError("Multigrid generated no level: the matrix has no more than min_coarse_rows rows, "
+                             "max_levels is 0 or the first level does not reduce the dimension")
+        factory = coarsest_solver[solver_selector(level, m)] if coarsest_solver else None
+        self.coarsest_solver = None if factory is None else factory(m)     # None: Identity
+        self.scalars = _Scalars(matrix.vals.device)
+        self._state_nrhs = None
+        self._callback = None
+
+    def _handle_list(self, index, m, factories, out):
+        f = factories[0 if len(factories) == 1 else index] if factories else None
+        if f is None:
+            out.append(None)
+            return
+        s = f(m)
+        if getattr(s, "uses_initial_guess", False) is True:
+            out.append(s)
+        elif isinstance(s, Preconditioner) and isinstance(s.ctx, JacobiCtx) and s.ctx.max_block_size == 1 and isinstance(m, Csr):
+            # Ir over a generated scalar Jacobi with an Iteration criterion: the fused sweep (or its three-call twin)
+            out.append(JacobiSmoother(self.gk, m, self.smoother_iters, self.smoother_relax, self.fused, inv_diag=s.keep[0]))
+        else:
+            out.append(_IrSmoother(self.gk, m, s, self.smoother_iters, self.smoother_relax))
+
+    # accessors of the reference
+    def get_mg_level_list(self):
+        return self.mg_level_list
+
+    def get_pre_smoother_list(self):
+        return self.pre_smoother_list
+
+    def get_mid_smoother_list(self):
+        return self.mid_smoother_list
+
+    def get_post_smoother_list(self):
+        return self.post_smoother_list
+
+    def get_coarsest_solver(self):
+        return self.coarsest_solver
+
+    def get_cycle(self):
+        return self._cycle
+
+    def set_cycle(self, cycle):
+        if cycle not in MG_CYCLES:
+            raise ValueError("cycle")
+        self._cycle = cycle
+
+    def _note(self, what, level):
+        if self.trace is not None:
+            self.trace.append((what, level))
+
+    def _allocate(self, nrhs, dv):
+        """MultigridState::generate: r of every level's rows, g and e of the next level's, once per nrhs"""
+        if self._state_nrhs == nrhs:
+            return
+        vec = lambda rows: torch.zeros((max(rows, 1), nrhs), dtype=torch.float64, device=dv)[:rows]
+        self._r = [vec(lvl.get_fine_op().nrows) for lvl in self.mg_level_list]
+        self._g = [vec(lvl.get_coarse_op().nrows) for lvl in self.mg_level_list]
+        self._e = [vec(lvl.get_coarse_op().nrows) for lvl in self.mg_level_list]
+        self._state_nrhs = nrhs
+
+    def _smooth(self, smoother, b, x, zero=False, level=0):
+        if zero and getattr(smoother, "accepts_zero_guess", False):
+            return smoother.apply(b, x, zero=True)
+        if zero and level != 0:
+            # no initial-guess interface: fill, then apply; x of the first level is zero already (multigrid.cpp:413-419)
+            self.gk.dense_fill_f64(torch.cuda.current_stream().cuda_stream, x.shape[0], x.shape[1], x, x.stride(0), 0.0)
+        return _apply_op(smoother, b, x)
+
+    def _run_cycle(self, cycle, level, m, b, x, x_is_zero, first, end):
+        """MultigridState::run_cycle (multigrid.cpp:377-485); queues work only"""
+        gk = self.gk
+        s = torch.cuda.current_stream().cuda_stream
+        total = len(self.mg_level_list)
+        nrhs = b.shape[1]
+        if level == total:
+            if self.coarsest_solver is None:
+                gk.dense_copy_f64(s, b.shape[0], nrhs, b, b.stride(0), x, x.stride(0))
+            else:
+                self._note("coarsest", level)
+                _apply_op(self.coarsest_solver, b, x)
+            return
+        lvl = self.mg_level_list[level]
+        pre, post = self.pre_smoother_list[level], self.post_smoother_list[level]
+        mid = self.mid_smoother_list[level] if self.mid_case == "standalone" else None
+        one, neg_one = self.scalars.get(1.0), self.scalars.get(-1.0)
+        if (first or self.mid_case in ("both", "pre_smoother")) and pre is not None:
+            self._note("pre", level)
+            self._smooth(pre, b, x, zero=x_is_zero, level=level)
+        r, g, e = self._r[level], self._g[level], self._e[level]
+        gk.dense_copy_f64(s, m.nrows, nrhs, b, b.stride(0), r, r.stride(0))
+        _csr_apply(m, x, r, neg_one, one)
+        self._note("restrict", level)
+        _csr_apply(lvl.get_restrict_op(), r, g)
+        if level + 1 == total:
+            gk.dense_fill_f64(s, e.shape[0], nrhs, e, e.stride(0), 0.0)
+        nxt = self.mg_level_list[level + 1].get_fine_op() if level + 1 < total else lvl.get_coarse_op()
+        self._run_cycle(cycle, level + 1, nxt, g, e, True, True, cycle == "v")
+        if level < total - 1:
+            if cycle == "f":
+                self._run_cycle("v", level + 1, nxt, g, e, False, False, True)
+            elif cycle == "w":
+                self._run_cycle(cycle, level + 1, nxt, g, e, False, False, True)
+        self._note("prolong", level)
+        _csr_apply(lvl.get_prolong_op(), e, x, one, one)
+        if (end or self.mid_case in ("both", "post_smoother")) and post is not None:
+            self._note("post", level)
+            self._smooth(post, b, x)
+        if cycle in ("w", "f") and not end and self.mid_case == "standalone" and mid is not None:
+            self._note("mid", level)
+            self._smooth(mid, b, x)
+
+    def _residual_norm(self, b, x):
+        """the look of a ResidualNorm criterion: || b - A x || per column, on the host"""
+        gk, n, nrhs = self.gk, self.matrix.nrows, b.shape[1]
+        s = torch.cuda.current_stream().cuda_stream
+        r = self._r[0]
+        gk.dense_copy_f64(s, n, nrhs, b, b.stride(0), r, r.stride(0))
+        _csr_apply(self.matrix, x, r, self.scalars.get(-1.0), self.scalars.get(1.0))
+        return self._norm2(r)
+
+    def _norm2(self, v):
+        gk, (n, nrhs) = self.gk, v.shape
+        nb = int(gk.dense_reduction_workspace_bytes(n, nrhs))
+        out = torch.zeros(nrhs, dtype=torch.float64, device=v.device)
+        gk.dense_compute_norm2_f64(torch.cuda.current_stream().cuda_stream, n, nrhs, v, v.stride(0), out,
+                                   _bytes(nb, v.device), nb)
+        return out.cpu().numpy()
+
+    def apply(self, b, x, initial_guess=None):
+        guess = initial_guess or self.default_initial_guess
+        if guess not in INITIAL_GUESS_MODES:
+            raise ValueError("initial_guess")
+        n = self.matrix.nrows
+        b2, x2, nrhs = _operands(n, b, x)
+        gk = self.gk
+        s = torch.cuda.current_stream().cuda_stream
+        if guess == "zero":
+            gk.dense_fill_f64(s, n, nrhs, x2, x2.stride(0), 0.0)
+        elif guess == "rhs":
+            gk.dense_copy_f64(s, n, nrhs, b2, b2.stride(0), x2, x2.stride(0))
+        self._allocate(nrhs, b2.device)
+        it, converged = 0, False
+        res = base = None
+        while True:
+            if it >= self.max_iters:     # Iteration is asked first, as by the drivers and the restatement
+                break
+            if self.reduction is not None:
+                res = self._residual_norm(b2, x2)
+                if base is None:
+                    base = {"rhs_norm": lambda: self._norm2(b2), "initial_resnorm": lambda: res.copy(),
+                            "absolute": lambda: np.ones(nrhs)}[self.baseline]()
+                if np.all(res <= self.reduction * base):
+                    converged = True
+                    break
+            self._run_cycle(self._cycle, 0, self.matrix, b2, x2, it == 0 and guess == "zero", True, True)
+            it += 1
+        return {"x": x2 if b.dim() > 1 else x2.reshape(n), "iterations": it, "converged": converged, "residual_norm": res,
+                "baseline_norm": base}
+
+    solve = apply
+
+    def apply_advanced(self, alpha, b, beta, x, initial_guess=None):
+        guess = initial_guess or self.default_initial_guess
+        n = self.matrix.nrows
+        b2, x2, nrhs = _operands(n, b, x)
+        gk = self.gk
+        s = torch.cuda.current_stream().cuda_stream
+        if guess == "zero":
+            gk.dense_fill_f64(s, n, nrhs, x2, x2.stride(0), 0.0)
+        elif guess == "rhs":
+            gk.dense_copy_f64(s, n, nrhs, b2, b2.stride(0), x2, x2.stride(0))
+        clone = x2.clone()
+        out = self.apply(b2, clone, initial_guess="provided" if guess != "zero" else "zero")
+        gk.dense_scale_f64(s, n, nrhs, self.scalars.get(beta), 1, x2, x2.stride(0))
+        gk.dense_add_scaled_f64(s, n, nrhs, self.scalars.get(alpha), 1, clone, clone.stride(0), x2, x2.stride(0))
+        out["x"] = x2 if b.dim() > 1 else x2.reshape(n)
+        return out
+
+    def callback(self):
+        """(fn, ctx_ptr) holder for the solver drivers: one application with the default initial guess"""
+        if self._callback is None:
+            self._callback = _PythonCallback(lambda b, x: self.apply(b, x), self.matrix.nrows)
+        return self._callback
+
+    # what _callback(precond) of the solve functions reads
+    @property
+    def fn(self):
+        return self.callback().fn
+
+    @property
+    def ctx_ptr(self):
+        return None
+
+    @property
+    def ctx(self):
+        return self.callback().ctx
+
+
+class OrderedCg:
+    """solver::Cg with an Iteration criterion and no preconditioner as the reference's kernel sequence (core/solver/cg.cpp:
+    cg::initialize, step_1, step_2, the SpMV of the matrix's strategy), with both dot products formed in the reference
+    executor's order: a 1 x n by n x 1 product of gkomi_dense_gemm_f64 in its ordered mode, one chain from +0.0.  With a
+    bit-exact SpMV strategy x is the reference executor's bit for bit, which the native Cg drivers (re-ordered
+    reductions) cannot give.  One chain per dot product: for small systems such as the coarsest level of a Multigrid.
+    apply(b, x) takes x as the initial guess; one right-hand side; nothing blocks.
+
+    This is not a general Cg: it exists to reproduce the reference executor's bits where a test pins them, and its serial
+    dot products make it slow on anything large.  Use cg_solve to solve a system."""
+
+    def __init__(self, gk, matrix, max_iters):
+        self.gk, self.matrix, self.max_iters = gk, matrix, int(max_iters)
+        n, dv = matrix.nrows, matrix.vals.device
+        vec = lambda: torch.zeros((max(n, 1), 1), dtype=torch.float64, device=dv)[:n]
+        self.r, self.z, self.p, self.q = vec(), vec(), vec(), vec()
+        self.scalars = torch.zeros(3, dtype=torch.float64, device=dv)      # prev_rho, rho, beta
+        self.status = torch.zeros(8, dtype=torch.uint8, device=dv)
+        self.one_minus = _Scalars(dv)
+
+    def _dot(self, a, b, out):
+        n = self.matrix.nrows
+        self.gk.dense_gemm_f64(torch.cuda.current_stream().cuda_stream, 1, 1, n, a, max(n, 1), b, 1, out, 1, None, None, 1, None, 0)
+
+    def apply(self, b, x):
+        gk, a, n = self.gk, self.matrix, self.matrix.nrows
+        if b.shape[1] != 1:
+            raise ValueError("OrderedCg takes one right-hand side")
+        s = torch.cuda.current_stream().cuda_stream
+        r, z, p, q = self.r, self.z, self.p, self.q
+        prev_rho, rho, beta = self.scalars[0:1], self.scalars[1:2], self.scalars[2:3]
+        gk.cg_initialize_f64(s, n, 1, b, b.stride(0), r, 1, z, 1, p, 1, q, 1, prev_rho, rho, self.status)
+        _csr_apply(a, x, r, self.one_minus.get(-1.0), self.one_minus.get(1.0))
+        for _ in range(self.max_iters):
+            gk.dense_copy_f64(s, n, 1, r, 1, z, 1)          # the Identity preconditioner
+            self._dot(r, z, rho)
+            gk.cg_step_1_f64(s, n, 1, p, 1, z, 1, rho, prev_rho, self.status)
+            _csr_apply(a, p, q)
+            self._dot(p, q, beta)
+            gk.cg_step_2_f64(s, n, 1, x, x.stride(0), r, 1, p, 1, q, 1, beta, rho, self.status)
+            prev_rho, rho = rho, prev_rho
+        return x
+
+
+def fixed_coarsening_factory(gk, select, skip_sorting=False):
+    """an mg_level entry: select(matrix) -> the coarse rows of that matrix"""
+    return lambda m: fixed_coarsening(gk, m.nrows, m.row_ptrs, m.col_idxs, m.vals, select(m), skip_sorting, m.strategy)

@@ -690,6 +690,8 @@ public:
     }
     const dim<2>& get_size() const noexcept { return size_; }
     std::shared_ptr<const Executor> get_executor() const noexcept { return exec_; }
+    // lin_op.hpp:255: does apply(b, x) read x?  false unless a solver says otherwise
+    virtual bool apply_uses_initial_guess() const { return false; }
 protected:
     LinOp(std::shared_ptr<const Executor> exec, const dim<2>& size = dim<2>{}) : exec_(std::move(exec)), size_(size) {}
     void set_size(const dim<2>& s) { size_ = s; }
@@ -2348,7 +2350,38 @@ struct precond_callback {
 
 // ---- solvers ------------------------------------------------------------------------------
 namespace solver {
+// include/ginkgo/core/solver/solver_base.hpp:57-72, 93-124
+enum class initial_guess_mode { zero, rhs, provided };
+class ApplyWithInitialGuess {
+public:
+    virtual ~ApplyWithInitialGuess() = default;
+    virtual void apply_with_initial_guess(const LinOp* b, LinOp* x, initial_guess_mode guess) const = 0;
+    initial_guess_mode get_default_initial_guess() const noexcept { return guess_; }
+protected:
+    void set_default_initial_guess(initial_guess_mode guess) { guess_ = guess; }
+    // prepare_initial_guess (solver_base.hpp:130-150)
+    static void prepare_initial_guess(const LinOp* b, LinOp* x, initial_guess_mode guess)
+    {
+        if (guess == initial_guess_mode::zero) {
+            matrix::detail_fmt::dense(x)->fill(0.0);
+        } else if (guess == initial_guess_mode::rhs) {
+            matrix::detail_fmt::dense(x)->copy_from(matrix::detail_fmt::dense(b));
+        }
+    }
+private:
+    initial_guess_mode guess_{initial_guess_mode::provided};
+};
 namespace detail {
+// GKOMI_MG_FUSED=0 / 1 forces the three-call sequence / the fused Jacobi sweep of a multigrid smoother at every size
+// (A/B runs); otherwise fused up to the last size at which it was measured through this mirror to be at least as fast:
+// the row "409600 | 2045440" of the mirror's table in profiles/multigrid_probe_reading.md; on the next row, 2946048
+// nonzeros, it loses, so the crossover lies between the two.  Either way the same bits.
+inline bool multigrid_fused(size_type nnz)
+{
+    const char* e = std::getenv("GKOMI_MG_FUSED");
+    if (e != nullptr && (e[0] == '0' || e[0] == '1') && e[1] == 0) return e[0] == '1';
+    return nnz <= 2045440;
+}
 template <typename Solver>
 class factory_base : public LinOpFactory {
 public:
@@ -2689,12 +2722,14 @@ protected:
 // preconditioner slot of the common base and factory: with_solver / with_generated_solver
 // are with_preconditioner / with_generated_preconditioner, get_solver() is get_preconditioner().
 template <typename V = double>
-class Ir : public detail::iterative_solver<Ir<V>> {
+class Ir : public detail::iterative_solver<Ir<V>>, public ApplyWithInitialGuess {
     using base = detail::iterative_solver<Ir<V>>;
 public:
     class Factory : public detail::factory_base<Ir> {
     public:
         Factory& with_relaxation_factor(V r) { relaxation_factor_ = r; return *this; }
+        Factory& with_default_initial_guess(initial_guess_mode g) { guess_ = g; return *this; }
+        initial_guess_mode guess_{initial_guess_mode::provided};
         Factory& with_solver(std::shared_ptr<const LinOpFactory> f) { this->precond_factory_ = std::move(f); return *this; }
         Factory& with_generated_solver(std::shared_ptr<const LinOp> p) { this->precond_ = std::move(p); return *this; }
         V relaxation_factor_{1.0};
@@ -2704,9 +2739,71 @@ public:
     // inner iterations of the last apply, summed over its inner solves: known when it ran as the native
     // mixed-precision driver (-1 otherwise)
     int64_t get_last_inner_iteration_count() const noexcept { return last_inner_iters_; }
+    // ir.hpp:105-109
+    bool apply_uses_initial_guess() const override { return this->get_default_initial_guess() == initial_guess_mode::provided; }
+    V get_relaxation_factor() const noexcept { return relaxation_factor_; }
+    // Ir::apply_with_initial_guess (core/solver/ir.cpp:170-183).  Ir<double> over a generated scalar Jacobi with an
+    // Iteration-only criterion on a Csr<double, int32> and one unit-stride column -- the smoother build_smoother makes --
+    // runs as gkomi_multigrid_jacobi_sweeps_f64_i32 where detail::multigrid_fused says so, else as copy + advanced SpMV
+    // + scalar_apply: the same bits; both run on buffers this solver keeps and add no synchronisation.  Anything else:
+    // the guess is prepared and the plain apply runs.
+    void apply_with_initial_guess(const LinOp* b, LinOp* x, initial_guess_mode guess) const override
+    {
+        if (jacobi_sweeps_as(V{}, b, x, guess)) return;
+        prepare_initial_guess(b, x, guess);
+        this->apply_impl(b, x);
+    }
 protected:
     friend class detail::factory_base<Ir>;
-    Ir(const Factory* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A)), relaxation_factor_(f->relaxation_factor_) {}
+    Ir(const Factory* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A)), relaxation_factor_(f->relaxation_factor_)
+    {
+        this->set_default_initial_guess(f->guess_);
+    }
+    bool jacobi_sweeps_as(float, const LinOp*, LinOp*, initial_guess_mode) const { return false; }
+    bool jacobi_sweeps_as(double, const LinOp* b, LinOp* x, initial_guess_mode guess) const
+    {
+        const auto& st = this->settings_;
+        auto jac = dynamic_cast<const preconditioner::Jacobi<double, int32>*>(this->precond_.get());
+        auto A = dynamic_cast<const matrix::Csr<double, int32>*>(this->A_.get());
+        auto db = dynamic_cast<const matrix::Dense<double>*>(b);
+        auto dx = dynamic_cast<matrix::Dense<double>*>(x);
+        if (!jac || jac->get_max_block_size() != 1 || !A || !db || !dx || st.implicit || st.reduction_factor != 0.0) return false;
+        if (db->get_size()[1] != 1 || db->get_stride() != 1 || dx->get_stride() != 1) return false;
+        ::gko::detail::require_device(this->exec_, "ir::apply");
+        const int64_t n = this->size_[0];
+        const bool zero = guess == initial_guess_mode::zero;
+        if (guess == initial_guess_mode::rhs) dx->copy_from(db);
+        // The sweep buffer, r and the three scalars are sized on the first call and kept (as Multigrid keeps its level
+        // vectors), so a call only queues work on the stream: no allocation, no upload, no synchronisation.
+        if (detail::multigrid_fused(A->get_num_stored_elements())) {
+            const size_type need = gkomi_multigrid_jacobi_sweeps_workspace_bytes(n) + 8;
+            if (sweep_ws_.get_num_elems() < need) sweep_ws_ = array<char>(this->exec_, need);
+            GKOMI_CALL(gkomi_multigrid_jacobi_sweeps_f64_i32(nullptr, n, 1, A->get_num_stored_elements(), A->get_const_row_ptrs(), A->get_const_col_idxs(),
+                                                             A->get_const_values(), jac->get_blocks(), relaxation_factor_, db->get_const_values(),
+                                                             dx->get_values(), st.max_iters, zero ? 1 : 0, sweep_ws_.get_data(), sweep_ws_.get_num_elems()));
+        } else {
+            if (!sweep_r_) {
+                sweep_one_ = initialize<matrix::Dense<double>>({1.0}, this->exec_);
+                sweep_neg_one_ = initialize<matrix::Dense<double>>({-1.0}, this->exec_);
+                sweep_relax_ = initialize<matrix::Dense<double>>({relaxation_factor_}, this->exec_);
+                sweep_r_ = matrix::Dense<double>::create(this->exec_, dim<2>(n, 1));
+            }
+            auto r = sweep_r_.get();
+            if (zero) dx->fill(0.0);
+            for (int64_t it = 0; it < st.max_iters; ++it) {
+                const matrix::Dense<double>* src = db;
+                if (!(it == 0 && zero)) {
+                    r->copy_from(db);
+                    A->apply(sweep_neg_one_.get(), dx, sweep_one_.get(), r);
+                    src = r;
+                }
+                jac->apply(sweep_relax_.get(), src, sweep_one_.get(), dx);
+            }
+        }
+        this->last_iters_ = st.max_iters;
+        this->last_converged_ = false;
+        return true;
+    }
     // Ir<double> over a generated Cg<float> on a Csr<float, int32> (the float copy of the Csr<double, int32> system),
     // both with Iteration + ResidualNorm, no inner preconditioner, one column: mixed-precision iterative refinement as one
     // native driver (gkomi_ir_mixed_solve_f64_i32).  false: not this configuration, the general path runs.
@@ -2756,10 +2853,13 @@ protected:
     }
     V relaxation_factor_;
     mutable int64_t last_inner_iters_{-1};
+    // state of jacobi_sweeps_as, allocated on its first call and reused
+    mutable array<char> sweep_ws_;
+    mutable std::unique_ptr<matrix::Dense<double>> sweep_r_, sweep_one_, sweep_neg_one_, sweep_relax_;
 };
 
 template <typename V = double>
-class Gmres : public detail::iterative_solver<Gmres<V>> {
+class Gmres: public detail::iterative_solver<Gmres<V>> {
     using base = detail::iterative_solver<Gmres<V>>;
 public:
     class Factory : public detail::factory_base<Gmres> {
@@ -4205,6 +4305,435 @@ protected:
 };
 }  // namespace solver
 }  // namespace experimental
+
+// ---- multigrid ------------------------------------------------------------------------------------------------------
+namespace multigrid {
+
+// include/ginkgo/core/multigrid/multigrid_level.hpp:60-95
+class MultigridLevel {
+public:
+    virtual ~MultigridLevel() = default;
+    virtual std::shared_ptr<const LinOp> get_fine_op() const = 0;
+    virtual std::shared_ptr<const LinOp> get_restrict_op() const = 0;
+    virtual std::shared_ptr<const LinOp> get_coarse_op() const = 0;
+    virtual std::shared_ptr<const LinOp> get_prolong_op() const = 0;
+};
+
+// multigrid_level.hpp:109-200: the four operators; as a LinOp the level is prolong(coarse(restrict(b)))
+template <typename V>
+class EnableMultigridLevel : public MultigridLevel {
+public:
+    using value_type = V;
+    std::shared_ptr<const LinOp> get_fine_op() const override { return fine_op_; }
+    std::shared_ptr<const LinOp> get_restrict_op() const override { return restrict_op_; }
+    std::shared_ptr<const LinOp> get_coarse_op() const override { return coarse_op_; }
+    std::shared_ptr<const LinOp> get_prolong_op() const override { return prolong_op_; }
+protected:
+    EnableMultigridLevel() = default;
+    explicit EnableMultigridLevel(std::shared_ptr<const LinOp> fine_op) : fine_op_(std::move(fine_op)) {}
+    void set_multigrid_level(std::shared_ptr<const LinOp> prolong_op, std::shared_ptr<const LinOp> coarse_op, std::shared_ptr<const LinOp> restrict_op)
+    {
+        if (fine_op_->get_size() != dim<2>(prolong_op->get_size()[0], restrict_op->get_size()[1])) {
+            throw DimensionMismatch(__FILE__, __LINE__, "prolong x restrict does not have the fine operator's size");
+        }
+        prolong_op_ = std::move(prolong_op);
+        coarse_op_ = std::move(coarse_op);
+        restrict_op_ = std::move(restrict_op);
+    }
+    void set_fine_op(std::shared_ptr<const LinOp> fine_op) { fine_op_ = std::move(fine_op); }
+    // get_composition()->apply: alpha and beta act on the last factor (core/base/composition.cpp)
+    void apply_composition(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const
+    {
+        auto exec = fine_op_->get_executor();
+        const auto nrhs = b->get_size()[1];
+        auto t1 = matrix::Dense<V>::create(exec, dim<2>(restrict_op_->get_size()[0], nrhs));
+        auto t2 = matrix::Dense<V>::create(exec, dim<2>(coarse_op_->get_size()[0], nrhs));
+        restrict_op_->apply(b, t1.get());
+        coarse_op_->apply(t1.get(), t2.get());
+        if (alpha) {
+            prolong_op_->apply(alpha, t2.get(), beta, x);
+        } else {
+            prolong_op_->apply(t2.get(), x);
+        }
+    }
+private:
+    std::shared_ptr<const LinOp> fine_op_, restrict_op_, coarse_op_, prolong_op_;
+};
+
+// multigrid::FixedCoarsening (include/ginkgo/core/multigrid/fixed_coarsening.hpp, core/multigrid/fixed_coarsening.cpp:69-118):
+// the coarse rows are given; R selects them, P = R^T, A_c = R (A P) through csr::transpose and two csr::spgemm.
+// The system matrix is a Csr, or an Fbcsr, which comes in through Fbcsr::convert_to(Csr*); the mirror's Coo, Ell, Sellp and
+// Hybrid have no conversion to Csr yet and are refused.
+template <typename V = double, typename I = int32>
+class FixedCoarsening : public LinOp, public EnableMultigridLevel<V> {
+public:
+    using csr_type = matrix::Csr<V, I>;
+    class Factory : public LinOpFactory {
+    public:
+        Factory() : LinOpFactory(nullptr) {}
+        Factory& with_coarse_rows(array<I> rows) { coarse_rows_ = std::move(rows); return *this; }
+        Factory& with_skip_sorting(bool skip) { skip_sorting_ = skip; return *this; }
+        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
+        std::unique_ptr<FixedCoarsening> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<FixedCoarsening>(new FixedCoarsening(this, std::move(A))); }
+        std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
+        array<I> coarse_rows_;
+        bool skip_sorting_{false};
+    };
+    static Factory build() { return Factory{}; }
+    std::shared_ptr<const LinOp> get_system_matrix() const { return system_matrix_; }
+protected:
+    FixedCoarsening(const Factory* f, std::shared_ptr<const LinOp> A) : LinOp(f->get_executor(), A->get_size()), EnableMultigridLevel<V>(A), system_matrix_(std::move(A))
+    {
+        if (size_[0] != size_[1]) throw DimensionMismatch(__FILE__, __LINE__, "FixedCoarsening needs a square matrix");
+        if (size_[0] != 0) this->generate(f);
+    }
+    void generate(const Factory* f)
+    {
+        ::gko::detail::require_device(exec_, "FixedCoarsening::generate");
+        auto given = std::dynamic_pointer_cast<const csr_type>(system_matrix_);
+        if (!given) {
+            // fixed_coarsening.cpp:77-87: another format is converted and the Csr becomes the fine operator
+            given = converted_to_csr(system_matrix_.get(), std::integral_constant<bool, std::is_same<V, double>::value && std::is_same<I, int32>::value>{});
+            if (!given) GKO_NOT_SUPPORTED("FixedCoarsening: the system matrix must be a Csr or an Fbcsr");
+            this->set_fine_op(given);
+        }
+        std::shared_ptr<const csr_type> fine = given;
+        if (!f->skip_sorting_ && !given->is_sorted_by_column_index()) {
+            auto sorted = csr_type::create(exec_, given->get_size(), given->get_num_stored_elements(), given->get_strategy());
+            exec_->copy_from(exec_.get(), given->get_size()[0] + 1, given->get_const_row_ptrs(), sorted->get_row_ptrs());
+            exec_->copy_from(exec_.get(), given->get_num_stored_elements(), given->get_const_col_idxs(), sorted->get_col_idxs());
+            exec_->copy_from(exec_.get(), given->get_num_stored_elements(), given->get_const_values(), sorted->get_values());
+            sorted->sort_by_column_index();
+            fine = std::move(sorted);
+            this->set_fine_op(fine);   // fixed_coarsening.cpp:87
+        }
+        const size_type coarse_dim = f->coarse_rows_.get_num_elems();
+        if (coarse_dim == 0) GKO_NOT_SUPPORTED("FixedCoarsening: coarse_rows is empty");
+        const size_type fine_dim = size_[0];
+        auto restrict_op = std::shared_ptr<csr_type>(csr_type::create(exec_, dim<2>(coarse_dim, fine_dim), coarse_dim, fine->get_strategy()));
+        exec_->copy_from(f->coarse_rows_.get_executor().get(), coarse_dim, f->coarse_rows_.get_const_data(), restrict_op->get_col_idxs());
+        std::vector<V> ones(coarse_dim, V{1});
+        std::vector<I> seq(coarse_dim + 1);
+        for (size_type i = 0; i <= coarse_dim; ++i) seq[i] = static_cast<I>(i);
+        exec_->copy_from(exec_->get_master().get(), coarse_dim, ones.data(), restrict_op->get_values());
+        exec_->copy_from(exec_->get_master().get(), coarse_dim + 1, seq.data(), restrict_op->get_row_ptrs());
+        auto prolong_op = std::shared_ptr<csr_type>(restrict_op->transpose());
+        auto coarse = std::shared_ptr<csr_type>(csr_type::create(exec_, dim<2>(coarse_dim, coarse_dim), 0, fine->get_strategy()));
+        auto tmp = csr_type::create(exec_, dim<2>(fine_dim, coarse_dim), 0, fine->get_strategy());
+        fine->apply(prolong_op.get(), tmp.get());
+        restrict_op->apply(tmp.get(), coarse.get());
+        this->set_multigrid_level(prolong_op, coarse, restrict_op);
+    }
+    void apply_impl(const LinOp* b, LinOp* x) const override { this->apply_composition(nullptr, b, nullptr, x); }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override { this->apply_composition(alpha, b, beta, x); }
+private:
+    // the mirror's conversions to a Csr: Fbcsr<double, int32> has one; a null pointer for everything else
+    static std::shared_ptr<const csr_type> converted_to_csr(const LinOp*, std::false_type) { return nullptr; }
+    static std::shared_ptr<const csr_type> converted_to_csr(const LinOp* A, std::true_type)
+    {
+        auto fbcsr = dynamic_cast<const matrix::Fbcsr<double, int32>*>(A);
+        if (!fbcsr) return nullptr;
+        auto result = csr_type::create(A->get_executor());
+        fbcsr->convert_to(result.get());
+        return std::shared_ptr<const csr_type>(std::move(result));
+    }
+    std::shared_ptr<const LinOp> system_matrix_;
+};
+
+}  // namespace multigrid
+
+namespace solver {
+
+// build_smoother (include/ginkgo/core/solver/ir.hpp:314-350): Ir with an Iteration criterion and a relaxation factor
+template <typename V>
+std::shared_ptr<typename Ir<V>::Factory> build_smoother(std::shared_ptr<const LinOpFactory> factory, size_type iteration = 1, V relaxation_factor = 0.9)
+{
+    auto exec = factory->get_executor();
+    return Ir<V>::build().with_solver(factory).with_relaxation_factor(relaxation_factor).with_criteria(stop::Iteration::build().with_max_iters(iteration).on(exec)).on(exec);
+}
+template <typename V>
+std::shared_ptr<typename Ir<V>::Factory> build_smoother(std::shared_ptr<const LinOp> solver, size_type iteration = 1, V relaxation_factor = 0.9)
+{
+    auto exec = solver->get_executor();
+    return Ir<V>::build().with_generated_solver(solver).with_relaxation_factor(relaxation_factor).with_criteria(stop::Iteration::build().with_max_iters(iteration).on(exec)).on(exec);
+}
+
+namespace multigrid {
+enum class cycle { v, f, w };
+enum class mid_smooth_type { both, post_smoother, pre_smoother, standalone };
+namespace detail {
+using factory_list = std::vector<std::shared_ptr<const LinOpFactory>>;
+inline factory_list make_list(const factory_list& v) { return v; }
+inline factory_list make_list(factory_list& v) { return v; }
+inline factory_list make_list(factory_list&& v) { return std::move(v); }
+template <typename... Args>
+factory_list make_list(Args&&... args) { return factory_list{std::shared_ptr<const LinOpFactory>(std::forward<Args>(args))...}; }
+}  // namespace detail
+}  // namespace multigrid
+
+// solver::Multigrid (include/ginkgo/core/solver/multigrid.hpp, core/solver/multigrid.cpp) for double: generate() and
+// validate() as :491-574 and :711-748, the cycle as MultigridState::run_cycle :377-485, the outer loop as :646-705 with the
+// criterion checked before each cycle, the advanced apply on a clone as :615-643.  The recursion runs on the host and only
+// queues work; the one look at the device is the residual norm of a ResidualNorm criterion between two cycles (a smoother
+// or coarsest solver the caller supplies does what it does).  A smoother slot whose product does not use an initial guess
+// is wrapped by build_smoother; Ir over a scalar Jacobi then runs the fused sweep or the three-call sequence on buffers
+// it keeps, without a synchronisation (Ir::apply_with_initial_guess).
+class Multigrid : public detail::iterative_solver<Multigrid>, public ApplyWithInitialGuess {
+    using base = detail::iterative_solver<Multigrid>;
+    using Vec = matrix::Dense<double>;
+public:
+    using selector = std::function<size_type(const size_type, const LinOp*)>;
+    class Factory : public detail::factory_base<Multigrid> {
+    public:
+        template <typename... A> Factory& with_mg_level(A&&... a) { mg_level = multigrid::detail::make_list(std::forward<A>(a)...); return *this; }
+        template <typename... A> Factory& with_pre_smoother(A&&... a) { pre_smoother = multigrid::detail::make_list(std::forward<A>(a)...); return *this; }
+        template <typename... A> Factory& with_mid_smoother(A&&... a) { mid_smoother = multigrid::detail::make_list(std::forward<A>(a)...); return *this; }
+        template <typename... A> Factory& with_post_smoother(A&&... a) { post_smoother = multigrid::detail::make_list(std::forward<A>(a)...); return *this; }
+        template <typename... A> Factory& with_coarsest_solver(A&&... a) { coarsest_solver = multigrid::detail::make_list(std::forward<A>(a)...); return *this; }
+        Factory& with_level_selector(selector s) { level_selector = std::move(s); return *this; }
+        Factory& with_solver_selector(selector s) { solver_selector = std::move(s); return *this; }
+        Factory& with_post_uses_pre(bool v) { post_uses_pre = v; return *this; }
+        Factory& with_mid_case(multigrid::mid_smooth_type v) { mid_case = v; return *this; }
+        Factory& with_max_levels(size_type v) { max_levels = v; return *this; }
+        Factory& with_min_coarse_rows(size_type v) { min_coarse_rows = v; return *this; }
+        Factory& with_cycle(multigrid::cycle v) { cycle = v; return *this; }
+        Factory& with_smoother_relax(double v) { smoother_relax = v; return *this; }
+        Factory& with_smoother_iters(size_type v) { smoother_iters = v; return *this; }
+        Factory& with_default_initial_guess(initial_guess_mode v) { default_initial_guess = v; return *this; }
+        multigrid::detail::factory_list mg_level, pre_smoother, mid_smoother, post_smoother, coarsest_solver;
+        selector level_selector, solver_selector;
+        bool post_uses_pre{true};
+        multigrid::mid_smooth_type mid_case{multigrid::mid_smooth_type::standalone};
+        size_type max_levels{10}, min_coarse_rows{64};
+        multigrid::cycle cycle{multigrid::cycle::v};
+        double smoother_relax{0.9};
+        size_type smoother_iters{1};
+        initial_guess_mode default_initial_guess{initial_guess_mode::provided};
+    };
+    static Factory build() { return Factory{}; }
+    const Factory& get_parameters() const noexcept { return parameters_; }
+    bool apply_uses_initial_guess() const override { return this->get_default_initial_guess() == initial_guess_mode::provided; }
+    const std::vector<std::shared_ptr<const ::gko::multigrid::MultigridLevel>>& get_mg_level_list() const { return mg_level_list_; }
+    const std::vector<std::shared_ptr<const LinOp>>& get_pre_smoother_list() const { return pre_smoother_list_; }
+    const std::vector<std::shared_ptr<const LinOp>>& get_mid_smoother_list() const { return mid_smoother_list_; }
+    const std::vector<std::shared_ptr<const LinOp>>& get_post_smoother_list() const { return post_smoother_list_; }
+    std::shared_ptr<const LinOp> get_coarsest_solver() const { return coarsest_solver_; }
+    multigrid::cycle get_cycle() const noexcept { return cycle_; }
+    void set_cycle(multigrid::cycle c) { cycle_ = c; }
+    void apply_with_initial_guess(const LinOp* b, LinOp* x, initial_guess_mode guess) const override
+    {
+        this->validate(b, x);
+        prepare_initial_guess(b, x, guess);
+        this->run(matrix::detail_fmt::dense(b), matrix::detail_fmt::dense(x), guess);
+    }
+    void apply_with_initial_guess(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x, initial_guess_mode guess) const
+    {
+        this->validate(b, x);
+        prepare_initial_guess(b, x, guess);
+        auto dx = matrix::detail_fmt::dense(x);
+        auto x_clone = dx->clone();
+        this->run(matrix::detail_fmt::dense(b), x_clone.get(), guess);
+        dx->scale(matrix::detail_fmt::dense(beta));
+        dx->add_scaled(matrix::detail_fmt::dense(alpha), x_clone.get());
+    }
+protected:
+    friend class detail::factory_base<Multigrid>;
+    Multigrid(const Factory* f, std::shared_ptr<const LinOp> A) : base(f, std::move(A)), parameters_(*f), cycle_(f->cycle)
+    {
+        this->validate_parameters();
+        level_selector_ = parameters_.level_selector ? parameters_.level_selector
+                          : parameters_.mg_level.size() == 1 ? selector([](const size_type, const LinOp*) { return size_type{0}; })
+                                                             : selector([](const size_type level, const LinOp*) { return level; });
+        solver_selector_ = parameters_.solver_selector ? parameters_.solver_selector : selector([](const size_type, const LinOp*) { return size_type{0}; });
+        this->set_default_initial_guess(parameters_.default_initial_guess);
+        if (this->size_[0] != 0) this->generate();
+    }
+    static void verify_legal_length(bool checked, size_type len, size_type ref_len)
+    {
+        if (checked && len > 1 && len != ref_len) GKO_NOT_SUPPORTED("Multigrid: a smoother list has 0, 1 or as many entries as mg_level");
+    }
+    void validate_parameters() const
+    {
+        const auto len = parameters_.mg_level.size();
+        if (len == 0) GKO_NOT_SUPPORTED("Multigrid: mg_level is empty");
+        for (const auto& f : parameters_.mg_level) {
+            if (f == nullptr) GKO_NOT_SUPPORTED("Multigrid: an mg_level entry is null");
+        }
+        verify_legal_length(true, parameters_.pre_smoother.size(), len);
+        verify_legal_length(!parameters_.post_uses_pre, parameters_.post_smoother.size(), len);
+        verify_legal_length(parameters_.mid_case == multigrid::mid_smooth_type::standalone, parameters_.mid_smoother.size(), len);
+    }
+    void handle_list(size_type index, std::shared_ptr<const LinOp> matrix, const multigrid::detail::factory_list& list,
+                     std::vector<std::shared_ptr<const LinOp>>& out) const
+    {
+        if (list.empty()) {
+            out.emplace_back(nullptr);
+            return;
+        }
+        const auto at = list.size() == 1 ? size_type{0} : index;
+        if (at >= list.size()) GKO_NOT_SUPPORTED("Multigrid: a selector's index is out of the list's bounds");
+        const auto& item = list[at];
+        if (item == nullptr) {
+            out.emplace_back(nullptr);
+            return;
+        }
+        std::shared_ptr<const LinOp> solver(item->generate_impl(matrix));
+        if (solver->apply_uses_initial_guess()) {
+            out.emplace_back(std::move(solver));
+        } else {
+            out.emplace_back(build_smoother<double>(solver, parameters_.smoother_iters, parameters_.smoother_relax)->generate(matrix));
+        }
+    }
+    void generate()
+    {
+        auto num_rows = this->size_[0];
+        size_type level = 0;
+        std::shared_ptr<const LinOp> matrix = this->A_;
+        while (level < parameters_.max_levels && num_rows > parameters_.min_coarse_rows) {
+            const auto index = level_selector_(level, matrix.get());
+            if (index >= parameters_.mg_level.size()) GKO_NOT_SUPPORTED("Multigrid: a selector's index is out of the list's bounds");
+            std::shared_ptr<const LinOp> product(parameters_.mg_level[index]->generate_impl(matrix));
+            auto mg_level = std::dynamic_pointer_cast<const ::gko::multigrid::MultigridLevel>(product);
+            if (!mg_level) GKO_NOT_SUPPORTED("Multigrid: an mg_level factory must generate a MultigridLevel");
+            if (mg_level->get_coarse_op()->get_size()[0] == num_rows) break;   // does not reduce the dimension
+            handle_list(index, mg_level->get_fine_op(), parameters_.pre_smoother, pre_smoother_list_);
+            if (parameters_.mid_case == multigrid::mid_smooth_type::standalone) {
+                handle_list(index, mg_level->get_fine_op(), parameters_.mid_smoother, mid_smoother_list_);
+            }
+            if (!parameters_.post_uses_pre) handle_list(index, mg_level->get_fine_op(), parameters_.post_smoother, post_smoother_list_);
+            mg_level_list_.emplace_back(mg_level);
+            level_owners_.emplace_back(std::move(product));
+            matrix = mg_level->get_coarse_op();
+            num_rows = matrix->get_size()[0];
+            ++level;
+        }
+        if (parameters_.post_uses_pre) post_smoother_list_ = pre_smoother_list_;
+        if (level == 0) GKO_NOT_SUPPORTED("Multigrid: no level was generated");
+        std::shared_ptr<const LinOpFactory> coarsest;
+        if (!parameters_.coarsest_solver.empty()) {
+            const auto at = solver_selector_(level, matrix.get());
+            if (at >= parameters_.coarsest_solver.size()) GKO_NOT_SUPPORTED("Multigrid: a selector's index is out of the list's bounds");
+            coarsest = parameters_.coarsest_solver[at];
+        }
+        coarsest_solver_ = coarsest ? std::shared_ptr<const LinOp>(coarsest->generate_impl(matrix))
+                                    : std::shared_ptr<const LinOp>(matrix::Identity<double>::create(this->exec_, matrix->get_size()[0]));
+    }
+    // MultigridState::generate: r of every level's rows, g and e of the next level's, once per number of columns
+    void allocate(size_type nrhs) const
+    {
+        if (state_nrhs_ == nrhs) return;
+        r_.clear(), g_.clear(), e_.clear();
+        for (const auto& lvl : mg_level_list_) {
+            r_.emplace_back(Vec::create(this->exec_, dim<2>(lvl->get_fine_op()->get_size()[0], nrhs)));
+            g_.emplace_back(Vec::create(this->exec_, dim<2>(lvl->get_coarse_op()->get_size()[0], nrhs)));
+            e_.emplace_back(Vec::create(this->exec_, dim<2>(lvl->get_coarse_op()->get_size()[0], nrhs)));
+        }
+        one_ = initialize<Vec>({1.0}, this->exec_);
+        neg_one_ = initialize<Vec>({-1.0}, this->exec_);
+        state_nrhs_ = nrhs;
+    }
+    void smooth(const LinOp* smoother, const LinOp* b, LinOp* x, bool x_is_zero, size_type level) const
+    {
+        if (auto with_guess = dynamic_cast<const ApplyWithInitialGuess*>(smoother)) {
+            with_guess->apply_with_initial_guess(b, x, x_is_zero ? initial_guess_mode::zero : with_guess->get_default_initial_guess());
+            return;
+        }
+        // x of the first level is zero already (multigrid.cpp:413-419)
+        if (x_is_zero && level != 0) matrix::detail_fmt::dense(x)->fill(0.0);
+        smoother->apply(b, x);
+    }
+    void run_cycle(multigrid::cycle cycle, size_type level, const LinOp* matrix, const LinOp* b, LinOp* x, bool x_is_zero, bool first, bool end) const
+    {
+        using multigrid::mid_smooth_type;
+        const auto total = mg_level_list_.size();
+        if (level == total) {
+            coarsest_solver_->apply(b, x);
+            return;
+        }
+        const auto& lvl = mg_level_list_[level];
+        const auto mid_case = parameters_.mid_case;
+        const LinOp* pre = pre_smoother_list_[level].get();
+        const LinOp* post = post_smoother_list_[level].get();
+        const LinOp* mid = mid_case == mid_smooth_type::standalone ? mid_smoother_list_[level].get() : nullptr;
+        if ((first || mid_case == mid_smooth_type::both || mid_case == mid_smooth_type::pre_smoother) && pre) smooth(pre, b, x, x_is_zero, level);
+        auto r = r_[level].get(), g = g_[level].get(), e = e_[level].get();
+        r->copy_from(matrix::detail_fmt::dense(b));
+        matrix->apply(neg_one_.get(), x, one_.get(), r);
+        lvl->get_restrict_op()->apply(r, g);
+        if (level + 1 == total) e->fill(0.0);
+        const LinOp* next = level + 1 < total ? mg_level_list_[level + 1]->get_fine_op().get() : lvl->get_coarse_op().get();
+        run_cycle(cycle, level + 1, next, g, e, true, true, cycle == multigrid::cycle::v);
+        if (level + 1 < total) {
+            if (cycle == multigrid::cycle::f) {
+                run_cycle(multigrid::cycle::v, level + 1, next, g, e, false, false, true);
+            } else if (cycle == multigrid::cycle::w) {
+                run_cycle(cycle, level + 1, next, g, e, false, false, true);
+            }
+        }
+        lvl->get_prolong_op()->apply(one_.get(), e, one_.get(), x);
+        if ((end || mid_case == mid_smooth_type::both || mid_case == mid_smooth_type::post_smoother) && post) smooth(post, b, x, false, level);
+        if ((cycle == multigrid::cycle::w || cycle == multigrid::cycle::f) && !end && mid_case == mid_smooth_type::standalone && mid) {
+            smooth(mid, b, x, false, level);
+        }
+    }
+    std::vector<double> host_norm2(const Vec* v) const
+    {
+        auto norm = Vec::create(this->exec_, dim<2>(1, v->get_size()[1]));
+        v->compute_norm2(norm.get());
+        std::vector<double> out(v->get_size()[1]);
+        this->exec_->get_master()->copy_from(this->exec_.get(), out.size(), norm->get_const_values(), out.data());
+        return out;
+    }
+    // apply_dense_impl (:646-705): Iteration and ResidualNorm, both asked before each cycle
+    void run(const Vec* b, Vec* x, initial_guess_mode guess) const
+    {
+        ::gko::detail::require_device(this->exec_, "multigrid::apply");
+        const auto& st = this->settings_;
+        if (st.implicit) GKO_NOT_SUPPORTED("Multigrid: ImplicitResidualNorm");
+        allocate(b->get_size()[1]);
+        std::vector<double> base_norm;
+        int64_t iter = 0;
+        bool converged = false;
+        while (true) {
+            if (iter >= st.max_iters) break;
+            if (st.reduction_factor > 0.0) {
+                auto r = r_[0].get();
+                r->copy_from(b);
+                this->A_->apply(neg_one_.get(), x, one_.get(), r);
+                const auto res = host_norm2(r);
+                if (base_norm.empty()) {
+                    base_norm = st.baseline == stop::mode::rhs_norm ? host_norm2(b) : st.baseline == stop::mode::initial_resnorm ? res : std::vector<double>(res.size(), 1.0);
+                }
+                converged = true;
+                for (size_type j = 0; j < res.size(); ++j) converged = converged && res[j] <= st.reduction_factor * base_norm[j];
+                if (converged) break;
+            }
+            run_cycle(cycle_, 0, this->A_.get(), b, x, iter == 0 && guess == initial_guess_mode::zero, true, true);
+            ++iter;
+        }
+        this->last_iters_ = iter;
+        this->last_converged_ = converged;
+    }
+    using base::apply_impl;
+    void apply_impl(const LinOp* b, LinOp* x) const override { this->apply_with_initial_guess(b, x, this->get_default_initial_guess()); }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override
+    {
+        this->apply_with_initial_guess(alpha, b, beta, x, this->get_default_initial_guess());
+    }
+private:
+    Factory parameters_;
+    multigrid::cycle cycle_;
+    selector level_selector_, solver_selector_;
+    std::vector<std::shared_ptr<const ::gko::multigrid::MultigridLevel>> mg_level_list_;
+    std::vector<std::shared_ptr<const LinOp>> level_owners_;
+    std::vector<std::shared_ptr<const LinOp>> pre_smoother_list_, mid_smoother_list_, post_smoother_list_;
+    std::shared_ptr<const LinOp> coarsest_solver_;
+    mutable std::vector<std::unique_ptr<Vec>> r_, g_, e_;
+    mutable std::unique_ptr<Vec> one_, neg_one_;
+    mutable size_type state_nrhs_{0};
+};
+
+}  // namespace solver
 
 }  // namespace gko
 
