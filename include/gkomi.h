@@ -2559,6 +2559,111 @@ int gkomi_multigrid_jacobi_sweeps_f64_i32(gkomi_stream_t s, int64_t n, int64_t n
     double* x, int64_t sweeps, int zero_guess, void* workspace,
     size_t workspace_bytes);
 
+/* ---- multigrid::Pgm (core/multigrid/pgm.cpp, core/multigrid/pgm_kernels.hpp) ---- */
+/* <double, int32>.  The reference executor walks the rows in order; on a weight
+ * matrix with a symmetric pattern (W = 0.5 |A| + 0.5 |A|^T, what Pgm::generate
+ * builds) these entry points give the same integers from launches in which no
+ * lane reads what another writes -- DESIGN.md 4.27 has the argument,
+ * tests/test_pgm_reference.py checks it.  On a weight matrix whose pattern is not
+ * symmetric find_strongest_neighbor and assign_to_exist_agg are not pinned.
+ * Every entry point returns GKOMI_EINVAL before any HIP call for a negative
+ * size, a null pointer with a positive size, a missing or short workspace and
+ * outputs that overlap inputs, the workspace or each other, as far as the
+ * arguments give the lengths (map_row's row_idxs has fine_row_ptrs[n] entries
+ * and map_col's agg as many as there are fine rows, which the host is not
+ * told: there an output that starts inside the input is refused); a size of 0
+ * returns 0.  "Blocks" = the call synchronises the stream to hand a count to the host. */
+/* Csr::compute_absolute (core/matrix/csr.cpp, through
+ * reference/components/absolute_array_kernels.cpp:54-62): the pattern is the
+ * caller's, abs_vals[i] = |vals[i]| */
+int gkomi_csr_compute_absolute_f64_i32(gkomi_stream_t s, int64_t nnz,
+    const double* vals, double* abs_vals);
+/* pgm::match_edge (reference/multigrid/pgm_kernels.cpp:67-86) */
+int gkomi_pgm_match_edge_i32(gkomi_stream_t s, int64_t n,
+    const int32_t* strongest_neighbor, int32_t* agg);
+/* pgm::count_unagg (:91-100); 4 bytes of workspace; blocks */
+int gkomi_pgm_count_unagg_i32(gkomi_stream_t s, int64_t n, const int32_t* agg,
+    int64_t* host_num_unagg, void* workspace, size_t workspace_bytes);
+/* pgm::renumber (:105-124): flags, exclusive sum, gather; blocks */
+size_t gkomi_pgm_renumber_workspace_bytes(int64_t n);
+int gkomi_pgm_renumber_i32(gkomi_stream_t s, int64_t n, int32_t* agg,
+    int64_t* host_num_agg, void* workspace, size_t workspace_bytes);
+/* pgm::sort_agg (:129-135): the pairs (row_idxs[i], col_idxs[i]) ascending, in
+ * place, and pgm::sort_row_major (:299-308): (row_idxs, col_idxs, vals) by
+ * (row, col), stable, in place.  Both through the stable radix sort on the key
+ * row << 32 | col; workspace gkomi_pgm_sort_workspace_bytes(num) for either. */
+size_t gkomi_pgm_sort_workspace_bytes(int64_t num);
+int gkomi_pgm_sort_agg_i32(gkomi_stream_t s, int64_t num, int32_t* row_idxs,
+    int32_t* col_idxs, void* workspace, size_t workspace_bytes);
+int gkomi_pgm_sort_row_major_f64_i32(gkomi_stream_t s, int64_t nnz,
+    int32_t* row_idxs, int32_t* col_idxs, double* vals, void* workspace,
+    size_t workspace_bytes);
+/* pgm::map_row (:140-151) and pgm::map_col (:156-164) */
+int gkomi_pgm_map_row_i32(gkomi_stream_t s, int64_t num_fine_row,
+    const int32_t* fine_row_ptrs, const int32_t* agg, int32_t* row_idxs);
+int gkomi_pgm_map_col_i32(gkomi_stream_t s, int64_t nnz,
+    const int32_t* fine_col_idxs, const int32_t* agg, int32_t* col_idxs);
+/* pgm::count_unrepeated_nnz (:169-186) on sorted pairs: run heads and their
+ * exclusive sum; blocks.  pgm::compute_coarse_coo (:313-345): one lane per run
+ * adds its values left to right, the reference's order and bits; coarse_nnz must
+ * be the number of runs (GKOMI_EINVAL otherwise, nothing written); blocks.
+ * Workspace for either: gkomi_pgm_coarse_coo_workspace_bytes(nnz). */
+size_t gkomi_pgm_coarse_coo_workspace_bytes(int64_t nnz);
+int gkomi_pgm_count_unrepeated_nnz_i32(gkomi_stream_t s, int64_t nnz,
+    const int32_t* row_idxs, const int32_t* col_idxs, int64_t* host_coarse_nnz,
+    void* workspace, size_t workspace_bytes);
+int gkomi_pgm_compute_coarse_coo_f64_i32(gkomi_stream_t s, int64_t fine_nnz,
+    const int32_t* row_idxs, const int32_t* col_idxs, const double* vals,
+    int64_t coarse_nnz, int32_t* coarse_row_idxs, int32_t* coarse_col_idxs,
+    double* coarse_vals, void* workspace, size_t workspace_bytes);
+/* pgm::find_strongest_neighbor (:192-241): a sub-wave of 4, 8, 16 or 64 lanes
+ * per row by the mean row length, each weight the one division
+ * vals[idx] / max(|diag[row]|, |diag[col]|), the greatest (weight, col) over
+ * unaggregated and over aggregated neighbours.  The first 4 bytes of the
+ * workspace are a device counter the number of absorbed rows is ADDED to (the
+ * caller zeroes it); workspace_bytes >= 4. */
+int gkomi_pgm_find_strongest_neighbor_f64_i32(gkomi_stream_t s, int64_t n,
+    int64_t nnz, const int32_t* w_row_ptrs, const int32_t* w_col_idxs,
+    const double* w_vals, const double* diag, int32_t* agg,
+    int32_t* strongest_neighbor, void* workspace, size_t workspace_bytes);
+/* pgm::assign_to_exist_agg (:247-293).  intermediate_agg != NULL: the
+ * deterministic form, every choice from the snapshot agg, written through
+ * intermediate_agg (n entries; it need not be initialised) and copied to agg.
+ * NULL: the sequential form, in which a row sees the unaggregated rows below it
+ * as assigned; computed as the static choice of every row and
+ * ceil(log2 n) rounds of pointer jumping, the count fixed before the first
+ * launch.  Workspace gkomi_pgm_assign_workspace_bytes(n). */
+size_t gkomi_pgm_assign_workspace_bytes(int64_t n);
+int gkomi_pgm_assign_to_exist_agg_f64_i32(gkomi_stream_t s, int64_t n,
+    int64_t nnz, const int32_t* w_row_ptrs, const int32_t* w_col_idxs,
+    const double* w_vals, const double* diag, int32_t* agg,
+    int32_t* intermediate_agg, void* workspace, size_t workspace_bytes);
+/* Pgm::generate (core/multigrid/pgm.cpp:147-236) on the device: the sorted fine
+ * operator unless skip_sorting (fine_col_idxs / fine_vals[nnz], outputs; not
+ * touched with skip_sorting), W and its diagonal, up to max_iterations rounds of
+ * find_strongest_neighbor + match_edge with the host's three-way check after each
+ * (one 4-byte read), assign_to_exist_agg for what is left, renumber, the
+ * restriction's sparsity (restrict_row_ptrs[n + 1], of which num_agg + 1 are
+ * written; restrict_col_idxs[n]) and the coarse matrix A_c = sum of the entries of
+ * the fine operator with equal (agg[row], agg[col]), stably sorted and added left
+ * to right -- the reference's bits.  agg[n] is the prolongation's row gatherer.
+ * Two calls with the same workspace (gkomi_pgm_generate_workspace_bytes(n, nnz),
+ * left alone in between): coarse_col_idxs == coarse_vals == NULL does all the work
+ * and writes agg, the restriction, coarse_row_ptrs[n + 1] (num_agg + 1 written),
+ * *host_num_agg, *host_coarse_nnz and host_info[4] = {rounds run, rows left for
+ * assign_to_exist_agg, exit (0 nothing left, 1 no new match, 2 ratio,
+ * 3 max_iterations), pointer-jumping rounds} (may be NULL); blocks.  With
+ * coarse_col_idxs / coarse_vals[*host_coarse_nnz] the entries are copied out. */
+size_t gkomi_pgm_generate_workspace_bytes(int64_t n, int64_t nnz);
+int gkomi_pgm_generate_f64_i32(gkomi_stream_t s, int64_t n, int64_t nnz,
+    const int32_t* row_ptrs, const int32_t* col_idxs, const double* vals,
+    int64_t max_iterations, double max_unassigned_ratio, int deterministic,
+    int skip_sorting, int32_t* fine_col_idxs, double* fine_vals, int32_t* agg,
+    int32_t* restrict_row_ptrs, int32_t* restrict_col_idxs,
+    int32_t* coarse_row_ptrs, int32_t* coarse_col_idxs, double* coarse_vals,
+    int64_t* host_num_agg, int64_t* host_coarse_nnz, int64_t* host_info,
+    void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

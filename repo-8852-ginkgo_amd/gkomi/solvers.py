@@ -1800,3 +1800,57 @@ class OrderedCg:
 def fixed_coarsening_factory(gk, select, skip_sorting=False):
     """an mg_level entry: select(matrix) -> the coarse rows of that matrix"""
     return lambda m: fixed_coarsening(gk, m.nrows, m.row_ptrs, m.col_idxs, m.vals, select(m), skip_sorting, m.strategy)
+
+
+PGM_EXITS = ("nothing left", "no new match", "ratio", "max_iterations")
+
+
+def pgm(gk, n, row_ptrs, col_idxs, vals, max_iterations=15, max_unassigned_ratio=0.05, deterministic=False,
+        skip_sorting=False, strategy=0):
+    """multigrid::Pgm::generate (core/multigrid/pgm.cpp:147-236) through gkomi_pgm_generate_f64_i32, all of it on the
+    device: the fine matrix sorted unless skipped (with skip_sorting the caller's arrays are the fine operator), the
+    aggregates, the restriction and the coarse matrix with the reference executor's integers and bits.  The restriction
+    (num_agg x n, sorted rows) and the prolongation (one entry per row at column agg[i]) are unit-valued Csr matrices:
+    their applies add what SparsityCsr's and RowGatherer's add, in the same order.  -> MultigridLevel with .agg (int32,
+    n), .num_agg and .info = dict(iterations, left, exit, jump_rounds)"""
+    n, max_iterations = int(n), int(max_iterations)
+    if n <= 0:
+        raise ValueError("Pgm needs a matrix with at least one row")
+    if max_iterations < 0 or not 0.0 <= float(max_unassigned_ratio) <= 1.0:
+        raise ValueError("max_iterations must not be negative and max_unassigned_ratio must lie in [0, 1]")
+    if row_ptrs.numel() != n + 1 or col_idxs.numel() != vals.numel():
+        raise ValueError("row_ptrs needs n + 1 entries, col_idxs as many as vals")
+    dv = vals.device
+    s = torch.cuda.current_stream().cuda_stream
+    nnz = int(vals.numel())
+    i32 = lambda k: torch.zeros(k, dtype=torch.int32, device=dv)
+    if skip_sorting:
+        fci, fv = col_idxs, vals
+    else:
+        fci, fv = _empty_csr(n, nnz, dv)
+    agg, rrp, rci, crp = i32(n), i32(n + 1), i32(n), i32(n + 1)
+    nb = gk.pgm_generate_workspace_bytes(n, nnz)
+    ws = _bytes(nb, dv)
+    num_agg, cnnz, info = ctypes.c_int64(0), ctypes.c_int64(0), (ctypes.c_int64 * 4)()
+
+    def call(cc, cv):
+        gk.pgm_generate_f64_i32(s, n, nnz, row_ptrs, col_idxs, vals, max_iterations, float(max_unassigned_ratio),
+                                int(bool(deterministic)), int(bool(skip_sorting)), None if skip_sorting else fci,
+                                None if skip_sorting else fv, agg, rrp, rci, crp, cc, cv, ctypes.addressof(num_agg),
+                                ctypes.addressof(cnnz), ctypes.addressof(info), ws, nb)
+    cc, cv = _count_then_fill(call, [cnnz], dv)
+    m = int(num_agg.value)
+    fine = Csr(gk, n, n, row_ptrs, fci, fv, strategy)
+    restrict = Csr(gk, m, n, rrp[:m + 1].clone(), rci, torch.ones(n, dtype=torch.float64, device=dv), strategy)
+    prolong = Csr(gk, n, m, torch.arange(n + 1, dtype=torch.int32, device=dv), agg.clone(),
+                  torch.ones(n, dtype=torch.float64, device=dv), strategy)
+    coarse = Csr(gk, m, m, crp[:m + 1].clone(), cc, cv, strategy)
+    lvl = MultigridLevel(fine, restrict, coarse, prolong)
+    lvl.agg, lvl.num_agg = agg, m
+    lvl.info = dict(iterations=int(info[0]), left=int(info[1]), exit=PGM_EXITS[int(info[2])], jump_rounds=int(info[3]))
+    return lvl
+
+
+def pgm_factory(gk, **parameters):
+    """an mg_level entry: Pgm with these parameters on whatever matrix the hierarchy hands it"""
+    return lambda m: pgm(gk, m.nrows, m.row_ptrs, m.col_idxs, m.vals, strategy=m.strategy, **parameters)

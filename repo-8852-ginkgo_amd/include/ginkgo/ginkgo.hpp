@@ -1153,6 +1153,19 @@ public:
         t->max_row_nnz_ = -1;
         return t;
     }
+    // Csr::compute_absolute (core/matrix/csr.cpp): the same pattern and strategy, |values|
+    std::unique_ptr<Csr> compute_absolute() const
+    {
+        static_assert(std::is_same<V, double>::value && std::is_same<I, int32>::value, "compute_absolute: <double, int32> only");
+        detail::require_device(exec_, "csr::compute_absolute");
+        const size_type nnz = get_num_stored_elements();
+        auto result = Csr::create(exec_, size_, nnz, strategy_);
+        exec_->copy(size_[0] + 1, get_const_row_ptrs(), result->get_row_ptrs());
+        exec_->copy(nnz, get_const_col_idxs(), result->get_col_idxs());
+        GKOMI_CALL(gkomi_csr_compute_absolute_f64_i32(nullptr, static_cast<int64_t>(nnz), get_const_values(), result->get_values()));
+        result->max_row_nnz_ = max_row_nnz_;
+        return result;
+    }
     // csr::sort_by_column_index / is_sorted_by_column_index (core/matrix/csr.cpp)
     void sort_by_column_index()
     {
@@ -4438,6 +4451,103 @@ private:
         return std::shared_ptr<const csr_type>(std::move(result));
     }
     std::shared_ptr<const LinOp> system_matrix_;
+};
+
+// multigrid::Pgm (include/ginkgo/core/multigrid/pgm.hpp, core/multigrid/pgm.cpp:147-236) through gkomi_pgm_generate_f64_i32:
+// the aggregates, the restriction and the coarse matrix of the reference executor, all computed on the device.  The
+// restriction (num_agg x n, sorted rows) and the prolongation (one entry per row at column agg[i]) are unit-valued Csr
+// matrices, whose applies add what SparsityCsr's and RowGatherer's add in the same order; classes of their own are a
+// follow-up.  The system matrix is a Csr, or an Fbcsr through its conversion.  When the matrix is sorted
+// or converted the new Csr becomes the fine operator (pgm.cpp:163-169); with skip_sorting a Csr stays the caller's object.
+template <typename V = double, typename I = int32>
+class Pgm : public LinOp, public EnableMultigridLevel<V> {
+public:
+    using value_type = V;
+    using index_type = I;
+    using csr_type = matrix::Csr<V, I>;
+    class Factory : public LinOpFactory {
+    public:
+        Factory() : LinOpFactory(nullptr) {}
+        Factory& with_max_iterations(unsigned v) { max_iterations_ = v; return *this; }
+        Factory& with_max_unassigned_ratio(double v) { max_unassigned_ratio_ = v; return *this; }
+        Factory& with_deterministic(bool v) { deterministic_ = v; return *this; }
+        Factory& with_skip_sorting(bool v) { skip_sorting_ = v; return *this; }
+        std::shared_ptr<Factory> on(std::shared_ptr<const Executor> exec) const { auto f = std::make_shared<Factory>(*this); f->exec_ = std::move(exec); return f; }
+        std::unique_ptr<Pgm> generate(std::shared_ptr<const LinOp> A) const { return std::unique_ptr<Pgm>(new Pgm(this, std::move(A))); }
+        std::unique_ptr<LinOp> generate_impl(std::shared_ptr<const LinOp> A) const override { return generate(std::move(A)); }
+        unsigned max_iterations_{15};
+        double max_unassigned_ratio_{0.05};
+        bool deterministic_{false};
+        bool skip_sorting_{false};
+    };
+    static Factory build() { return Factory{}; }
+    std::shared_ptr<const LinOp> get_system_matrix() const { return system_matrix_; }
+    I* get_agg() noexcept { return agg_.get_data(); }
+    const I* get_const_agg() const noexcept { return agg_.get_const_data(); }
+protected:
+    Pgm(const Factory* f, std::shared_ptr<const LinOp> A)
+        : LinOp(f->get_executor(), A->get_size()), EnableMultigridLevel<V>(A), system_matrix_(std::move(A)), agg_(f->get_executor(), system_matrix_->get_size()[0])
+    {
+        if (size_[0] != size_[1]) throw DimensionMismatch(__FILE__, __LINE__, "Pgm needs a square matrix");
+        if (size_[0] != 0) this->generate(f, std::integral_constant<bool, std::is_same<V, double>::value && std::is_same<I, int32>::value>{});
+    }
+    void generate(const Factory*, std::false_type) { GKO_NOT_SUPPORTED("multigrid::Pgm: <double, int32> only"); }
+    void generate(const Factory* f, std::true_type)
+    {
+        ::gko::detail::require_device(exec_, "Pgm::generate");
+        auto given = std::dynamic_pointer_cast<const csr_type>(system_matrix_);
+        if (!given) {
+            auto fbcsr = dynamic_cast<const matrix::Fbcsr<double, int32>*>(system_matrix_.get());
+            if (!fbcsr) GKO_NOT_SUPPORTED("Pgm: the system matrix must be a Csr or an Fbcsr");
+            auto converted = csr_type::create(exec_);
+            fbcsr->convert_to(converted.get());
+            given = std::shared_ptr<const csr_type>(std::move(converted));
+            this->set_fine_op(given);
+        }
+        const size_type n = size_[0], nnz = given->get_num_stored_elements();
+        std::shared_ptr<csr_type> sorted;
+        if (!f->skip_sorting_) {
+            // the driver writes the sorted columns and values; the row pointers are the matrix's
+            sorted = csr_type::create(exec_, given->get_size(), nnz, given->get_strategy());
+            exec_->copy(n + 1, given->get_const_row_ptrs(), sorted->get_row_ptrs());
+        }
+        array<I> r_row_ptrs(exec_, n + 1), r_col_idxs(exec_, n), c_row_ptrs(exec_, n + 1);
+        array<char> ws(exec_, gkomi_pgm_generate_workspace_bytes(n, nnz) + 8);
+        int64_t num_agg = 0, coarse_nnz = 0;
+        auto call = [&](I* cc, V* cv) {
+            return gkomi_pgm_generate_f64_i32(nullptr, n, nnz, given->get_const_row_ptrs(), given->get_const_col_idxs(), given->get_const_values(),
+                                              f->max_iterations_, f->max_unassigned_ratio_, f->deterministic_, f->skip_sorting_,
+                                              sorted ? sorted->get_col_idxs() : nullptr, sorted ? sorted->get_values() : nullptr, agg_.get_data(),
+                                              r_row_ptrs.get_data(), r_col_idxs.get_data(), c_row_ptrs.get_data(), cc, cv, &num_agg, &coarse_nnz, nullptr,
+                                              ws.get_data(), ws.get_num_elems());
+        };
+        GKOMI_CALL(call(nullptr, nullptr));
+        const size_type coarse_dim = static_cast<size_type>(num_agg);
+        auto strategy = given->get_strategy();
+        auto coarse = std::shared_ptr<csr_type>(csr_type::create(exec_, dim<2>(coarse_dim, coarse_dim), static_cast<size_type>(coarse_nnz), strategy));
+        exec_->copy(coarse_dim + 1, c_row_ptrs.get_const_data(), coarse->get_row_ptrs());
+        if (coarse_nnz > 0) GKOMI_CALL(call(coarse->get_col_idxs(), coarse->get_values()));
+        auto restrict_op = std::shared_ptr<csr_type>(csr_type::create(exec_, dim<2>(coarse_dim, n), n, strategy));
+        auto prolong_op = std::shared_ptr<csr_type>(csr_type::create(exec_, dim<2>(n, coarse_dim), n, strategy));
+        std::vector<V> ones(n, V{1});
+        std::vector<I> seq(n + 1);
+        for (size_type i = 0; i <= n; ++i) seq[i] = static_cast<I>(i);
+        auto host = exec_->get_master();
+        exec_->copy(coarse_dim + 1, r_row_ptrs.get_const_data(), restrict_op->get_row_ptrs());
+        exec_->copy(n, r_col_idxs.get_const_data(), restrict_op->get_col_idxs());
+        exec_->copy_from(host.get(), n, ones.data(), restrict_op->get_values());
+        exec_->copy_from(host.get(), n + 1, seq.data(), prolong_op->get_row_ptrs());
+        exec_->copy(n, agg_.get_const_data(), prolong_op->get_col_idxs());
+        exec_->copy_from(host.get(), n, ones.data(), prolong_op->get_values());
+        GKOMI_CALL(gkomi_synchronize(nullptr));  // the workspace goes away with this scope
+        if (sorted) this->set_fine_op(sorted);   // pgm.cpp:168
+        this->set_multigrid_level(prolong_op, coarse, restrict_op);
+    }
+    void apply_impl(const LinOp* b, LinOp* x) const override { this->apply_composition(nullptr, b, nullptr, x); }
+    void apply_impl(const LinOp* alpha, const LinOp* b, const LinOp* beta, LinOp* x) const override { this->apply_composition(alpha, b, beta, x); }
+private:
+    std::shared_ptr<const LinOp> system_matrix_;
+    array<I> agg_;
 };
 
 }  // namespace multigrid
