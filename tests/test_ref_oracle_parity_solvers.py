@@ -8,6 +8,7 @@ import math
 import numpy as np
 import pytest
 
+import exact_systems as exs
 import idr_util
 import ilu_exact_util as xu
 import ilu_util
@@ -533,6 +534,125 @@ def cg_f32_case(sysname, x0_kind):
 
 for _x0 in ("zero", "guess"):
     REG.case(f"solve-cg-f32-poisson40-{_x0}")(cg_f32_case("poisson40", _x0))
+
+
+# ---- the exact systems of tests/exact_systems.py: breakdown guards, zero right-hand sides, one-step convergence
+
+def exact_case(solver, case):
+    """One kept (solver, case) pair at the small size: iterations exactly, x and the residual norm the oracle reports
+    as bits -- the all-NaN x of Gmres on a zero right-hand side included."""
+    c = exs.CASES[case]
+    n = c.sizes()[0]
+
+    def build(oracle, batch):
+        (_, rp, ci, v), b, x0 = c.build(n)
+        f32, jacobi = solver == "cg_f32", solver == "cg_jacobi"
+        dt = np.float32 if f32 else np.float64
+        arrays, params = ref_exec.csr_arrays(n, n, rp, ci, v.astype(dt), vdt=dt)
+        arrays.update(b=b.astype(dt), x=x0.astype(dt))
+        params.update(b_rows=n, b_cols=1, x_rows=n, x_cols=1, solver=SOLVERS["cg" if f32 or jacobi else solver],
+                      max_iters=c.max_iters, reduction=exs.REDUCTION, baseline=exs.BASELINES[c.baseline])
+        if f32:
+            params.update(vt=1)
+        if jacobi:
+            params.update(precond=1, max_block_size=1)
+        if solver == "gmres":
+            params.update(krylov_dim=c.krylov_dim)
+        if solver == "ir":
+            params.update(relaxation_factor=exs.IR_RELAXATION)
+        idx = batch.add("solve", arrays, **params)
+
+        def check(results):
+            r = ok(results[idx])
+            it, x, res = exs.run(oracle, solver, case, n)
+            what = f"{solver} on {case}"
+            assert int(r["iterations"][0]) == it, f"{what}: {it} iterations, the reference {int(r['iterations'][0])}"
+            # the oracle reports no `converged`: on every one of these cases the limit is what ends an unconverged solve
+            assert bool(r["converged"][0]) == (it < c.max_iters), what
+            assert_bits(x, r["x"], what + " x")
+            # the oracle's norm where it reports one, else the exact known |b - A x| (exs.run); the reference's Ir logs none
+            if res is not None and solver != "ir":
+                assert_bits(np.array([res], r["resnorm"].dtype), r["resnorm"], what + " final residual norm")
+        return check
+    return build
+
+
+def exact_columns_case(solver, names):
+    """Three different columns in one solve (exs.column_sets): iterations, x and, for Gmres, the residual norms of
+    exs.solve_columns against the reference executor.  For Cg, Fcg, Bicgstab, Cgs, Bicg and Ir every column is its own
+    single-column solve and the count is the largest.  Not for Gmres: there the column that stopped first receives its
+    correction again at every later restart (exs.gmres_columns says why); the reference's result is the expectation."""
+    n = exs.SMALL
+
+    def build(oracle, batch):
+        built = [exs.CASES[c].build(n) for c in names]
+        _, rp, ci, v = built[0][0]
+        b = np.stack([t[1] for t in built], 1)
+        x0 = np.stack([t[2] for t in built], 1)
+        arrays, params = ref_exec.csr_arrays(n, n, rp, ci, v)
+        arrays.update(b=b.reshape(-1).copy(), x=x0.reshape(-1).copy())
+        params.update(b_rows=n, b_cols=3, x_rows=n, x_cols=3, solver=SOLVERS[solver], max_iters=exs.MAX_ITERS,
+                      reduction=exs.REDUCTION)
+        if solver == "gmres":
+            params.update(krylov_dim=5)
+        if solver == "ir":
+            params.update(relaxation_factor=exs.IR_RELAXATION)
+        idx = batch.add("solve", arrays, **params)
+
+        def check(results):
+            r = ok(results[idx])
+            it, x, res = exs.solve_columns(oracle, solver, names, n)
+            what = f"{solver} on the columns {names}"
+            assert int(r["iterations"][0]) == it, what
+            assert_bits(x.reshape(-1), r["x"], what + " x")
+            if res is not None:
+                assert_bits(res, r["resnorm"].reshape(-1), what + " residual norms")
+        return check
+    return build
+
+
+def exact_idr_case(case):
+    """Idr on a case where every vector stays zero (b = 0, or an exact guess): the literal restatement with the
+    reference's deterministic subspace.  On b = 0 the reference divides 0 by m_kk = 0 and returns NaN."""
+    c = exs.CASES[case]
+    n = c.sizes()[0]
+
+    def build(oracle, batch):
+        (_, rp, ci, v), b, x0 = c.build(n)
+        arrays, params = ref_exec.csr_arrays(n, n, rp, ci, v)
+        arrays.update(b=b.copy(), x=x0.copy())
+        idx = batch.add("solve", arrays, b_rows=n, b_cols=1, x_rows=n, x_cols=1, solver=SOLVERS["idr"],
+                        max_iters=c.max_iters, reduction=exs.REDUCTION, subspace_dim=exs.IDR_SUBSPACE_DIM,
+                        kappa=exs.IDR_KAPPA, deterministic=1, **params)
+
+        def check(results):
+            r = ok(results[idx])
+            with np.errstate(invalid="ignore"):
+                res = idr_util.solve(idr_util.csr_apply(oracle, n, rp, ci, v), b.reshape(n, 1).copy(),
+                                     deterministic_subspace(exs.IDR_SUBSPACE_DIM, n), subspace_dim=exs.IDR_SUBSPACE_DIM,
+                                     kappa=exs.IDR_KAPPA, max_iters=c.max_iters, reduction=exs.REDUCTION,
+                                     x=x0.reshape(n, 1).copy(), literal=True)
+            assert int(r["iterations"][0]) == res["iterations"], case
+            assert_bits(res["x"][:, 0].copy(), r["x"], f"idr on {case} x")
+            # what the library's drivers do instead (literal=False, the subspace the GPU tests use) gives the same
+            it, x, _ = exs.run(oracle, "idr", case, n)
+            assert it == res["iterations"]
+            assert_bits(x, r["x"], f"idr on {case}: the drivers' variant")
+        return check
+    return build
+
+
+def _register_exact():
+    for case in ("Z0", "E"):
+        REG.case(f"exact-idr-{case}")(exact_idr_case(case))
+    for solver, case in exs.pairs(exs.ALL7 + ("cg_f32", "cg_jacobi")):
+        REG.case(f"exact-{solver}-{case}")(exact_case(solver, case))
+    for solver in exs.ALL7:
+        for names in exs.column_sets(solver):
+            REG.case(f"exact-{solver}-columns-{'-'.join(names)}")(exact_columns_case(solver, names))
+
+
+_register_exact()
 
 
 @pytest.mark.parametrize("name", REG.names())

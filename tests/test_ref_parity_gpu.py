@@ -13,9 +13,13 @@ what the driver gives now).  With neither driver nor a recording for these
 inputs the module fails; it never skips.
 
 Shapes are the smallest that cross the kernels' boundaries; the solvers are
-not repeated (their reductions are re-ordered on the device by design, and
-test_ref_oracle_parity_solvers.py proves the restatements they are bounded
-against equal to the reference on the same systems)."""
+not repeated here on generic systems (their reductions are re-ordered on the
+device by design, and test_ref_oracle_parity_solvers.py proves the restatements
+they are bounded against equal to the reference on the same systems).  On the
+exact systems of exact_systems.py, where no summation order changes a bit,
+test_whole_solves_exact_gpu.py holds every solve driver to the oracle bit for
+bit, iteration count included, and test_ref_oracle_parity_solvers.py holds the
+oracle to the reference on the same inputs."""
 import ctypes
 import os
 
