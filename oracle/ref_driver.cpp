@@ -3,9 +3,11 @@
 // Runs batches of cases on the reference library's ReferenceExecutor through
 // its public API, so that the tests can compare the C oracle, the Python
 // restatements and the HIP kernels with the reference itself instead of with
-// a restatement of it.  This file is the project's own; it is compiled
-// against the reference's headers by oracle/ref.mk into oracle/_ref/ and the
-// product never links or loads it.
+// a restatement of it.  The verbs that pin a single kernel (par_ilut, par_ict,
+// isai, cb_gmres, multigrid) call gko::kernels::reference::... directly and
+// include that kernel's core/**/*_kernels.hpp for it.  This file is the
+// project's own; it is compiled against the reference's headers by
+// oracle/ref.mk into oracle/_ref/ and the product never links or loads it.
 //
 //   ref_driver IN OUT
 //
@@ -16,6 +18,8 @@
 //        u32 status (0 ok, 1 failed), str message, u32 narrays x (as above)
 // str = u32 length + bytes; dtype 0 f64, 1 f32, 2 i32, 3 i64, 4 u8.  Values
 // travel as raw IEEE bytes both ways (tests/ref_exec.py is the other end).
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -27,6 +31,14 @@
 #include <vector>
 
 #include <ginkgo/ginkgo.hpp>
+
+#include "core/factorization/factorization_kernels.hpp"
+#include "core/factorization/par_ict_kernels.hpp"
+#include "core/factorization/par_ilut_kernels.hpp"
+#include "core/preconditioner/isai_kernels.hpp"
+#include "core/solver/cb_gmres_accessor.hpp"
+#include "core/solver/cb_gmres_kernels.hpp"
+#include "core/solver/multigrid_kernels.hpp"
 
 namespace {
 
@@ -145,6 +157,16 @@ std::unique_ptr<gko::matrix::Dense<V>> scalar(V v)
 // ---- the storage formats, reached from a Csr by the reference's conversions
 
 enum { F_CSR, F_ELL, F_SELLP, F_HYBRID, F_COO, F_FBCSR, F_DENSE };
+// the words of the cases as numbers: WORDS of tests/ref_exec.py has each list in the same order.  (The storage of
+// cb_gmres is the reference's own solver::cb_gmres::storage_precision.)
+enum { BASE_RHS_NORM, BASE_INITIAL_RESNORM, BASE_ABSOLUTE };   // the baseline of a residual-norm criterion
+enum { ISAI_LOWER, ISAI_UPPER, ISAI_GENERAL, ISAI_SPD };
+enum { CYCLE_V, CYCLE_F, CYCLE_W };
+enum { MID_BOTH, MID_POST_SMOOTHER, MID_PRE_SMOOTHER, MID_STANDALONE };
+enum { COARSEST_IDENTITY, COARSEST_DIRECT, COARSEST_CG };
+enum { GUESS_ZERO, GUESS_RHS, GUESS_PROVIDED };
+enum { SMOOTHER_NULL, SMOOTHER_EYE, SMOOTHER_JACOBI };
+enum { LEVEL_HALVE, LEVEL_ALL_ROWS, LEVEL_PGM };
 
 template <typename V, typename I>
 std::unique_ptr<gko::LinOp> to_format(const Case& c, const gko::matrix::Csr<V, I>* csr)
@@ -732,6 +754,674 @@ void v_criterion(Case& c)
     c.put("flags", flags, 2);
 }
 
+// ---- the families pinned through JSON fixtures (tests/golden/*_ref.json): one verb each, `op` selects the sub-case.
+// Their results carry the names the fixtures use: a Csr as <name>row_ptrs, <name>col_idxs, <name>vals.
+
+using csr = gko::matrix::Csr<double, gko::int32>;
+using coo = gko::matrix::Coo<double, gko::int32>;
+using dense = gko::matrix::Dense<double>;
+using factories = std::vector<std::shared_ptr<const gko::LinOpFactory>>;
+
+void out_parts(Case& c, const std::string& name, const gko::LinOp* op)
+{
+    auto m = gko::as<csr>(op);
+    c.put(name + "row_ptrs", m->get_const_row_ptrs(), m->get_size()[0] + 1);
+    c.put(name + "col_idxs", m->get_const_col_idxs(), m->get_num_stored_elements());
+    c.put(name + "vals", m->get_const_values(), m->get_num_stored_elements());
+}
+
+// row-major without the padding of a strided view
+void out_rows(Case& c, const std::string& name, const dense* m)
+{
+    std::vector<double> v;
+    for (size_type i = 0; i < m->get_size()[0]; ++i) {
+        for (size_type j = 0; j < m->get_size()[1]; ++j) v.push_back(m->at(i, j));
+    }
+    c.put(name, v.data(), v.size());
+}
+
+template <typename T>
+void out_counts(Case& c, const std::string& name, const T* p, size_t count)
+{
+    std::vector<gko::int64> v(p, p + count);
+    c.put(name, v.data(), v.size());
+}
+
+struct iteration_logger : gko::log::Logger {
+    mutable gko::int64 last = -1;
+    mutable std::vector<double> tau;
+    void on_iteration_complete(const gko::LinOp*, const size_type& it, const gko::LinOp*, const gko::LinOp*,
+                               const gko::LinOp* t) const override
+    {
+        last = static_cast<gko::int64>(it);
+        if (t != nullptr) {
+            auto d = gko::as<dense>(t);
+            tau.assign(d->get_const_values(), d->get_const_values() + d->get_size()[1]);
+        }
+    }
+    iteration_logger() : gko::log::Logger(gko::log::Logger::iteration_complete_mask) {}
+};
+
+// ParIlut / ParIct ::generate with the parameters iterations, fill_in_limit, approximate_select
+template <typename Factorization>
+std::unique_ptr<Factorization> threshold_factorization(const Case& c, std::shared_ptr<csr> a)
+{
+    return Factorization::build()
+        .with_iterations(static_cast<size_type>(c.pi("iterations")))
+        .with_fill_in_limit(c.p("fill_in_limit"))
+        .with_approximate_select(c.pi("approximate_select") != 0)
+        .on(exec)
+        ->generate(a);
+}
+
+// par_ilut: op 0 ParIlut::generate; op 1 each of the five kernels alone on the intermediate matrices of the first
+// iteration (core/factorization/par_ilut.cpp:257-344) at fill_in_limit 1.2
+void v_par_ilut(Case& c)
+{
+    namespace ilut = gko::kernels::reference::par_ilut_factorization;
+    namespace fact = gko::kernels::reference::factorization;
+    auto a = gko::share(in_csr<double, gko::int32>(c));
+    const auto size = a->get_size();
+    const size_type n = size[0];
+    if (c.pi("op") == 0) {
+        auto f = threshold_factorization<gko::factorization::ParIlut<double, gko::int32>>(c, a);
+        const gko::int32 nnz[2] = {static_cast<gko::int32>(f->get_l_factor()->get_num_stored_elements()),
+                                   static_cast<gko::int32>(f->get_u_factor()->get_num_stored_elements())};
+        c.put("nnz", nnz, 2);
+        out_parts(c, "l.", f->get_l_factor().get());
+        out_parts(c, "u.", f->get_u_factor().get());
+        return;
+    }
+    if (c.pi("op") != 1) throw std::runtime_error("unknown par_ilut op");
+    gko::array<gko::int32> l_rp(exec, n + 1), u_rp(exec, n + 1);
+    fact::initialize_row_ptrs_l_u(exec, a.get(), l_rp.get_data(), u_rp.get_data());
+    const size_t l_nnz = l_rp.get_data()[n], u_nnz = u_rp.get_data()[n];
+    auto l = csr::create(exec, size, gko::array<double>(exec, l_nnz), gko::array<gko::int32>(exec, l_nnz), std::move(l_rp));
+    auto u = csr::create(exec, size, gko::array<double>(exec, u_nnz), gko::array<gko::int32>(exec, u_nnz), std::move(u_rp));
+    fact::initialize_l_u(exec, a.get(), l.get(), u.get());
+    const gko::int32 l_limit = static_cast<gko::int32>(l_nnz * 1.2), u_limit = static_cast<gko::int32>(u_nnz * 1.2);
+    auto lu = csr::create(exec, size);
+    l->apply(u.get(), lu.get());
+    out_parts(c, "lu.", lu.get());
+    auto l_new = csr::create(exec, size), u_new = csr::create(exec, size);
+    ilut::add_candidates(exec, lu.get(), a.get(), l.get(), u.get(), l_new.get(), u_new.get());
+    out_parts(c, "add_candidates.l.", l_new.get());
+    out_parts(c, "add_candidates.u.", u_new.get());
+    auto u_new_csc = gko::as<csr>(u_new->transpose());
+    const coo* no_coo = nullptr;
+    ilut::compute_l_u_factors(exec, a.get(), l_new.get(), no_coo, u_new.get(), no_coo, u_new_csc.get());
+    out_parts(c, "sweep.l.", l_new.get());
+    out_parts(c, "sweep.u.", u_new.get());
+    out_parts(c, "sweep.u_csc.", u_new_csc.get());
+    const gko::int32 ln = static_cast<gko::int32>(l_new->get_num_stored_elements());
+    const gko::int32 un = static_cast<gko::int32>(u_new->get_num_stored_elements());
+    const gko::int32 ranks[2] = {std::max<gko::int32>(0, ln - l_limit - 1), std::max<gko::int32>(0, un - u_limit - 1)};
+    c.put("ranks", ranks, 2);
+    gko::array<double> tmp(exec), tmp2(exec);
+    double select[2] = {}, approx[2] = {};
+    ilut::threshold_select(exec, l_new.get(), ranks[0], tmp, tmp2, select[0]);
+    ilut::threshold_select(exec, u_new_csc.get(), ranks[1], tmp, tmp2, select[1]);
+    c.put("select", select, 2);
+    coo* null_coo = nullptr;
+    auto l_f = csr::create(exec, size), u_f = csr::create(exec, size);
+    auto l_coo = coo::create(exec, size);
+    ilut::threshold_filter(exec, l_new.get(), select[0], l_f.get(), l_coo.get(), true);
+    ilut::threshold_filter(exec, u_new.get(), select[1], u_f.get(), null_coo, false);
+    out_parts(c, "filter.l.", l_f.get());
+    c.put("filter.l.row_idxs", l_coo->get_const_row_idxs(), l_f->get_num_stored_elements());
+    out_parts(c, "filter.u.", u_f.get());
+    auto l_a = csr::create(exec, size), ut_a = csr::create(exec, size);
+    ilut::threshold_filter_approx(exec, l_new.get(), ranks[0], tmp, approx[0], l_a.get(), null_coo);
+    ilut::threshold_filter_approx(exec, u_new_csc.get(), ranks[1], tmp, approx[1], ut_a.get(), null_coo);
+    c.put("approx", approx, 2);
+    out_parts(c, "filter_approx.l.", l_a.get());
+    out_parts(c, "filter_approx.u_csc.", ut_a.get());
+}
+
+// par_ict: op 0 ParIct::generate; op 1 each kernel alone on the intermediate matrices of the first iteration
+// (core/factorization/par_ict.cpp:228-292) at fill_in_limit 1.2
+void v_par_ict(Case& c)
+{
+    namespace ict = gko::kernels::reference::par_ict_factorization;
+    namespace ilut = gko::kernels::reference::par_ilut_factorization;
+    namespace fact = gko::kernels::reference::factorization;
+    auto a = gko::share(in_csr<double, gko::int32>(c));
+    const auto size = a->get_size();
+    const size_type n = size[0];
+    if (c.pi("op") == 0) {
+        auto f = threshold_factorization<gko::factorization::ParIct<double, gko::int32>>(c, a);
+        const gko::int32 nnz = static_cast<gko::int32>(f->get_l_factor()->get_num_stored_elements());
+        c.put("nnz", &nnz, 1);
+        out_parts(c, "l.", f->get_l_factor().get());
+        return;
+    }
+    if (c.pi("op") != 1) throw std::runtime_error("unknown par_ict op");
+    gko::array<gko::int32> l_rp(exec, n + 1);
+    fact::initialize_row_ptrs_l(exec, a.get(), l_rp.get_data());
+    const size_t l_nnz = l_rp.get_data()[n];
+    auto l = csr::create(exec, size, gko::array<double>(exec, l_nnz), gko::array<gko::int32>(exec, l_nnz), std::move(l_rp));
+    fact::initialize_l(exec, a.get(), l.get(), true);
+    out_parts(c, "initialize_l.", l.get());
+    const gko::int32 l_limit = static_cast<gko::int32>(l_nnz * 1.2);
+    auto lh = gko::as<csr>(l->conj_transpose());
+    auto llh = csr::create(exec, size);
+    l->apply(lh.get(), llh.get());
+    out_parts(c, "llh.", llh.get());
+    auto l_new = csr::create(exec, size);
+    ict::add_candidates(exec, llh.get(), a.get(), l.get(), l_new.get());
+    out_parts(c, "add_candidates.", l_new.get());
+    const coo* no_coo = nullptr;
+    ict::compute_factor(exec, a.get(), l_new.get(), no_coo);
+    out_parts(c, "sweep.", l_new.get());
+    const gko::int32 ln = static_cast<gko::int32>(l_new->get_num_stored_elements());
+    const gko::int32 rank = std::max<gko::int32>(0, ln - l_limit - 1);
+    c.put("ranks", &rank, 1);
+    gko::array<double> tmp(exec), tmp2(exec);
+    double select = 0.0, approx = 0.0;
+    ilut::threshold_select(exec, l_new.get(), rank, tmp, tmp2, select);
+    c.put("select", &select, 1);
+    coo* null_coo = nullptr;
+    auto l_f = csr::create(exec, size);
+    ilut::threshold_filter(exec, l_new.get(), select, l_f.get(), null_coo, true);
+    out_parts(c, "filter.", l_f.get());
+    auto l_a = csr::create(exec, size);
+    ilut::threshold_filter_approx(exec, l_new.get(), rank, tmp, approx, l_a.get(), null_coo);
+    c.put("approx", &approx, 1);
+    out_parts(c, "filter_approx.", l_a.get());
+    ict::compute_factor(exec, a.get(), l_f.get(), no_coo);
+    out_parts(c, "second_sweep.", l_f.get());
+}
+
+template <gko::preconditioner::isai_type Type>
+std::shared_ptr<const gko::LinOp> isai_inverse(const Case& c, std::shared_ptr<csr> a)
+{
+    return gko::preconditioner::Isai<Type, double, gko::int32>::build()
+        .with_sparsity_power(static_cast<int>(c.pi("sparsity_power")))
+        .with_excess_limit(static_cast<size_type>(c.pi("excess_limit")))
+        .on(exec)
+        ->generate(a)
+        ->get_approximate_inverse();
+}
+
+// isai: Isai::generate by kind, sparsity_power and excess_limit (for spd: L, the second operator of the composition),
+// then generate_tri_inverse / generate_general_inverse alone on that pattern with zeroed values (long rows stay zero)
+// with both prefix arrays and counts = { rows over the limit, their entries, longest row, blocks of the excess loop },
+// and generate_excess_system of every block b of the loop over excess_limit as excess/<b>/...
+void v_isai(Case& c)
+{
+    namespace isai = gko::kernels::reference::isai;
+    using gko::preconditioner::isai_type;
+    auto a = gko::share(in_csr<double, gko::int32>(c));
+    const long n = a->get_size()[0], kind = c.pi("kind"), limit = c.pi("excess_limit");
+    a->sort_by_column_index();
+    const bool tri = kind == ISAI_LOWER || kind == ISAI_UPPER;
+    std::shared_ptr<const csr> inverse;
+    switch (kind) {
+    case ISAI_LOWER: inverse = gko::as<const csr>(isai_inverse<isai_type::lower>(c, a)); break;
+    case ISAI_UPPER: inverse = gko::as<const csr>(isai_inverse<isai_type::upper>(c, a)); break;
+    case ISAI_GENERAL: inverse = gko::as<const csr>(isai_inverse<isai_type::general>(c, a)); break;
+    case ISAI_SPD:
+        inverse = gko::as<const csr>(
+            gko::as<const gko::Composition<double>>(isai_inverse<isai_type::spd>(c, a))->get_operators()[1]);
+        break;
+    default: throw std::runtime_error("unknown isai kind");
+    }
+    auto direct = inverse->clone();
+    std::fill_n(direct->get_values(), direct->get_num_stored_elements(), 0.0);
+    gko::array<gko::int32> rhs_ptrs(exec, n + 1), nz_ptrs(exec, n + 1);
+    if (tri) {
+        isai::generate_tri_inverse(exec, a.get(), direct.get(), rhs_ptrs.get_data(), nz_ptrs.get_data(), kind == ISAI_LOWER);
+    } else {
+        isai::generate_general_inverse(exec, a.get(), direct.get(), rhs_ptrs.get_data(), nz_ptrs.get_data(), kind == ISAI_SPD);
+    }
+    gko::int32 counts[4] = {0, 0, 0, 0};
+    for (long row = 0; row < n; ++row) {
+        const gko::int32 len = direct->get_const_row_ptrs()[row + 1] - direct->get_const_row_ptrs()[row];
+        counts[2] = std::max(counts[2], len);
+        if (len > isai::row_size_limit) {
+            ++counts[0];
+            counts[1] += len;
+        }
+    }
+    // an inverse whose long rows went through the iterative default solver is not reproducible bit for bit
+    if (tri || counts[0] == 0) out_parts(c, "generate/inverse.", inverse.get());
+    out_parts(c, "kernel/direct.", direct.get());
+    c.put("kernel/excess_rhs_ptrs", rhs_ptrs.get_const_data(), n + 1);
+    c.put("kernel/excess_nz_ptrs", nz_ptrs.get_const_data(), n + 1);
+    // the block loop of core/preconditioner/isai.cpp:191-221
+    const auto* host_rhs = rhs_ptrs.get_const_data();
+    const auto* host_nz = nz_ptrs.get_const_data();
+    const long total = host_rhs[n];
+    const long lim = limit == 0 ? total : limit;
+    long block = 0;
+    while (total > 0 && block < n) {
+        const long start = block;
+        long dim = 0;
+        for (; dim < lim && block < n; dim = host_rhs[block] - host_rhs[start]) ++block;
+        if (dim == 0) break;
+        const long e_nnz = host_nz[block] - host_nz[start];
+        auto system = csr::create(exec, gko::dim<2>(dim, dim), e_nnz);
+        auto rhs = dense::create(exec, gko::dim<2>(dim, 1));
+        isai::generate_excess_system(exec, a.get(), direct.get(), host_rhs, host_nz, system.get(), rhs.get(), start, block);
+        const std::string tag = "excess/" + std::to_string(counts[3]) + "/";
+        const gko::int32 range[2] = {static_cast<gko::int32>(start), static_cast<gko::int32>(block)};
+        c.put(tag + "range", range, 2);
+        out_parts(c, tag + "system.", system.get());
+        c.put(tag + "rhs_vals", rhs->get_const_values(), dim);
+        ++counts[3];
+    }
+    c.put("kernel/counts", counts, 4);
+}
+
+gko::stop::mode baseline_mode(long word)
+{
+    switch (word) {
+    case BASE_RHS_NORM: return gko::stop::mode::rhs_norm;
+    case BASE_INITIAL_RESNORM: return gko::stop::mode::initial_resnorm;
+    case BASE_ABSOLUTE: return gko::stop::mode::absolute;
+    }
+    throw std::runtime_error("unknown baseline");
+}
+
+// the stored bits of a Krylov basis as integers of the storage's width; the wire has no 16-bit type, so those go as
+// bytes
+template <typename Stored>
+void out_raw(Case& c, const std::string& name, const Stored* p, size_t count)
+{
+    if (sizeof(Stored) == 8) {
+        c.put(name, reinterpret_cast<const gko::int64*>(p), count);
+    } else if (sizeof(Stored) == 4) {
+        c.put(name, reinterpret_cast<const gko::int32*>(p), count);
+    } else {
+        static_assert(sizeof(Stored) >= 2, "no storage type is narrower than 16 bits");
+        c.put(name, reinterpret_cast<const gko::uint8*>(p), 2 * count);
+    }
+}
+
+// the scalars of an integer basis, (krylov_dim + 1) x nrhs; nothing for the floating storages
+template <typename Range>
+void out_scalars(Case& c, Range range, size_t count, std::true_type)
+{
+    c.put("scalars", range.get_accessor().get_const_scalar(), count);
+}
+
+template <typename Range>
+void out_scalars(Case&, Range, size_t, std::false_type)
+{}
+
+// initialize, restart, `steps` times { next = A next; arnoldi } with column stop_col stopped before step stop_step
+// (-1: never), then solve_krylov
+template <typename Storage>
+void cb_gmres_kernels(Case& c, const csr* a, const dense* b)
+{
+    namespace kernels = gko::kernels::reference::cb_gmres;
+    using helper = gko::cb_gmres::Range3dHelper<double, Storage>;
+    const size_type n = b->get_size()[0], nrhs = b->get_size()[1], kd = c.pi("krylov_dim");
+    const long steps = c.pi("steps"), stop_col = c.pi("stop_col"), stop_step = c.pi("stop_step");
+    helper h(exec, gko::dim<3>{kd + 1, n, nrhs});
+    auto range = h.get_range();
+    auto residual = dense::create(exec, dim<2>{n, nrhs});
+    auto next = dense::create(exec, dim<2>{n, nrhs});
+    auto pv = dense::create(exec, dim<2>{n, nrhs});
+    auto hessenberg = dense::create(exec, dim<2>{kd + 1, kd * nrhs});
+    auto buffer = dense::create(exec, dim<2>{kd + 1, nrhs});
+    auto gsin = dense::create(exec, dim<2>{kd, nrhs});
+    auto gcos = dense::create(exec, dim<2>{kd, nrhs});
+    auto rnc = dense::create(exec, dim<2>{kd + 1, nrhs});
+    auto residual_norm = dense::create(exec, dim<2>{1, nrhs});
+    auto arnoldi_norm = dense::create(exec, dim<2>{3, nrhs});
+    auto y = dense::create(exec, dim<2>{kd, nrhs});
+    auto before = dense::create(exec, dim<2>{n, nrhs});
+    hessenberg->fill(0.0);
+    buffer->fill(0.0);
+    arnoldi_norm->fill(0.0);
+    y->fill(0.0);
+    gko::array<size_type> final_iter_nums(exec, nrhs), num_reorth(exec, 1);
+    gko::array<gko::stopping_status> stop_status(exec, nrhs), reorth_status(exec, nrhs);
+    gko::array<char> tmp(exec);
+
+    kernels::initialize(exec, b, residual.get(), gsin.get(), gcos.get(), &stop_status, kd);
+    out_rows(c, "initialize/residual", residual.get());
+    kernels::restart(exec, residual.get(), residual_norm.get(), rnc.get(), arnoldi_norm.get(), range, next.get(),
+                     &final_iter_nums, tmp, kd);
+    out_rows(c, "restart/residual_norm", residual_norm.get());
+    out_rows(c, "restart/residual_norm_collection", rnc.get());
+    out_rows(c, "restart/next", next.get());
+    out_raw(c, "restart/basis", h.get_bases().get_const_data(), (kd + 1) * n * nrhs);
+    for (long s = 0; s < steps; ++s) {
+        if (s == stop_step) stop_status.get_data()[stop_col].stop(1);
+        pv->copy_from(next.get());
+        a->apply(pv.get(), next.get());
+        auto hessenberg_iter = hessenberg->create_submatrix(gko::span{0, s + 2}, gko::span{nrhs * s, nrhs * (s + 1)});
+        auto buffer_iter = buffer->create_submatrix(gko::span{0, s + 2}, gko::span{0, nrhs});
+        kernels::arnoldi(exec, next.get(), gsin.get(), gcos.get(), residual_norm.get(), rnc.get(), range,
+                         hessenberg_iter.get(), buffer_iter.get(), arnoldi_norm.get(), s, &final_iter_nums, &stop_status,
+                         &reorth_status, &num_reorth);
+        const std::string at = "arnoldi/" + std::to_string(s) + "/";
+        out_rows(c, at + "next", next.get());
+        out_rows(c, at + "hessenberg_iter", hessenberg_iter.get());
+        out_rows(c, at + "arnoldi_norm", arnoldi_norm.get());
+        out_rows(c, at + "residual_norm", residual_norm.get());
+        out_rows(c, at + "residual_norm_collection", rnc.get());
+        out_counts(c, at + "final_iter_nums", final_iter_nums.get_const_data(), nrhs);
+    }
+    out_rows(c, "givens_sin", gsin.get());
+    out_rows(c, "givens_cos", gcos.get());
+    auto hessenberg_view = hessenberg->create_submatrix(gko::span{0, steps}, gko::span{0, nrhs * steps});
+    kernels::solve_krylov(exec, rnc.get(), range.get_accessor().to_const(), hessenberg_view.get(), y.get(), before.get(),
+                          &final_iter_nums);
+    out_rows(c, "solve_krylov/y", y.get());
+    out_rows(c, "solve_krylov/before_preconditioner", before.get());
+    out_raw(c, "basis", h.get_bases().get_const_data(), (kd + 1) * n * nrhs);
+    out_scalars(c, range, (kd + 1) * nrhs, gko::cb_gmres::detail::has_3d_scaled_accessor<decltype(range)>{});
+}
+
+// cb_gmres: op 0 a whole solve from x = 0 (storage, krylov_dim, max_iters, reduction, baseline, jacobi = the
+// block-Jacobi max_block_size or 0 for no preconditioner); op 1 the four kernels (cb_gmres_kernels above).
+// storage is the reference's storage_precision: 0 keep, 1 reduce1, 2 reduce2, 3 integer, 4 ireduce1, 5 ireduce2
+void v_cb_gmres(Case& c)
+{
+    using gko::solver::cb_gmres::storage_precision;
+    auto a = gko::share(in_csr<double, gko::int32>(c));
+    auto b = in_dense<double>(c, "b");
+    const long storage = c.pi("storage");
+    if (c.pi("op") == 0) {
+        auto builder = gko::solver::CbGmres<double>::build()
+                           .with_krylov_dim(static_cast<size_type>(c.pi("krylov_dim")))
+                           .with_storage_precision(static_cast<storage_precision>(storage))
+                           .with_criteria(gko::stop::Iteration::build()
+                                              .with_max_iters(static_cast<size_type>(c.pi("max_iters")))
+                                              .on(exec),
+                                          gko::stop::ResidualNorm<double>::build()
+                                              .with_baseline(baseline_mode(c.pi("baseline")))
+                                              .with_reduction_factor(c.p("reduction"))
+                                              .on(exec));
+        if (c.pi("jacobi") > 0) {
+            builder.with_preconditioner(gko::preconditioner::Jacobi<double, gko::int32>::build()
+                                            .with_max_block_size(static_cast<gko::uint32>(c.pi("jacobi")))
+                                            .on(exec));
+        }
+        auto solver = builder.on(exec)->generate(a);
+        auto logger = std::make_shared<iteration_logger>();
+        solver->add_logger(logger);
+        auto x = dense::create(exec, b->get_size());
+        x->fill(0.0);
+        solver->apply(b.get(), x.get());
+        out_rows(c, "x", x.get());
+        c.put_scalar<gko::int64>("iterations", logger->last);
+        c.put("residual_norm", logger->tau.data(), logger->tau.size());
+        return;
+    }
+    if (c.pi("op") != 1) throw std::runtime_error("unknown cb_gmres op");
+    switch (storage) {
+    case 0: return cb_gmres_kernels<double>(c, a.get(), b.get());
+    case 1: return cb_gmres_kernels<float>(c, a.get(), b.get());
+    case 2: return cb_gmres_kernels<gko::half>(c, a.get(), b.get());
+    case 3: return cb_gmres_kernels<gko::int64>(c, a.get(), b.get());
+    case 4: return cb_gmres_kernels<gko::int32>(c, a.get(), b.get());
+    case 5: return cb_gmres_kernels<gko::int16>(c, a.get(), b.get());
+    default: throw std::runtime_error("unknown storage");
+    }
+}
+
+gko::solver::initial_guess_mode guess_mode(long word)
+{
+    switch (word) {
+    case GUESS_ZERO: return gko::solver::initial_guess_mode::zero;
+    case GUESS_RHS: return gko::solver::initial_guess_mode::rhs;
+    case GUESS_PROVIDED: return gko::solver::initial_guess_mode::provided;
+    }
+    throw std::runtime_error("unknown initial guess");
+}
+
+// the i32 array `name` of smoother words, of any length
+factories smoothers(const Case& c, const std::string& name)
+{
+    factories out;
+    size_t count;
+    const gko::int32* words = c.arr<gko::int32>(name, &count);
+    for (size_t i = 0; i < count; ++i) {
+        switch (words[i]) {
+        case SMOOTHER_NULL: out.push_back(nullptr); break;
+        case SMOOTHER_EYE: out.push_back(gko::share(gko::matrix::IdentityFactory<double>::create(exec))); break;
+        case SMOOTHER_JACOBI:
+            out.push_back(gko::share(gko::preconditioner::Jacobi<double, gko::int32>::build().with_max_block_size(1u).on(exec)));
+            break;
+        default: throw std::runtime_error("unknown smoother");
+        }
+    }
+    return out;
+}
+
+// solver::Multigrid over the given level factories, applied to b and x: cycle, mid_case, post_uses_pre, max_levels,
+// min_coarse_rows, coarsest (direct: Lu with symmetric sparsity; cg: ten iterations), relax, smoother_iters, guess,
+// max_iters, reduction (0: Iteration only) and the smoother lists pre, mid, post.  With cg_max_iters and cg_reduction
+// that Multigrid preconditions a Cg instead, which is applied.  The solve of multigrid and of pgm.
+void multigrid_solve(Case& c, const factories& levels)
+{
+    namespace mg = gko::solver::multigrid;
+    auto a = gko::share(in_csr<double, gko::int32>(c));
+    auto b = in_dense<double>(c, "b");
+    auto x = in_dense<double>(c, "x");
+    factories coarsest;
+    switch (c.pi("coarsest")) {
+    case COARSEST_IDENTITY: break;
+    case COARSEST_DIRECT:
+        coarsest.push_back(gko::share(gko::experimental::solver::Direct<double, gko::int32>::build()
+                                          .with_factorization(gko::experimental::factorization::Lu<double, gko::int32>::build()
+                                                                  .with_symmetric_sparsity(true)
+                                                                  .on(exec))
+                                          .on(exec)));
+        break;
+    case COARSEST_CG:
+        coarsest.push_back(gko::share(
+            gko::solver::Cg<double>::build().with_criteria(gko::stop::Iteration::build().with_max_iters(10u).on(exec)).on(exec)));
+        break;
+    default: throw std::runtime_error("unknown coarsest solver");
+    }
+    std::vector<std::shared_ptr<const gko::stop::CriterionFactory>> criteria;
+    criteria.push_back(
+        gko::share(gko::stop::Iteration::build().with_max_iters(static_cast<size_type>(c.pi("max_iters"))).on(exec)));
+    if (c.p("reduction") != 0.0) {
+        criteria.push_back(gko::share(gko::stop::ResidualNorm<double>::build()
+                                          .with_baseline(gko::stop::mode::rhs_norm)
+                                          .with_reduction_factor(c.p("reduction"))
+                                          .on(exec)));
+    }
+    mg::mid_smooth_type mid_case;
+    switch (c.pi("mid_case")) {
+    case MID_BOTH: mid_case = mg::mid_smooth_type::both; break;
+    case MID_POST_SMOOTHER: mid_case = mg::mid_smooth_type::post_smoother; break;
+    case MID_PRE_SMOOTHER: mid_case = mg::mid_smooth_type::pre_smoother; break;
+    case MID_STANDALONE: mid_case = mg::mid_smooth_type::standalone; break;
+    default: throw std::runtime_error("unknown mid_case");
+    }
+    mg::cycle cycle;
+    switch (c.pi("cycle")) {
+    case CYCLE_V: cycle = mg::cycle::v; break;
+    case CYCLE_F: cycle = mg::cycle::f; break;
+    case CYCLE_W: cycle = mg::cycle::w; break;
+    default: throw std::runtime_error("unknown cycle");
+    }
+    auto factory = gko::solver::Multigrid::build()
+                      .with_mg_level(levels)
+                      .with_pre_smoother(smoothers(c, "pre"))
+                      .with_mid_smoother(smoothers(c, "mid"))
+                      .with_post_smoother(smoothers(c, "post"))
+                      .with_post_uses_pre(c.pi("post_uses_pre") != 0)
+                      .with_mid_case(mid_case)
+                      .with_max_levels(static_cast<size_type>(c.pi("max_levels")))
+                      .with_min_coarse_rows(static_cast<size_type>(c.pi("min_coarse_rows")))
+                      .with_coarsest_solver(coarsest)
+                      .with_cycle(cycle)
+                      .with_smoother_relax(c.p("relax"))
+                      .with_smoother_iters(static_cast<size_type>(c.pi("smoother_iters")))
+                      .with_default_initial_guess(guess_mode(c.pi("guess")))
+                      .with_criteria(criteria)
+                      .on(exec);
+    auto logger = std::make_shared<iteration_logger>();
+    if (c.has("cg_max_iters")) {
+        auto cg = gko::solver::Cg<double>::build()
+                      .with_preconditioner(gko::share(std::move(factory)))
+                      .with_criteria(gko::stop::Iteration::build()
+                                         .with_max_iters(static_cast<size_type>(c.pi("cg_max_iters")))
+                                         .on(exec),
+                                     gko::stop::ResidualNorm<double>::build()
+                                         .with_baseline(gko::stop::mode::rhs_norm)
+                                         .with_reduction_factor(c.p("cg_reduction"))
+                                         .on(exec))
+                      .on(exec)
+                      ->generate(a);
+        cg->add_logger(logger);
+        cg->apply(b.get(), x.get());
+        out_rows(c, "x", x.get());
+        c.put_scalar<gko::int64>("iterations", logger->last);
+        return;
+    }
+    auto solver = factory->generate(a);
+    solver->add_logger(logger);
+    solver->apply(b.get(), x.get());
+    out_rows(c, "x", x.get());
+    c.put_scalar<gko::int64>("iterations", logger->last);
+    std::vector<gko::int64> rows;
+    for (const auto& level : solver->get_mg_level_list()) {
+        rows.push_back(static_cast<gko::int64>(level->get_coarse_op()->get_size()[0]));
+    }
+    c.put("levels", rows.data(), rows.size());
+}
+
+// FixedCoarsening on every second row (or on every row: a level that does not reduce) of whatever matrix it is handed
+struct strided_coarsening : gko::EnablePolymorphicObject<strided_coarsening, gko::LinOpFactory> {
+    explicit strided_coarsening(std::shared_ptr<const gko::Executor> e, long stride = 2)
+        : gko::EnablePolymorphicObject<strided_coarsening, gko::LinOpFactory>(e), stride_(stride)
+    {}
+    std::unique_ptr<gko::LinOp> generate_impl(std::shared_ptr<const gko::LinOp> op) const override
+    {
+        const long n = static_cast<long>(op->get_size()[0]);
+        const long m = (n + stride_ - 1) / stride_;
+        gko::array<gko::int32> rows(this->get_executor(), m);
+        for (long i = 0; i < m; ++i) rows.get_data()[i] = static_cast<gko::int32>(i * stride_);
+        return gko::multigrid::FixedCoarsening<double, gko::int32>::build().with_coarse_rows(rows).on(this->get_executor())->generate(op);
+    }
+    long stride_;
+};
+
+// multigrid: op 0 the three kcycle kernels on alpha rho gamma beta zeta (1 x nrhs) and v g d e (n x nrhs);
+// op 1 FixedCoarsening on coarse_rows; op 2 the smoother Multigrid builds, Ir over scalar Jacobi (sweeps, zero_guess,
+// relax); op 3 a whole solve (multigrid_solve) over the mg_level words halve / all_rows
+void v_multigrid(Case& c)
+{
+    namespace kernels = gko::kernels::reference::multigrid;
+    switch (c.pi("op")) {
+    case 0: {
+        auto alpha = in_dense<double>(c, "alpha"), rho = in_dense<double>(c, "rho"), gamma = in_dense<double>(c, "gamma");
+        auto beta = in_dense<double>(c, "beta"), zeta = in_dense<double>(c, "zeta");
+        auto v = in_dense<double>(c, "v"), g = in_dense<double>(c, "g"), d = in_dense<double>(c, "d"), e = in_dense<double>(c, "e");
+        const long nrhs = alpha->get_size()[1];
+        auto d2 = gko::clone(d), e2 = gko::clone(e);
+        kernels::kcycle_step_1(exec, alpha.get(), rho.get(), v.get(), g.get(), d.get(), e.get());
+        out_rows(c, "step_1/g", g.get());
+        out_rows(c, "step_1/d", d.get());
+        out_rows(c, "step_1/e", e.get());
+        kernels::kcycle_step_2(exec, alpha.get(), rho.get(), gamma.get(), beta.get(), zeta.get(), d2.get(), e2.get());
+        out_rows(c, "step_2/e", e2.get());
+        // old = beta, new = 0.25 beta: equal to the threshold in every column, then one column just above it
+        auto fresh = gko::clone(beta);
+        for (long j = 0; j < nrhs; ++j) fresh->at(0, j) = 0.25 * beta->at(0, j);
+        bool equal = false, above = true;
+        kernels::kcycle_check_stop(exec, beta.get(), fresh.get(), 0.25, equal);
+        fresh->at(0, nrhs - 1) = std::nextafter(fresh->at(0, nrhs - 1), 1e300);
+        kernels::kcycle_check_stop(exec, beta.get(), fresh.get(), 0.25, above);
+        const gko::int64 stops[2] = {equal, above};
+        c.put("check_stop/is_stop", stops, 2);
+        break;
+    }
+    case 1: {
+        auto a = gko::share(in_csr<double, gko::int32>(c));
+        auto level = gko::multigrid::FixedCoarsening<double, gko::int32>::build()
+                         .with_coarse_rows(in_array<gko::int32>(c, "coarse_rows"))
+                         .with_skip_sorting(c.pi("skip_sorting") != 0)
+                         .on(exec)
+                         ->generate(a);
+        out_parts(c, "fine/", level->get_fine_op().get());
+        out_parts(c, "restrict/", level->get_restrict_op().get());
+        out_parts(c, "prolong/", level->get_prolong_op().get());
+        out_parts(c, "coarse/", level->get_coarse_op().get());
+        break;
+    }
+    case 2: {
+        auto a = gko::share(in_csr<double, gko::int32>(c));
+        auto b = in_dense<double>(c, "b");
+        auto x = in_dense<double>(c, "x");
+        std::shared_ptr<const gko::LinOpFactory> inner =
+            gko::preconditioner::Jacobi<double, gko::int32>::build().with_max_block_size(1u).on(exec);
+        // build_smoother's Ir (include/ginkgo/core/solver/ir.hpp:314-326) with the initial-guess mode as a factory
+        // parameter: apply_with_initial_guess itself is reserved to Multigrid
+        auto smoother = gko::solver::Ir<double>::build()
+                            .with_solver(inner)
+                            .with_relaxation_factor(c.p("relax"))
+                            .with_criteria(gko::stop::Iteration::build()
+                                               .with_max_iters(static_cast<size_type>(c.pi("sweeps")))
+                                               .on(exec))
+                            .with_default_initial_guess(guess_mode(c.pi("zero_guess") ? GUESS_ZERO : GUESS_PROVIDED))
+                            .on(exec)
+                            ->generate(a);
+        smoother->apply(b.get(), x.get());
+        out_rows(c, "x", x.get());
+        break;
+    }
+    case 3: {
+        factories levels;
+        size_t count;
+        const gko::int32* words = c.arr<gko::int32>("mg_level", &count);
+        for (size_t i = 0; i < count; ++i) {
+            if (words[i] != LEVEL_HALVE && words[i] != LEVEL_ALL_ROWS) throw std::runtime_error("unknown mg_level");
+            levels.push_back(std::make_shared<strided_coarsening>(exec, words[i] == LEVEL_ALL_ROWS ? 1 : 2));
+        }
+        multigrid_solve(c, levels);
+        break;
+    }
+    default: throw std::runtime_error("unknown multigrid op");
+    }
+}
+
+// pgm: op 0 Pgm::generate (pgm_max_iterations, pgm_max_unassigned_ratio, pgm_deterministic, skip_sorting): the
+// aggregates, the restriction, the fine operator's column order and the coarse matrix; op 1 a whole solve
+// (multigrid_solve) with that Pgm factory for every mg_level word
+void v_pgm(Case& c)
+{
+    using pgm = gko::multigrid::Pgm<double, gko::int32>;
+    long op = c.pi("op");
+    auto factory = gko::share(pgm::build()
+                                  .with_max_iterations(static_cast<unsigned>(c.pi("pgm_max_iterations")))
+                                  .with_max_unassigned_ratio(c.p("pgm_max_unassigned_ratio"))
+                                  .with_deterministic(c.pi("pgm_deterministic") != 0)
+                                  .with_skip_sorting(op == 0 && c.pi("skip_sorting") != 0)
+                                  .on(exec));
+    if (op == 0) {
+        auto a = gko::share(in_csr<double, gko::int32>(c));
+        auto level = factory->generate(a);
+        const size_t n = a->get_size()[0];
+        out_counts(c, "agg", level->get_const_agg(), n);
+        auto restriction = gko::as<gko::matrix::SparsityCsr<double, gko::int32>>(level->get_restrict_op());
+        c.put_scalar<gko::int64>("num_agg", restriction->get_size()[0]);
+        c.put("restrict/row_ptrs", restriction->get_const_row_ptrs(), restriction->get_size()[0] + 1);
+        c.put("restrict/col_idxs", restriction->get_const_col_idxs(), n);
+        auto fine = gko::as<csr>(level->get_fine_op());
+        c.put("fine/col_idxs", fine->get_const_col_idxs(), fine->get_num_stored_elements());
+        out_parts(c, "coarse/", level->get_coarse_op().get());
+    } else if (op == 1) {
+        size_t count;
+        const gko::int32* words = c.arr<gko::int32>("mg_level", &count);
+        for (size_t i = 0; i < count; ++i) {
+            if (words[i] != LEVEL_PGM) throw std::runtime_error("unknown mg_level");
+        }
+        multigrid_solve(c, factories(count, factory));
+    } else {
+        throw std::runtime_error("unknown pgm op");
+    }
+}
+
 // ---- dispatch: vt 0 double, 1 float; it 0 int32, 1 int64
 
 void run(Case& c)
@@ -763,6 +1453,12 @@ void run(Case& c)
         if (v == "trs") return v_trs<double, gko::int32>(c);
         if (v == "jacobi") return v_jacobi<double, gko::int32>(c);
         if (v == "solve") return v_solve<double, gko::int32>(c);
+        if (v == "par_ilut") return v_par_ilut(c);
+        if (v == "par_ict") return v_par_ict(c);
+        if (v == "isai") return v_isai(c);
+        if (v == "cb_gmres") return v_cb_gmres(c);
+        if (v == "multigrid") return v_multigrid(c);
+        if (v == "pgm") return v_pgm(c);
     }
     throw std::runtime_error("no verb " + v + " for these types");
 }

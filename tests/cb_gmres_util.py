@@ -10,7 +10,12 @@ core/solver/cb_gmres.cpp:204-487, forced-iteration logic included.  Two switches
          ("device", rows per lane): the order in which csrc/cb_gmres.hip adds (device_sum below).
 
 tests/test_cb_gmres_reference.py pins truncate + sequential to results recorded from the reference, bit for bit."""
+import functools
+
 import numpy as np
+
+import ref_exec
+from ref_exec import as_record, matches, unhex      # the GPU tests reach matches and unhex through this module
 
 STORAGES = ("keep", "reduce1", "reduce2", "integer", "ireduce1", "ireduce2")
 STORAGE_DTYPE = {"keep": np.float64, "reduce1": np.float32, "reduce2": np.uint16, "integer": np.int64,
@@ -402,7 +407,7 @@ def solve(matrix, b, x, krylov_dim, storage, max_iters, reduction, baseline="rhs
             "passes": passes_seen, "converged": bool(np.all((status & 0x80) != 0)), "baseline_norm": base}
 
 
-# ---- the recorded cases (tools/cb_gmres_ref_record.cpp -> tests/golden/cb_gmres_ref.json) ---------------------------
+# ---- the recorded cases (ref_driver's verb cb_gmres -> tests/golden/cb_gmres_ref.json) ------------------------------
 
 def _dense_case(rows, b, x, krylov_dim=100, reduction=1e-14, max_iters=100):
     """a known-answer system of reference/test/solver/cb_gmres_kernels.cpp (numbers only): baseline initial_resnorm"""
@@ -464,67 +469,30 @@ def solve_problem(case):
     return n, rp, ci, v, right_hand_side(n, case["nrhs"])
 
 
-def _problem_text(n, rp, ci, v, b):
-    return " ".join([" ".join(str(int(t)) for t in rp), " ".join(str(int(t)) for t in ci),
-                     " ".join(float(t).hex() for t in v), " ".join(float(t).hex() for t in b.reshape(-1))])
+def queue_cases(batch):
+    """queues every solve and every kernel trace, for every storage, on a ref_exec.Batch -> {case/storage: index}"""
+    where = {}
+    for op, cases in ((0, SOLVE_CASES), (1, KERNEL_CASES)):
+        for name, c in cases.items():
+            n, rp, ci, v, b = solve_problem(c)
+            arrays, size = ref_exec.csr_arrays(n, n, rp, ci, v)
+            rhs, shape = ref_exec.dense_arrays("b", b)
+            if op == 0:
+                params = dict(max_iters=c["max_iters"], reduction=c["reduction"], jacobi=c["jacobi"],
+                              baseline=ref_exec.word("baseline", c["baseline"]))
+            else:
+                params = dict(steps=c["steps"], stop_col=c["stop_col"], stop_step=c["stop_step"])
+            for storage in STORAGES:
+                where[f"{name}/{storage}"] = batch.add("cb_gmres", {**arrays, **rhs}, op=op, krylov_dim=c["krylov_dim"],
+                                                       storage=ref_exec.word("storage", storage), **params, **size, **shape)
+    return where
 
 
-def recorder_input():
-    lines = []
-    for name, c in SOLVE_CASES.items():
-        n, rp, ci, v, b = solve_problem(c)
-        for sid, storage in enumerate(STORAGES):
-            lines.append(f"solve {name}/{storage} {sid} {c['krylov_dim']} {c['max_iters']} {float(c['reduction']).hex()} "
-                         f"{0 if c['baseline'] == 'rhs_norm' else 1} {c['jacobi']} {n} {b.shape[1]} {len(ci)} "
-                         + _problem_text(n, rp, ci, v, b))
-    for name, c in KERNEL_CASES.items():
-        n, rp, ci, v, b = solve_problem(c)
-        for sid, storage in enumerate(STORAGES):
-            lines.append(f"kernels {name}/{storage} {sid} {c['krylov_dim']} {c['steps']} {c['stop_col']} "
-                         f"{c['stop_step']} {n} {b.shape[1]} {len(ci)} " + _problem_text(n, rp, ci, v, b))
-    return "\n".join(lines) + "\n"
-
-
-def parse_recorder_output(text):
-    """{case/storage: {what: [items as written]}}"""
-    out = {}
-    for line in text.splitlines():
-        name, what, count, *items = line.split()
-        assert len(items) == int(count), (name, what)
-        out.setdefault(name, {})[what] = items
-    return out
-
-
-def hexes(a):
-    return [float(t).hex() for t in np.asarray(a, np.float64).reshape(-1)]
-
-
-def unhex(items):
-    return np.array([float.fromhex(t) for t in items], np.float64)
-
-
-LONG = 32   # arrays up to this many entries are kept in full, longer ones as their count, digest and first entries
-
-
-def as_record(items, integers=False):
-    """what the fixture keeps of a recorded array: doubles as hexadecimal floats, the basis as raw integers; a long
-    array as the SHA-256 of its bits (float64 / int64, little-endian) with its count and its first four entries"""
-    import hashlib
-    items = [int(t) for t in items] if integers else list(items)
-    if len(items) <= LONG:
-        return items
-    bits = np.array(items, "<i8") if integers else unhex(items).astype("<f8")
-    head = items[:4] if integers else [float.fromhex(t).hex() for t in items[:4]]     # one spelling, Python's
-    return {"count": len(items), "sha256": hashlib.sha256(bits.tobytes()).hexdigest(), "head": head}
-
-
-def matches(rec, got, integers=False):
-    """the array `got` is the recorded one, bit for bit"""
-    got = np.ascontiguousarray(got).reshape(-1)
-    mine = as_record([int(t) for t in got] if integers else hexes(got), integers)
-    if isinstance(rec, dict) or integers:
-        return mine == rec
-    return len(rec) == got.size and np.array_equal(unhex(rec).view(np.int64), got.astype(np.float64).view(np.int64))
+def case_arrays(results, where):
+    """{case/storage: {what: array}}; the Krylov basis comes back as the stored bits in the storage's own width and
+    is widened here"""
+    return {key: {what: a.view(RAW_DTYPE[key.split("/")[-1]]).astype(np.int64) if what.endswith("basis") else a
+                  for what, a in results[i].items()} for key, i in where.items()}
 
 
 def dump_fixture(fix, path):
@@ -550,12 +518,18 @@ def restated_solve(name, storage, half, group=0, trace=None):
     return x, res
 
 
+@functools.lru_cache(maxsize=None)
+def _rne_iterations(name, storage, group):
+    """the restatement's iteration count in "rne" mode: computed once, for the tests and for fixture_from"""
+    return restated_solve(name, storage, "rne", group)[1]["iterations"]
+
+
 def reordered_counts(name, storage):
     """the restatement's iteration counts ("rne") with the sums grouped by 64, by 1024 and in the device's own order: a
     case whose counts all stay within 1 of the sequential one is held to +-1 of the sequential count on the device; any
     other says nothing about a sum order but its own and is held to +-1 of the count in the device's order, the last"""
     per_lane = 16 // np.dtype(STORAGE_DTYPE[storage]).itemsize
-    return [restated_solve(name, storage, "rne", g)[1]["iterations"] for g in (64, 1024, ("device", per_lane))]
+    return [_rne_iterations(name, storage, g) for g in (64, 1024, ("device", per_lane))]
 
 
 def count_is_stable(rec):
@@ -582,22 +556,20 @@ def jacobi_apply(n, rp, ci, v, max_block_size, nrhs):
 
 
 def fixture_from(records):
-    """the committed fixture from the recorder's output plus what the restatement adds: the iteration counts in "rne"
-    mode (sequential sums), which the GPU tests compare the half and integer storages with"""
-    fix = {"source": "tools/cb_gmres_ref_record.cpp over the reference executor; cases: tests/cb_gmres_util.py "
+    """the committed fixture from the driver's arrays (case_arrays) plus what the restatement adds: the iteration
+    counts in "rne" mode (sequential sums), which the GPU tests compare the half and integer storages with"""
+    fix = {"source": "oracle/ref_driver.cpp, verb cb_gmres, over the reference executor; cases: tests/cb_gmres_util.py "
                      "(SOLVE_CASES with the known-answer systems of reference/test/solver/cb_gmres_kernels.cpp, "
                      "KERNEL_CASES)", "solves": {}, "kernels": {}}
     for name in SOLVE_CASES:
         for storage in STORAGES:
             r = records[f"{name}/{storage}"]
-            _, rne = restated_solve(name, storage, "rne")
             fix["solves"][f"{name}/{storage}"] = {"x": as_record(r["x"]), "iterations": int(r["iterations"][0]),
-                                                 "residual_norm": r["residual_norm"],
-                                                 "rne_iterations": rne["iterations"],
+                                                 "residual_norm": as_record(r["residual_norm"]),
+                                                 "rne_iterations": _rne_iterations(name, storage, 0),
                                                  "reordered_iterations": reordered_counts(name, storage)}
     for name in KERNEL_CASES:
         for storage in STORAGES:
             r = records[f"{name}/{storage}"]
-            fix["kernels"][f"{name}/{storage}"] = {k: as_record(v, "basis" in k or "final_iter" in k)
-                                                   for k, v in r.items()}
+            fix["kernels"][f"{name}/{storage}"] = {k: as_record(v) for k, v in r.items()}
     return fix

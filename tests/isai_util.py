@@ -13,8 +13,10 @@ import numpy as np
 
 import ilu_exact_util as xu
 import lu_util
+import ref_exec
 import spgemm_util as su
 from ilu_exact_util import _arrays, _div, _lists, _sqrt
+from ref_exec import digest
 
 ROW_SIZE_LIMIT = 32          # kernels::isai::row_size_limit (core/preconditioner/isai_kernels.hpp)
 KINDS = ("lower", "upper", "general", "spd")
@@ -290,16 +292,6 @@ def golden_mtx(name, stored_zero=None):
     return xu.sort_by_column_index(tuple(matgen.coo_to_csr(nr, rows, cols, vals)))
 
 
-def tril(m):
-    rows = xu.to_rows(m)
-    return xu.from_rows([{c: v for c, v in row.items() if c <= r} for r, row in enumerate(rows)])
-
-
-def triu(m):
-    rows = xu.to_rows(m)
-    return xu.from_rows([{c: v for c, v in row.items() if c >= r} for r, row in enumerate(rows)])
-
-
 def ilu0_factors(name):
     """(L, U) of the exact ILU(0) of a golden matrix"""
     return xu.ilu_generate(golden_mtx(name))
@@ -351,12 +343,7 @@ def spd_banded(n, half, seed=11):
     return xu.from_rows(rows)
 
 
-def with_pattern(m, pattern_rows):
-    """an explicit pattern for the inverse: rows as lists of columns, values 0"""
-    return xu.from_rows([{c: 0.0 for c in sorted(cols)} for cols in pattern_rows])
-
-
-# ---- results recorded from the reference executor (tools/isai_ref_record.cpp -> golden/isai_ref.json) -----------------
+# ---- results recorded from the reference executor (ref_driver's verb isai -> golden/isai_ref.json) -------------------
 
 def _ani1_lower(change):
     rows = xu.to_rows(ilu0_factors("ani1.mtx")[0])
@@ -398,7 +385,7 @@ def _cases():
 
 RECORDED_CASES = _cases()
 # name -> (rows over the limit, their entries, longest row, blocks of the excess loop): computed on the CPU from the
-# patterns of the all-ones powers of the matrices; the recorder prints what it meets and the tests compare
+# patterns of the all-ones powers of the matrices; the driver's counts are what it meets and the tests compare
 EXPECTED_COUNTS = {
     "ani4_l_p3": (0, 0, 28, 0), "ani4_u_p3": (0, 0, 25, 0),
     "ani4_l_p4_limit0": (157, 5574, None, 1), "ani4_u_p4_limit0": (51, 1829, None, 1),
@@ -408,48 +395,32 @@ EXPECTED_COUNTS = {
 }
 
 
-def recorder_input(cases):
-    """the stdin of tools/isai_ref_record.cpp for {name: (kind, power, limit, matrix)}"""
-    out = []
-    for name, (kind, power, limit, m) in cases.items():
-        rp, ci, v = m
-        out.append(f"case {name} {kind} {power} {limit} {len(rp) - 1} {len(ci)}")
-        out.append(" ".join(str(int(x)) for x in rp))
-        out.append(" ".join(str(int(x)) for x in ci))
-        out.append(" ".join(float(x).hex() for x in v))
-    return "\n".join(out) + "\n"
+def made_cases():
+    return {name: (kind, power, limit, make()) for name, (kind, power, limit, make) in RECORDED_CASES.items()}
 
 
-def parse_recorder_output(text):
-    """{case: {"<section>/<name>": array or {"row_ptrs", "col_idxs", "vals"}}} from the recorder's stdout"""
+def queue_cases(batch):
+    """queues every recorded case on a ref_exec.Batch -> {name: index of its result}"""
+    where = {}
+    for name, (kind, power, limit, (rp, ci, v)) in made_cases().items():
+        arrays, size = ref_exec.csr_arrays(len(rp) - 1, len(rp) - 1, rp, ci, v)
+        where[name] = batch.add("isai", arrays, kind=ref_exec.word("isai", kind), sparsity_power=power,
+                                excess_limit=limit, **size)
+    return where
+
+
+def case_arrays(results, where):
+    """{case: {"<section>/<name>": array or {"row_ptrs", "col_idxs", "vals"}}} from the driver's results"""
     res = {}
-    for line in text.splitlines():
-        t = line.split()
-        case, section, what, count = t[0], t[1], t[2], int(t[3])
-        assert len(t) == 4 + count, line[:80]
-        if what.endswith("vals"):
-            arr = np.array([float.fromhex(x) for x in t[4:]], np.float64)
-        else:
-            arr = np.array([int(x) for x in t[4:]], np.int32)
-        rec = res.setdefault(case, {})
-        if "." in what:
-            mat, part = what.split(".")
-            rec.setdefault(f"{section}/{mat}", {})[part] = arr
-        else:
-            rec[f"{section}/{what}"] = arr
+    for name, i in where.items():
+        rec = res.setdefault(name, {})
+        for what, arr in results[i].items():
+            if "." in what:
+                mat, part = what.split(".")
+                rec.setdefault(mat, {})[part] = arr
+            else:
+                rec[what] = arr
     return res
-
-
-def digest(rec):
-    """SHA-256 of the bytes of an array (little-endian int32 / float64), of a CSR matrix those of row_ptrs, col_idxs
-    and vals one after the other"""
-    import hashlib
-    parts = [rec[k] for k in ("row_ptrs", "col_idxs", "vals")] if isinstance(rec, dict) else [rec]
-    return hashlib.sha256(b"".join(np.ascontiguousarray(p).tobytes() for p in parts)).hexdigest()
-
-
-def as_record(m):
-    return dict(zip(("row_ptrs", "col_idxs", "vals"), m))
 
 
 def fixture_record(rec):
@@ -462,26 +433,12 @@ def fixture_record(rec):
     return out
 
 
-def fixture_from(recorded, cases):
-    return {"source": "tools/isai_ref_record.cpp over the reference executor (preconditioner::Isai::generate and "
-                      "kernels::reference::isai) on RECORDED_CASES of tests/isai_util.py; sha256: see digest() there",
+def fixture_from(recorded):
+    cases = made_cases()
+    return {"source": "oracle/ref_driver.cpp, verb isai, over the reference executor (preconditioner::Isai::generate "
+                      "and kernels::reference::isai) on RECORDED_CASES of tests/isai_util.py; sha256: see digest() in "
+                      "tests/ref_exec.py",
             "cases": {name: {"kind": cases[name][0], "sparsity_power": cases[name][1], "excess_limit": cases[name][2],
                              "n": len(cases[name][3][0]) - 1, "nnz": len(cases[name][3][1]),
                              "records": {k: fixture_record(r) for k, r in sorted(recorded[name].items())}}
                       for name in cases}}
-
-
-def made_cases():
-    return {name: (kind, power, limit, make()) for name, (kind, power, limit, make) in RECORDED_CASES.items()}
-
-
-if __name__ == "__main__":
-    # python tests/isai_util.py <isai_ref_record binary> <fixture.json>
-    import json
-    import subprocess
-    import sys
-    cases = made_cases()
-    run = subprocess.run([sys.argv[1]], input=recorder_input(cases), stdout=subprocess.PIPE, text=True, check=True)
-    with open(sys.argv[2], "w") as f:
-        json.dump(fixture_from(parse_recorder_output(run.stdout), cases), f, separators=(",", ":"))
-        f.write("\n")

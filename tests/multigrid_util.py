@@ -5,13 +5,14 @@ scalar Jacobi (core/solver/ir.cpp:186-276, reference/preconditioner/jacobi_kerne
 generate, cycle and outer loop (core/solver/multigrid.cpp:377-705) with a trace of the calls it makes.  Every numpy
 operation below is elementwise -- one rounding per product and per sum, no fused multiply-add -- and rows are walked in
 stored order, so the results are the reference executor's bit for bit; tests/golden/multigrid_ref.json (recorded from
-the reference by tools/multigrid_ref_record.cpp) pins that.  The yardstick of tests/test_multigrid_gpu.py, with the
-cases both test files and the recorder share."""
+the reference by the verb multigrid of oracle/ref_driver.cpp) pins that.  The yardstick of tests/test_multigrid_gpu.py,
+with the cases both test files and the driver share."""
 import os
 
 import numpy as np
 
 import matgen
+import ref_exec
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -474,7 +475,7 @@ class _Recording:
         return x
 
 
-# ---- cases shared by the recorder, the CPU tests and the GPU tests -----------------------------------------
+# ---- cases shared by the driver, the CPU tests and the GPU tests -------------------------------------------
 
 def read_mtx(name):
     kind, nr, nc, rows, cols, vals = matgen.read_mtx(os.path.join(HERE, "golden", name))
@@ -612,7 +613,7 @@ class _PlainJacobi:
         return x
 
 
-# ---- recorder input / output (tools/multigrid_ref_record.cpp) ----------------------------------------------
+# ---- the cases as ref_driver's verb multigrid takes them; as text for the mirror's examples ----------------
 
 def _ints(a):
     return " ".join(str(int(t)) for t in a)
@@ -645,36 +646,63 @@ def kcycle_operands(n, nrhs):
     return alpha, rho, gamma, beta, zeta, v, g, d, e
 
 
-def recorder_input():
-    lines = []
+def _dense(arrays, params, **named):
+    for name, a in named.items():
+        arr, shape = ref_exec.dense_arrays(name, a)
+        arrays.update(arr)
+        params.update(shape)
+
+
+def solve_arguments(c, m):
+    """the arrays and parameters of a whole-apply case on the matrix m, as multigrid_solve of oracle/ref_driver.cpp
+    reads them (the solve op of the verbs multigrid and pgm)"""
+    word, words = ref_exec.word, ref_exec.words
+    arrays, params = ref_exec.csr_arrays(*m)
+    _dense(arrays, params, b=right_hand_side(m[0]), x=initial_guess(m[0]))
+    arrays.update(mg_level=words("mg_level", c["mg_level"]), pre=words("smoother", c["pre"]),
+                  mid=words("smoother", c["mid"]), post=words("smoother", c["post"]))
+    params.update(cycle=word("cycle", c["cycle"]), mid_case=word("mid_case", c["mid_case"]),
+                  post_uses_pre=c["post_uses_pre"], max_levels=c["max_levels"], min_coarse_rows=c["min_coarse_rows"],
+                  coarsest=word("coarsest", c["coarsest"]), relax=c["relax"], smoother_iters=c["iters"],
+                  guess=word("guess", c["guess"]), max_iters=c["max_iters"], reduction=c["reduction"] or 0.0)
+    return arrays, params
+
+
+def queue_cases(batch):
+    """queues every case on a ref_exec.Batch -> {name: index of its result}"""
+    where = {}
     for name, (n, nrhs) in KCYCLE_CASES.items():
         alpha, rho, gamma, beta, zeta, v, g, d, e = kcycle_operands(n, nrhs)
-        lines.append(f"kcycle {name} {n} {nrhs} " + " ".join(_hex(t) for t in (alpha, rho, gamma, beta, zeta, v, g, d, e)
-                                                              if np.asarray(t).size))
+        row = lambda t: t.reshape(1, nrhs)
+        arrays, params = {}, {}
+        _dense(arrays, params, alpha=row(alpha), rho=row(rho), gamma=row(gamma), beta=row(beta), zeta=row(zeta),
+               v=v, g=g, d=d, e=e)
+        where[name] = batch.add("multigrid", arrays, op=0, **params)
     for name, make in COARSENING_CASES.items():
         m, rows, skip = make()
-        lines.append(f"coarsen {name} {int(skip)} {len(rows)} {_ints(rows)} {_matrix_text(m)}")
+        arrays, params = ref_exec.csr_arrays(*m)
+        arrays["coarse_rows"] = np.asarray(rows, np.int32)
+        where[name] = batch.add("multigrid", arrays, op=1, skip_sorting=skip, **params)
     for name, (mat, sweeps, zero, relax) in SMOOTHER_CASES.items():
         m = case_matrix(mat)
-        lines.append(f"smooth {name} {sweeps} {int(zero)} {float(relax).hex()} {_matrix_text(m)} "
-                     f"{_hex(right_hand_side(m[0]))} {_hex(initial_guess(m[0]))}")
+        arrays, params = ref_exec.csr_arrays(*m)
+        _dense(arrays, params, b=right_hand_side(m[0]), x=initial_guess(m[0]))
+        where[name] = batch.add("multigrid", arrays, op=2, sweeps=sweeps, zero_guess=zero, relax=relax, **params)
     for name, c in SOLVE_CASES.items():
-        m = case_matrix(c["matrix"])
-        word = lambda names: " ".join([str(len(names))] + ["null" if t is None else t for t in names])
-        lines.append(f"solve {name} {c['cycle']} {c['mid_case']} {int(c['post_uses_pre'])} {c['max_levels']} "
-                     f"{c['min_coarse_rows']} {c['coarsest']} {float(c['relax']).hex()} {c['iters']} {c['guess']} "
-                     f"{c['max_iters']} {float(c['reduction'] or 0.0).hex()} {word(c['mg_level'])} {word(c['pre'])} "
-                     f"{word(c['mid'])} {word(c['post'])} {_matrix_text(m)} {_hex(right_hand_side(m[0]))} "
-                     f"{_hex(initial_guess(m[0]))}")
-    return "\n".join(lines) + "\n"
+        arrays, params = solve_arguments(c, case_matrix(c["matrix"]))
+        where[name] = batch.add("multigrid", arrays, op=3, **params)
+    return where
 
 
-def fixture_from(records):
-    """the committed fixture from the parsed recorder output: short arrays in full, long ones as count + digest"""
-    import cb_gmres_util as cu
-    fix = {"source": "tools/multigrid_ref_record.cpp over the reference executor; cases: tests/multigrid_util.py"}
+def case_arrays(results, where):
+    return {name: results[i] for name, i in where.items()}
+
+
+def fixture_from(records, verb="multigrid"):
+    """the committed fixture from the driver's arrays: short arrays in full, long ones as count + digest"""
+    fix = {"source": f"oracle/ref_driver.cpp, verb {verb}, over the reference executor; cases: tests/{verb}_util.py"}
     for name, arrays in records.items():
-        fix[name] = {what: cu.as_record(items, integers=what.endswith(INTEGER_RECORDS)) for what, items in arrays.items()}
+        fix[name] = {what: ref_exec.as_record(a) for what, a in arrays.items()}
     return fix
 
 
@@ -723,7 +751,7 @@ def restated_solve(name):
 
 
 def restated_records():
-    """everything the recorder prints, from the restatement: {case: {what: array}}"""
+    """everything the driver returns, from the restatement: {case: {what: array}}"""
     out = {}
     for cases, fn in ((KCYCLE_CASES, restated_kcycle), (COARSENING_CASES, restated_coarsening),
                       (SMOOTHER_CASES, restated_smoother), (SOLVE_CASES, restated_solve)):
@@ -736,8 +764,10 @@ INTEGER_RECORDS = ("row_ptrs", "col_idxs", "iterations", "levels", "is_stop")
 
 
 def record_matches(rec, what, got):
-    import cb_gmres_util as cu
-    return cu.matches(rec, got, integers=what.endswith(INTEGER_RECORDS))
+    return ref_exec.matches(rec, got, integers=what.endswith(INTEGER_RECORDS))
+
+
+V_CYCLE_PRECONDITIONER = _case(matrix=None, max_iters=1, guess="zero")
 
 
 def dot(a, b):
@@ -752,7 +782,7 @@ def preconditioned_cg(m, b, max_iters, reduction):
     """solver::Cg (core/solver/cg.cpp) on one right-hand side from x = 0, preconditioned by one V-cycle of the
     three-level hierarchy of the "direct" cases with a zero initial guess; ResidualNorm(reduction, rhs_norm).
     -> (x, iterations)"""
-    mg, _, _ = restated(_case(matrix=None, max_iters=1, guess="zero"), matrix=m)
+    mg, _, _ = restated(V_CYCLE_PRECONDITIONER, matrix=m)
     x = np.zeros_like(b)
     r = b.copy()
     z, p, q = np.zeros_like(b), np.zeros_like(b), np.zeros_like(b)

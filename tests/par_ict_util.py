@@ -139,7 +139,7 @@ def dense_to_csr(a):
     return xu.dense_to_csr(a)
 
 
-# ---- results recorded from the reference executor (tools/par_ict_ref_record.cpp -> golden/par_ict_ref.json) ---------
+# ---- results recorded from the reference executor (ref_driver's verb par_ict -> golden/par_ict_ref.json) -----------
 
 def _ani1_with_some_diagonals_halved():
     """ani1 with the diagonal entry of every fifth row halved: not positive definite any more, so both sweeps of
@@ -161,10 +161,15 @@ RECORDED_CASES = {
 }
 RECORDED_LIMITS = pu.RECORDED_LIMITS
 
-recorder_input = pu.recorder_input
-parse_recorder_output = pu.parse_recorder_output
-digest = pu.digest
-fixture_record = pu.fixture_record
+case_arrays = pu.case_arrays
+
+
+def made_cases():
+    return {name: make() for name, make in RECORDED_CASES.items()}
+
+
+def queue_cases(batch):
+    return pu.queue_cases(batch, "par_ict", made_cases())
 
 
 def group_records(arrays):
@@ -173,24 +178,5 @@ def group_records(arrays):
     return {k: ([x[0] for x in r] if k.endswith("/nnz") else r) for k, r in out.items()}
 
 
-def fixture_from(recorded, cases):
-    return {"source": "tools/par_ict_ref_record.cpp over the reference executor (ParIct::generate and "
-                      "kernels::reference::par_ict_factorization) on RECORDED_CASES of tests/par_ict_util.py; "
-                      "generate/<select>/<fill_in_limit>/<iterations>/<factor>; sha256: see digest() in "
-                      "tests/par_ilut_util.py",
-            "cases": {name: {"n": len(cases[name][0]) - 1, "nnz": len(cases[name][1]),
-                             "records": {k: fixture_record(len(cases[name][0]) - 1, k, r)
-                                         for k, r in group_records(recorded[name]).items()}}
-                      for name in cases}}
-
-
-if __name__ == "__main__":
-    # python tests/par_ict_util.py <par_ict_ref_record binary> <fixture.json>
-    import json
-    import subprocess
-    import sys
-    cases = {name: make() for name, make in RECORDED_CASES.items()}
-    run = subprocess.run([sys.argv[1]], input=recorder_input(cases), capture_output=True, text=True, check=True)
-    with open(sys.argv[2], "w") as f:
-        json.dump(fixture_from(parse_recorder_output(run.stdout), cases), f, separators=(",", ":"))
-        f.write("\n")
+def fixture_from(recorded):
+    return pu.fixture_from(recorded, "par_ict", made_cases(), group_records)

@@ -10,8 +10,10 @@ from bisect import bisect_left, bisect_right
 import numpy as np
 
 import ilu_exact_util as xu
+import ref_exec
 import spgemm_util as su
 from ilu_exact_util import _arrays, _div, _lists
+from ref_exec import digest
 
 SENTINEL = su.SENTINEL
 # core/factorization/par_ilut_kernels.hpp:99-100
@@ -225,7 +227,7 @@ def dense_to_csr(a):
     return xu.dense_to_csr(a)
 
 
-# ---- results recorded from the reference executor (tools/par_ilut_ref_record.cpp -> golden/par_ilut_ref.json) -------
+# ---- results recorded from the reference executor (ref_driver's verb par_ilut -> golden/par_ilut_ref.json) ---------
 
 def _golden_mtx(name):
     import os
@@ -261,35 +263,40 @@ RECORDED_LIMITS = (0.75, 1.2, 2.0)
 FULL_ARRAYS_UP_TO = 64       # rows: the fixture holds whole arrays up to here, SHA-256 digests beyond
 
 
-def recorder_input(cases):
-    """the stdin of tools/par_ilut_ref_record.cpp for {name: matrix}"""
-    out = []
-    for name, m in cases.items():
-        rp, ci, v = m
-        out.append(f"matrix {name} {len(rp) - 1} {len(ci)}")
-        out.append(" ".join(str(int(x)) for x in rp))
-        out.append(" ".join(str(int(x)) for x in ci))
-        out.append(" ".join(float(x).hex() for x in v))
-    return "\n".join(out) + "\n"
+def made_cases():
+    return {name: make() for name, make in RECORDED_CASES.items()}
 
 
-def parse_recorder_output(text):
-    """{case: {"<section>/<array>": numpy array}} from the recorder's stdout"""
+def queue_cases(batch, verb="par_ilut", cases=None):
+    """queues what the fixture records of every matrix on a ref_exec.Batch: generate for approximate_select 0 / 1,
+    fill_in_limit 0.75 / 1.2 / 2.0 and 1 ... 5 iterations, then each kernel alone on the intermediate matrices of
+    the first iteration -> [(case, section, index of the result, whether the fixture keeps the factors)]"""
+    where = []
+    for name, (rp, ci, v) in (made_cases() if cases is None else cases).items():
+        arrays, size = ref_exec.csr_arrays(len(rp) - 1, len(rp) - 1, rp, ci, v)
+        for select in ("exact", "approx"):
+            for limit in RECORDED_LIMITS:
+                for iterations in range(1, 6):
+                    i = batch.add(verb, arrays, op=0, iterations=iterations, fill_in_limit=limit,
+                                  approximate_select=select == "approx", **size)
+                    where.append((name, f"generate/{select}/{limit:g}/{iterations}", i, iterations in (1, 5)))
+        where.append((name, "kernels", batch.add(verb, arrays, op=1, **size), True))
+    return where
+
+
+def case_arrays(results, where):
+    """{case: {"<section>/<array>": numpy array}} from the driver's results: the number of entries of the factors
+    of every generate, the factors after 1 and 5 iterations"""
     res = {}
-    for line in text.splitlines():
-        t = line.split()
-        case, section, what, count = t[0], t[1], t[2], int(t[3])
-        assert len(t) == 4 + count, line[:80]
-        if what.endswith("vals") or what in ("select", "approx"):
-            arr = np.array([float.fromhex(x) for x in t[4:]], np.float64)
-        else:
-            arr = np.array([int(x) for x in t[4:]], np.int32)
-        res.setdefault(case, {})[f"{section}/{what}"] = arr
+    for name, section, i, factors in where:
+        for what, a in results[i].items():
+            if factors or what == "nnz":
+                res.setdefault(name, {})[f"{section}/{what}"] = a
     return res
 
 
 def group_records(arrays):
-    """the arrays of one case, as parse_recorder_output gives them, grouped: the three arrays of a CSR matrix under
+    """the arrays of one case, as case_arrays gives them, grouped: the three arrays of a CSR matrix under
     the matrix' name, the entry counts of 1 ... 5 iterations of one configuration as one list of pairs"""
     out = {}
     for key in sorted(arrays):
@@ -304,14 +311,6 @@ def group_records(arrays):
             else:
                 out[key] = arrays[key]
     return out
-
-
-def digest(rec):
-    """SHA-256 of the bytes of an array (little-endian int32 / float64), of a CSR matrix those of row_ptrs, col_idxs
-    and vals one after the other"""
-    import hashlib
-    parts = [rec[k] for k in ("row_ptrs", "col_idxs", "vals")] if isinstance(rec, dict) else [rec]
-    return hashlib.sha256(b"".join(np.ascontiguousarray(p).tobytes() for p in parts)).hexdigest()
 
 
 def _items(arr):
@@ -336,23 +335,15 @@ def fixture_record(n, key, rec):
     return out
 
 
-def fixture_from(recorded, cases):
-    return {"source": "tools/par_ilut_ref_record.cpp over the reference executor (ParIlut::generate and "
-                      "kernels::reference::par_ilut_factorization) on RECORDED_CASES of tests/par_ilut_util.py; "
-                      "generate/<select>/<fill_in_limit>/<iterations>/<factor>; sha256: see digest() there",
+def fixture_from(recorded, verb="par_ilut", cases=None, group=None):
+    cases = made_cases() if cases is None else cases
+    group = group or group_records
+    klass = {"par_ilut": "ParIlut", "par_ict": "ParIct"}[verb]
+    return {"source": f"oracle/ref_driver.cpp, verb {verb}, over the reference executor ({klass}::generate and "
+                      f"kernels::reference::{verb}_factorization) on RECORDED_CASES of tests/{verb}_util.py; "
+                      "generate/<select>/<fill_in_limit>/<iterations>/<factor>; sha256: see digest() in "
+                      "tests/ref_exec.py",
             "cases": {name: {"n": len(cases[name][0]) - 1, "nnz": len(cases[name][1]),
                              "records": {k: fixture_record(len(cases[name][0]) - 1, k, r)
-                                         for k, r in group_records(recorded[name]).items()}}
+                                         for k, r in group(recorded[name]).items()}}
                       for name in cases}}
-
-
-if __name__ == "__main__":
-    # python tests/par_ilut_util.py <par_ilut_ref_record binary> <fixture.json>
-    import json
-    import subprocess
-    import sys
-    cases = {name: make() for name, make in RECORDED_CASES.items()}
-    run = subprocess.run([sys.argv[1]], input=recorder_input(cases), capture_output=True, text=True, check=True)
-    with open(sys.argv[2], "w") as f:
-        json.dump(fixture_from(parse_recorder_output(run.stdout), cases), f, separators=(",", ":"))
-        f.write("\n")

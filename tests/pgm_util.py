@@ -4,19 +4,21 @@
 reference/multigrid/pgm_kernels.cpp:67-348, csr::transpose, csr::spgeam by reference/components/csr_spgeam.hpp:58-104
 and csr::extract_diagonal): literal sequential loops over the rows, in place on agg, a stable sort and left-to-right
 sums for the coarse matrix.  Python floats are IEEE doubles and every statement rounds once, so the results are the
-reference executor's bit for bit; tests/golden/pgm_ref.json (recorded by tools/pgm_ref_record.cpp) pins that.
+reference executor's bit for bit; tests/golden/pgm_ref.json (recorded by the verb pgm of oracle/ref_driver.cpp) pins
+that.
 
 `generate(m, ..., parallel=True)` is the form the device kernels compute: every sweep reads a snapshot of agg taken
 when it starts, match_edge likewise, and the default assign_to_exist_agg is the static choice p(r) of every row
 followed by ceil(log2 n) rounds of pointer jumping.  tests/test_pgm_reference.py holds the two equal on every case and
 on seeded random matrices -- the order-independence argument of DESIGN.md 4.27, tested.
 
-Also the cases both test files and the recorder share, the recorder's input and the fixture writer."""
+Also the cases both test files and the driver share, the driver's input and the fixture writer."""
 import os
 
 import numpy as np
 
 import multigrid_util as mu
+import ref_exec
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 csr = mu.csr
@@ -402,12 +404,6 @@ def star_plus_ring(n):
     return from_dense_pattern(n, e)
 
 
-def stencil_system(n):
-    """the matrix of the SolvesStencilSystem cases (reference/test/solver/multigrid_kernels.cpp:1247-1262 through
-    tests/golden/multigrid.json): tridiagonal 2, -1"""
-    return path(n)
-
-
 # name -> (matrix maker, generate's keyword arguments); deterministic is run both ways by the tests
 CASES = {
     "reference_5x5": (reference_5x5, dict(max_iterations=2, max_unassigned_ratio=0.1, skip_sorting=True)),
@@ -473,8 +469,7 @@ INTEGER_RECORDS = ("agg", "num_agg", "row_ptrs", "col_idxs", "iterations", "leve
 
 
 def record_matches(rec, what, got):
-    import cb_gmres_util as cu
-    return cu.matches(rec, got, integers=what.endswith(INTEGER_RECORDS))
+    return ref_exec.matches(rec, got, integers=what.endswith(INTEGER_RECORDS))
 
 
 # ---- whole solves: Multigrid with Pgm on every level -------------------------------------------------------
@@ -526,9 +521,34 @@ def restated_solve(name):
     return {"x": x, "iterations": [it], "levels": [lvl.coarse[0] for lvl in mg.mg_level_list]}
 
 
-# ---- recorder input / output (tools/pgm_ref_record.cpp) ----------------------------------------------------
+# ---- the cases as ref_driver's verb pgm takes them; as text for examples/pgm_multigrid.cpp ----------------
+
+def _pgm_parameters(kw, deterministic):
+    return dict(pgm_max_iterations=kw.get("max_iterations", 15),
+                pgm_max_unassigned_ratio=kw.get("max_unassigned_ratio", 0.05), pgm_deterministic=deterministic)
+
+
+def queue_cases(batch):
+    """queues every case on a ref_exec.Batch -> {name: index of its result}"""
+    where = {}
+    for name, (_, kw) in CASES.items():
+        arrays, params = ref_exec.csr_arrays(*case_matrix(name))
+        for det in (0, 1):
+            where[f"{name}/det{det}"] = batch.add("pgm", arrays, op=0, skip_sorting=kw.get("skip_sorting", False),
+                                                  **_pgm_parameters(kw, det), **params)
+    for name, c in SOLVE_CASES.items():
+        arrays, params = mu.solve_arguments(c, solve_matrix(c["matrix"]))
+        where[name] = batch.add("pgm", arrays, op=1, **_pgm_parameters(c["pgm"], c["pgm"].get("deterministic", False)),
+                                **params)
+    return where
+
+
+case_arrays = mu.case_arrays
+
 
 def recorder_input():
+    """the cases as text, one per line: the stdin of examples/pgm_multigrid.cpp in its `run` mode, which prints what
+    the driver returns as "<case> <what> <count> <items...>" lines (parse_example_output)"""
     lines = []
     for name, (_, kw) in CASES.items():
         m = case_matrix(name)
@@ -549,6 +569,22 @@ def recorder_input():
     return "\n".join(lines) + "\n"
 
 
+def parse_example_output(text):
+    """{case: {what: [items as written]}} from the lines "<case> <what> <count> <items...>" the example prints"""
+    out = {}
+    for line in text.splitlines():
+        name, what, count, *items = line.split()
+        assert len(items) == int(count), (name, what)
+        out.setdefault(name, {})[what] = items
+    return out
+
+
+def arrays_from_text(records):
+    """the parsed lines as the arrays case_arrays gives: integers as int64, doubles from their hexadecimal spelling"""
+    return {name: {what: np.array([int(t) for t in items], np.int64) if what.endswith(INTEGER_RECORDS)
+                   else ref_exec.unhex(items) for what, items in arrays.items()} for name, arrays in records.items()}
+
+
 def restated_records():
     out = {f"{name}/det{det}": level_records(restated(name, bool(det))) for name in CASES for det in (0, 1)}
     for name in SOLVE_CASES:
@@ -557,11 +593,7 @@ def restated_records():
 
 
 def fixture_from(records):
-    import cb_gmres_util as cu
-    fix = {"source": "tools/pgm_ref_record.cpp over the reference executor; cases: tests/pgm_util.py"}
-    for name, arrays in records.items():
-        fix[name] = {what: cu.as_record(items, integers=what.endswith(INTEGER_RECORDS)) for what, items in arrays.items()}
-    return fix
+    return mu.fixture_from(records, "pgm")
 
 
 dump_fixture = mu.dump_fixture

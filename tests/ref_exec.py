@@ -8,7 +8,10 @@ bit for bit.  One process serves a whole batch: collect the cases of a module
 with Batch.add(), run them once, index the results by the returned number.
 """
 import hashlib
+import importlib
+import json
 import os
+import re
 import struct
 import subprocess
 import tempfile
@@ -26,6 +29,25 @@ _DTYPES = {v: k for k, v in _CODES.items()}
 
 # format numbers of the driver's `fmt` parameter
 CSR, ELL, SELLP, HYBRID, COO, FBCSR, DENSE = range(7)
+# the words of the cases as the numbers the driver's parameters carry: word("cycle", "w") == 2
+WORDS = {"baseline": ("rhs_norm", "initial_resnorm", "absolute"),
+         "storage": ("keep", "reduce1", "reduce2", "integer", "ireduce1", "ireduce2"),
+         "isai": ("lower", "upper", "general", "spd"),
+         "cycle": ("v", "f", "w"),
+         "mid_case": ("both", "post_smoother", "pre_smoother", "standalone"),
+         "coarsest": ("identity", "direct", "cg"),
+         "guess": ("zero", "rhs", "provided"),
+         "smoother": ("null", "eye", "jacobi"),
+         "mg_level": ("halve", "all_rows", "pgm")}
+
+
+def word(kind, w):
+    return WORDS[kind].index(w)
+
+
+def words(kind, ws):
+    """a list of words of any length (None: "null") as the i32 array the driver takes"""
+    return np.array([word(kind, "null" if w is None else w) for w in ws], np.int32)
 
 
 def reference_dir():
@@ -231,3 +253,126 @@ def assert_bits(got, want, what=""):
         hexs = (lambda x: float(x).hex()) if g.dtype.kind == "f" else str
         raise AssertionError(f"{what}: {int(bad.sum())} of {g.size} differ, first at {i}: "
                              f"got {hexs(g[i])}, reference {hexs(w[i])}")
+
+
+# ---- the JSON fixtures recorded from the driver (tests/golden/<family>_ref.json) and the one rule that compares
+# an array with what such a fixture keeps of it
+
+FAMILIES = ("par_ilut", "par_ict", "isai", "cb_gmres", "multigrid", "pgm")
+LONG = 32   # arrays up to this many entries are kept in full, longer ones as their count, digest and first entries
+_HEX = re.compile(r"-?0x[0-9a-f.]+p[+-]\d+$")
+
+
+def unhex(items):
+    return np.array([float.fromhex(t) for t in items], np.float64)
+
+
+def csr_parts(m):
+    """a Csr given as (row_ptrs, col_idxs, vals) or as a dict of these"""
+    return m if isinstance(m, dict) else dict(zip(("row_ptrs", "col_idxs", "vals"), m))
+
+
+def digest(rec):
+    """SHA-256 of the bytes of an array as it is (little-endian int32 / float64), of a Csr those of row_ptrs,
+    col_idxs and vals one after the other"""
+    parts = [rec] if isinstance(rec, np.ndarray) else [csr_parts(rec)[k] for k in ("row_ptrs", "col_idxs", "vals")]
+    return hashlib.sha256(b"".join(np.ascontiguousarray(p).tobytes() for p in parts)).hexdigest()
+
+
+def as_record(a):
+    """what a fixture keeps of an array: doubles as hexadecimal floats (the committed files spell them as C's %a
+    does, a file written again as Python does: compare by value), integers as they are; a long array as the
+    SHA-256 of its bits (float64 / int64, little-endian) with its count and its first four entries"""
+    a = np.ascontiguousarray(a).reshape(-1)
+    integers = a.dtype.kind != "f"
+    bits = a.astype("<i8" if integers else "<f8")
+    if a.size <= LONG:
+        return [int(t) for t in bits] if integers else [float(t).hex() for t in bits]
+    return {"count": int(a.size), "sha256": hashlib.sha256(bits.tobytes()).hexdigest(),
+            "head": [int(t) for t in bits[:4]] if integers else [float(t).hex() for t in bits[:4]]}
+
+
+def _same_items(items, a):
+    """a list of integers or of hexadecimal floats holds the array's values: doubles by their bits, never by spelling"""
+    a = np.asarray(a).reshape(-1)
+    if len(items) != a.size:
+        return False
+    if a.dtype.kind == "f":
+        return all(isinstance(t, str) for t in items) and bits_equal(unhex(items), a.astype(np.float64))
+    return [int(t) for t in a] == list(items)
+
+
+def matches(rec, got, integers=None):
+    """`got` is the recorded array, bit for bit.  rec is what as_record() keeps, or -- the layout of the par_ilut,
+    par_ict and isai fixtures -- {"sha256": digest(got)} with "items" for a short array and "nnz" for a Csr, which
+    `got` then gives as (row_ptrs, col_idxs, vals).  integers: take `got` as integers (default: by its dtype)."""
+    if isinstance(rec, dict) and "count" not in rec:
+        if digest(got) != rec["sha256"]:
+            return False
+        if "nnz" in rec:
+            parts = csr_parts(got)
+            return rec["nnz"] == len(parts["vals"]) and \
+                ("items" not in rec or (set(rec["items"]) == set(parts)
+                                        and all(_same_items(rec["items"][k], parts[k]) for k in parts)))
+        return "items" not in rec or _same_items(rec["items"], got)
+    got = np.ascontiguousarray(got).reshape(-1)
+    if integers is None:
+        integers = got.dtype.kind != "f"
+    got = got.astype(np.int64 if integers else np.float64)
+    if isinstance(rec, dict):
+        return rec["count"] == got.size and rec["sha256"] == as_record(got)["sha256"] and _same_items(rec["head"], got[:4])
+    return _same_items(rec, got)
+
+
+def fixture_difference(fresh, committed, at=""):
+    """where two fixtures differ, or None: the same keys both ways, lists of the same length, every leaf equal --
+    a double written as a hexadecimal float by its value, whichever way it is spelled"""
+    if isinstance(fresh, dict) and isinstance(committed, dict):
+        if set(fresh) != set(committed):
+            return f"{at}: keys {sorted(set(fresh) ^ set(committed))[:6]} are on one side only"
+        pairs = [(f"{at}/{k}", fresh[k], committed[k]) for k in fresh]
+    elif isinstance(fresh, (list, tuple)) and isinstance(committed, (list, tuple)):
+        if len(fresh) != len(committed):
+            return f"{at}: {len(fresh)} entries, committed {len(committed)}"
+        pairs = [(f"{at}[{i}]", a, b) for i, (a, b) in enumerate(zip(fresh, committed))]
+    else:
+        both_hex = isinstance(fresh, str) and isinstance(committed, str) and _HEX.match(fresh) and _HEX.match(committed)
+        same = float.fromhex(fresh).hex() == float.fromhex(committed).hex() if both_hex else \
+            type(fresh) is type(committed) and fresh == committed
+        return None if same else f"{at}: {fresh!r}, committed {committed!r}"
+    return next((d for d in (fixture_difference(a, b, p) for p, a, b in pairs) if d is not None), None)
+
+
+def recorded(family):
+    """The fixture of a family as the driver gives it now, in one driver process.  <family>_util.py has the rest:
+    queue_cases(batch) -> where each case's result is, case_arrays(results, where) -> {case: {what: ndarray}} under
+    the fixture's names, fixture_from(arrays) and, where the file has a layout of its own, dump_fixture(fixture, path)."""
+    util = importlib.import_module(family + "_util")
+    batch = Batch()
+    where = util.queue_cases(batch)
+    results = batch.run()
+    failed = [r["error"] for r in results if "error" in r]
+    assert not failed, failed[:3]
+    return util.fixture_from(util.case_arrays(results, where))
+
+
+def difference_from_driver(family, committed):
+    """where a committed fixture differs from what the driver gives now, or None.  The committed "source" is not
+    compared, it names the program that wrote those bytes; the one a file written now would carry must name the
+    driver and the verb"""
+    fresh = recorded(family)
+    if f"oracle/ref_driver.cpp, verb {family}," not in fresh["source"]:
+        return f"source: {fresh['source']!r} does not name the driver and its verb"
+    return fixture_difference({**fresh, "source": committed["source"]}, committed)
+
+
+def record(family, path=None):
+    """Write a family's fixture again (never to make a test pass: the driver and the committed file must agree):
+    python -c "import sys; sys.path.insert(0, 'tests'); import ref_exec; ref_exec.record('pgm')" """
+    path = path or os.path.join(REPO_ROOT, "tests", "golden", family + "_ref.json")
+    util = importlib.import_module(family + "_util")
+    if hasattr(util, "dump_fixture"):
+        return util.dump_fixture(recorded(family), path)
+    with open(path, "w") as f:
+        json.dump(recorded(family), f, separators=(",", ":"))
+        f.write("\n")

@@ -1,26 +1,23 @@
 """CPU side of CB-GMRES.  The numpy restatement (tests/cb_gmres_util.py) in its "truncate" + sequential mode is pinned, bit
-for bit, to results recorded from the reference executor (tests/golden/cb_gmres_ref.json, written by
-tools/cb_gmres_ref_record.cpp): the outputs of the four kernels and whole solves for every storage type.  Where the
-reference executor's objects and a compiler are present the recorder is built and run again, so the fixture cannot go
-stale.  Then what the GPU tests rely on is checked here, without a device: the case set takes 0, 1 and 2
+for bit, to results recorded from the reference executor (tests/golden/cb_gmres_ref.json, written by the verb cb_gmres of
+oracle/ref_driver.cpp): the outputs of the four kernels and whole solves for every storage type.  Wherever that driver
+is, it runs again and the fixture is compared with what it gives, so the fixture cannot go stale.  Then what the GPU tests rely on is checked here, without a device: the case set takes 0, 1 and 2
 re-orthogonalisation passes and a forced reset, no loop test sits near eta, and the iteration counts do not move by more
 than one when the sums are grouped.
 
 The fixture keeps arrays of up to 32 entries in full, as hexadecimal floats (the basis as raw storage integers); a longer
-array is kept as its count, the SHA-256 of its bits and its first four entries (cb_gmres_util.as_record), which keeps the
+array is kept as its count, the SHA-256 of its bits and its first four entries (ref_exec.as_record), which keeps the
 file small.  The comparison is bit for bit either way, but a mismatch in a long array is only reported, not located: to
-find the entry, run tools/cb_gmres_ref_record.cpp on cb_gmres_util.recorder_input() and compare its full output."""
+find the entry, compare with the arrays of cb_gmres_util.case_arrays() for a ref_exec.Batch of queue_cases()."""
 import functools
-import glob
 import json
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import cb_gmres_util as cu
+import ref_exec
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -31,12 +28,12 @@ KERNELS = [f"{name}/{storage}" for name in cu.KERNEL_CASES for storage in cu.STO
 
 def same(rec, got):
     """the recorded doubles (hexadecimal floats, or count + digest of a long array) are these, bit for bit"""
-    return cu.matches(rec, np.asarray(got, np.float64))
+    return ref_exec.matches(rec, np.asarray(got, np.float64))
 
 
 def test_the_fixture_describes_the_cases_of_the_restatement():
     assert list(REF["solves"]) == SOLVES and list(REF["kernels"]) == KERNELS
-    assert "tools/cb_gmres_ref_record.cpp" in REF["source"]
+    assert "oracle/ref_driver.cpp, verb cb_gmres," in REF["source"]
     assert os.path.getsize(os.path.join(HERE, "golden", "cb_gmres_ref.json")) < 1 << 20
 
 
@@ -68,7 +65,7 @@ def test_known_answers_of_the_reference_s_tests(key):
     tol = {"keep": 1e-14, "integer": 1e-14, "reduce1": 1e-6, "ireduce1": 1e-6, "reduce2": 1e-2, "ireduce2": 1e-2}[storage]
     if name == "medium_k4":
         tol = np.sqrt(tol)
-    x = cu.unhex(REF["solves"][key]["x"])       # (these systems have 3 to 6 rows: kept in full)
+    x = ref_exec.unhex(REF["solves"][key]["x"])       # (these systems have 3 to 6 rows: kept in full)
     want = np.array(case["expect_x"])
     assert np.linalg.norm(x - want) <= 100 * tol * np.linalg.norm(want)
 
@@ -88,7 +85,7 @@ def test_restated_kernels_equal_the_recorded_ones_bit_for_bit(key):
     rn, rnc, nxt, fin = cu.restart(residual, basis, kd, an)
     assert same(rec["restart/residual_norm"], rn) and same(rec["restart/residual_norm_collection"], rnc)
     assert same(rec["restart/next"], nxt)
-    assert cu.matches(rec["restart/basis"], basis.raw(), integers=True)
+    assert ref_exec.matches(rec["restart/basis"], basis.raw(), integers=True)
     hess = np.zeros((kd + 1, kd * nrhs))
     buf = np.zeros((kd + 1, nrhs))
     for s in range(c["steps"]):
@@ -102,11 +99,11 @@ def test_restated_kernels_equal_the_recorded_ones_bit_for_bit(key):
         assert same(rec[at + "hessenberg_iter"], h_iter), at
         assert same(rec[at + "arnoldi_norm"], an), at
         assert same(rec[at + "residual_norm"], rn) and same(rec[at + "residual_norm_collection"], rnc), at
-        assert cu.matches(rec[at + "final_iter_nums"], fin, integers=True), at
+        assert ref_exec.matches(rec[at + "final_iter_nums"], fin, integers=True), at
     assert same(rec["givens_sin"], gsin) and same(rec["givens_cos"], gcos)
     y, before = cu.solve_krylov(rnc, basis, hess, fin)
     assert same(rec["solve_krylov/y"], y) and same(rec["solve_krylov/before_preconditioner"], before)
-    assert cu.matches(rec["basis"], basis.raw(), integers=True)
+    assert ref_exec.matches(rec["basis"], basis.raw(), integers=True)
     if cu.is_scaled(storage):
         assert same(rec["scalars"], basis.scalars)
 
@@ -140,6 +137,8 @@ def test_the_fixture_knows_which_iteration_counts_survive_a_reordered_sum(key):
     is held to +-1 of the last of these, and cd7_k30 and cd8_k30_r6, which qualify, stand in for it."""
     rec = REF["solves"][key]
     assert rec["reordered_iterations"] == cu.reordered_counts(*key.split("/"))
+    # what they are held against: the same solve with sequential sums, which the driver pins in "truncate" mode
+    assert rec["rne_iterations"] == cu.restated_solve(*key.split("/"), "rne")[1]["iterations"]
     assert cu.count_is_stable(rec) == (key != "cd8_k30/reduce2"), (key, rec["rne_iterations"], rec["reordered_iterations"])
 
 
@@ -151,25 +150,42 @@ def test_half_conversions():
     assert list(r[:3]) == [1.0, 1.0, 1.0 + 2.0 ** -9] and r[3] != 0.0 and r[4] == 2.0 ** -24 and r[5] == np.inf
 
 
-def test_the_recorder_reproduces_the_fixture(tmp_path):
-    """tools/cb_gmres_ref_record.cpp, built against the reference executor's objects where they and a compiler are
-    present, writes the fixture as it is committed"""
-    objs = sorted(glob.glob(os.path.join(ROOT, "oracle", "_ref", "obj", "**", "*.o"), recursive=True))
-    inc = os.path.join(ROOT, "oracle", "_ref", "include")
-    where = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "-f", "ref.mk", "ref-where"],
-                           capture_output=True, text=True)
-    ref_src = where.stdout.strip()
-    if not objs or shutil.which("g++") is None or not os.path.isdir(os.path.join(ref_src, "core", "solver")):
-        pytest.skip("the reference executor's objects or its headers are not on this machine")
-    exe = tmp_path / "cb_gmres_ref_record"
-    r = subprocess.run(["g++", "-std=c++14", "-O1", "-fPIC", "-ffp-contract=off", "-pthread", "-w", f"-I{inc}",
-                        f"-I{ref_src}/include", f"-I{ref_src}", os.path.join(ROOT, "tools", "cb_gmres_ref_record.cpp"),
-                        *objs, "-o", str(exe), "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    run = subprocess.run([str(exe)], input=cu.recorder_input(), capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-3000:]
-    fresh = cu.fixture_from(cu.parse_recorder_output(run.stdout))
-    assert json.loads(json.dumps(fresh)) == REF
+def test_compress_stores_what_a_basis_write_stores():
+    """cu.compress, which the GPU tests compare the device's stored basis with, is the write the pinned kernels make:
+    a half through cu.float_to_half_bits in either mode, an integer as the quotient by the scalar, cut"""
+    v = np.array([1.0, 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, -2.5e-5, 6.0e-8, -0.0, 0.333251953125, -0.75])
+    for mode in ("truncate", "rne"):
+        assert np.array_equal(cu.compress(v, "reduce2", half=mode).view(np.uint16), cu.float_to_half_bits(v, mode))
+    assert np.array_equal(cu.compress(v, "keep"), v.view(np.int64))
+    assert np.array_equal(cu.compress(v, "reduce1"), v.astype(np.float32).view(np.int32))
+    for storage in ("integer", "ireduce1", "ireduce2"):
+        scalar = cu.correction(storage)
+        assert np.array_equal(cu.compress(v, storage, scalar), np.trunc(v / scalar).astype(np.int64))
+
+
+def test_the_device_s_sum_is_a_reordering_of_the_sequential_one():
+    """cu.device_sum against cu.ssum in row order, which the driver pins: equal where every partial sum is exact
+    (small integers), and within 2 gamma_(n-1) sum|p| otherwise -- each of two sums of n terms, in whatever order, is
+    within gamma_(n-1) sum|p| of the exact one, gamma_k = k u / (1 - k u), u = 2^-53"""
+    rng = np.random.default_rng(7)
+    for n in (1, 63, 1025, 5000):           # one lane, one wave, more than one workgroup at 2 rows per lane
+        for per_lane in (2, 4, 8):
+            for dot in (False, True):
+                whole = rng.integers(-1000, 1000, n).astype(np.float64)
+                assert cu.device_sum(whole, per_lane, dot) == cu.ssum(whole) == whole.sum()
+                assert cu.ssum(whole, ("device", per_lane), dot) == cu.device_sum(whole, per_lane, dot)
+                p = rng.standard_normal(n) * 10.0 ** rng.integers(-3, 4, n)
+                gamma = (n - 1) * 2.0 ** -53 / (1 - (n - 1) * 2.0 ** -53)
+                assert abs(cu.device_sum(p, per_lane, dot) - cu.ssum(p)) <= 2 * gamma * np.abs(p).sum()
+
+
+def test_the_driver_reproduces_the_fixture():
+    """oracle/_ref/ref_driver, the reference executor itself, gives the fixture as it is committed: every recorded array
+    of every case, the keys compared both ways.  One driver process; a missing driver fails wherever the reference or
+    oracle/_ref/ is."""
+    if ref_exec.may_skip():
+        pytest.skip("neither the reference nor oracle/_ref/ is on this machine")
+    assert ref_exec.difference_from_driver("cb_gmres", REF) is None
 
 
 # ---- the C ABI and the Python layer, without a device -----------------------------------------------------------------

@@ -40,7 +40,6 @@ def same_csr(got, want):
 
 
 def matches(rec, got):
-    got = iu.as_record(got) if isinstance(got, tuple) else got
     return iu.digest(got) == rec["sha256"]
 
 

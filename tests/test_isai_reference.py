@@ -1,14 +1,12 @@
 """CPU side of ISAI.  The plain-Python restatement (tests/isai_util.py) is pinned to the reference twice: to the answers
 the reference's own tests expect (tests/golden/isai.json and the isai_*.mtx files, the reference's tolerance) and, bit for
-bit, to results recorded from the reference executor (tests/golden/isai_ref.json, written by tools/isai_ref_record.cpp).
-Where the reference executor's objects and a compiler are present the recorder is built and run again, so the fixture
-cannot go stale.  Then the C ABI's argument checks and the Python layer's, none of which needs a device."""
+bit, to results recorded from the reference executor (tests/golden/isai_ref.json, written by the verb isai of
+oracle/ref_driver.cpp).  Wherever that driver is, it runs again and the fixture is compared with what it gives, so the
+fixture cannot go stale.  Then the C ABI's argument checks and the Python layer's, none of which needs a device."""
 import ctypes
 import functools
-import glob
 import json
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -16,6 +14,7 @@ import pytest
 
 import ilu_exact_util as xu
 import isai_util as iu
+import ref_exec
 import spgemm_util as su
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -169,11 +168,7 @@ def restated(name):
     return inv, trace
 
 
-def matches(rec, got):
-    got = iu.as_record(got) if isinstance(got, tuple) else got
-    if iu.digest(got) != rec["sha256"]:
-        return False
-    return "items" not in rec or iu.fixture_record(got)["items"] == rec["items"]
+matches = ref_exec.matches     # an array or a CSR matrix is the recorded one: the digest, and the items where kept
 
 
 def counts_of(pattern, trace):
@@ -191,7 +186,7 @@ def long_rows_zeroed(m):
 
 def test_the_fixture_describes_the_cases_of_the_restatement():
     assert list(REF["cases"]) == list(iu.RECORDED_CASES)
-    assert "tools/isai_ref_record.cpp" in REF["source"]
+    assert "RECORDED_CASES of tests/isai_util.py" in REF["source"]
     for name, c in REF["cases"].items():
         kind, power, limit, m = recorded_case(name)
         assert (c["kind"], c["sparsity_power"], c["excess_limit"], c["n"], c["nnz"]) == (kind, power, limit, len(m[0]) - 1, len(m[1])), name
@@ -199,7 +194,7 @@ def test_the_fixture_describes_the_cases_of_the_restatement():
 
 
 def test_the_recorded_cases_exercise_the_paths_they_are_there_for():
-    """the counts the recorder met: rows over the limit, their entries, the longest row, blocks of the excess loop"""
+    """the counts the driver met: rows over the limit, their entries, the longest row, blocks of the excess loop"""
     met = {name: c["records"]["kernel/counts"]["items"] for name, c in REF["cases"].items()}
     for name, want in iu.EXPECTED_COUNTS.items():
         assert all(w is None or w == g for w, g in zip(want, met[name])), (name, met[name])
@@ -244,27 +239,13 @@ def test_the_guard_writes_identity_rows_in_the_recorded_cases():
     assert all(np.isfinite(v) for row in rows for v in row.values())
 
 
-def test_the_recorder_reproduces_the_fixture(tmp_path):
-    """tools/isai_ref_record.cpp, built against the reference executor's objects where they and a compiler are present,
-    writes the fixture as it is committed"""
-    objs = sorted(glob.glob(os.path.join(ROOT, "oracle", "_ref", "obj", "**", "*.o"), recursive=True))
-    inc = os.path.join(ROOT, "oracle", "_ref", "include")
-    where = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "-f", "ref.mk", "ref-where"],
-                           capture_output=True, text=True)
-    ref_src = where.stdout.strip()
-    if not objs or shutil.which("g++") is None or not os.path.isdir(os.path.join(ref_src, "core", "preconditioner")):
-        pytest.skip("the reference executor's objects or its headers are not on this machine")
-    exe = tmp_path / "isai_ref_record"
-    r = subprocess.run(["g++", "-std=c++14", "-O1", "-fPIC", "-ffp-contract=off", "-pthread", "-w", f"-I{inc}",
-                        f"-I{ref_src}/include", f"-I{ref_src}", os.path.join(ROOT, "tools", "isai_ref_record.cpp"), *objs,
-                        "-o", str(exe), "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    cases = {name: recorded_case(name) for name in iu.RECORDED_CASES}
-    run = subprocess.run([str(exe)], input=iu.recorder_input(cases), capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-3000:]
-    print(run.stderr)
-    fresh = iu.fixture_from(iu.parse_recorder_output(run.stdout), cases)
-    assert json.loads(json.dumps(fresh)) == REF
+def test_the_driver_reproduces_the_fixture():
+    """oracle/_ref/ref_driver, the reference executor itself, gives the fixture as it is committed: every recorded array
+    of every case, the keys compared both ways.  One driver process; a missing driver fails wherever the reference or
+    oracle/_ref/ is."""
+    if ref_exec.may_skip():
+        pytest.skip("neither the reference nor oracle/_ref/ is on this machine")
+    assert ref_exec.difference_from_driver("isai", REF) is None
 
 
 # ---- the C ABI and the Python layer, without a device -----------------------------------------------------------------

@@ -1,19 +1,16 @@
 """solver::Multigrid without a device: the numpy restatement (tests/multigrid_util.py) against what the reference
-executor computed (tests/golden/multigrid_ref.json, written by tools/multigrid_ref_record.cpp) and against the data
-transcribed from the reference's own tests (tests/golden/multigrid.json); where the reference executor's objects and
-a compiler are present the recorder is built and run again, so the fixture cannot go stale; the C ABI's argument
+executor computed (tests/golden/multigrid_ref.json, written by the verb multigrid of oracle/ref_driver.cpp) and against
+the data transcribed from the reference's own tests (tests/golden/multigrid.json); wherever that driver is, it runs
+again and the fixture is compared with what it gives, so the fixture cannot go stale; the C ABI's argument
 checks; and the conditions on the cases that keep the GPU tests from hiding a failure."""
-import glob
 import json
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-import cb_gmres_util as cu
 import multigrid_util as mu
+import ref_exec
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -36,25 +33,30 @@ def test_the_restatement_equals_the_reference_executor(restated):
         assert REF[name]["iterations"] == [int(restated[name]["iterations"][0])]
 
 
-def test_the_recorder_reproduces_the_fixture(tmp_path):
-    """tools/multigrid_ref_record.cpp, built against the reference executor's objects where they and a compiler are
-    present, writes the fixture as it is committed"""
-    objs = sorted(glob.glob(os.path.join(ROOT, "oracle", "_ref", "obj", "**", "*.o"), recursive=True))
-    inc = os.path.join(ROOT, "oracle", "_ref", "include")
-    where = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "-f", "ref.mk", "ref-where"],
-                           capture_output=True, text=True)
-    ref_src = where.stdout.strip()
-    if not objs or shutil.which("g++") is None or not os.path.isdir(os.path.join(ref_src, "core", "solver")):
-        pytest.skip("the reference executor's objects or its headers are not on this machine")
-    exe = tmp_path / "multigrid_ref_record"
-    r = subprocess.run(["g++", "-std=c++14", "-O1", "-fPIC", "-ffp-contract=off", "-pthread", "-w", f"-I{inc}",
-                        f"-I{ref_src}/include", f"-I{ref_src}", os.path.join(ROOT, "tools", "multigrid_ref_record.cpp"),
-                        *objs, "-o", str(exe), "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    run = subprocess.run([str(exe)], input=mu.recorder_input(), capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-3000:]
-    fresh = mu.fixture_from(cu.parse_recorder_output(run.stdout))
-    assert json.loads(json.dumps(fresh)) == REF
+def test_preconditioned_cg_equals_the_reference_executor():
+    """solver::Cg preconditioned by one V-cycle on 1138_bus, the yardstick of the GPU tests' Cg over Multigrid: the
+    restatement's x and iteration count are the driver's, bit for bit"""
+    if ref_exec.may_skip():
+        pytest.skip("neither the reference nor oracle/_ref/ is on this machine")
+    m = mu.case_matrix("1138_bus")
+    arrays, params = mu.solve_arguments(mu.V_CYCLE_PRECONDITIONER, m)
+    arrays["x"] = np.zeros(m[0])
+    batch = ref_exec.Batch()
+    batch.add("multigrid", arrays, op=3, cg_max_iters=500, cg_reduction=1e-6, **params)
+    got = batch.run()[0]
+    x, iterations = mu.preconditioned_cg(m, mu.right_hand_side(m[0]), 500, 1e-6)
+    assert "error" not in got, got
+    assert int(got["iterations"][0]) == iterations
+    ref_exec.assert_bits(got["x"], x.reshape(-1), "x")
+
+
+def test_the_driver_reproduces_the_fixture():
+    """oracle/_ref/ref_driver, the reference executor itself, gives the fixture as it is committed: every recorded array
+    of every case, the keys compared both ways.  One driver process; a missing driver fails wherever the reference or
+    oracle/_ref/ is."""
+    if ref_exec.may_skip():
+        pytest.skip("neither the reference nor oracle/_ref/ is on this machine")
+    assert ref_exec.difference_from_driver("multigrid", REF) is None
 
 
 # ---- data transcribed from the reference's tests ---------------------------------------------------------------

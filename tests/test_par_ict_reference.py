@@ -1,16 +1,14 @@
 """CPU side of ParICT.  The plain-Python restatement (tests/par_ict_util.py) is pinned to the reference twice: to the
 answers the reference's own tests expect (tests/golden/par_ict.json, the reference's tolerance) and, bit for bit, to
-results recorded from the reference executor (tests/golden/par_ict_ref.json, written by tools/par_ict_ref_record.cpp).
-Where the reference executor's objects and a compiler are present the recorder is built and run again, so the fixture
-cannot go stale.  Then the C ABI's argument checks and the Python layer's, none of which needs a device; the mirror
+results recorded from the reference executor (tests/golden/par_ict_ref.json, written by the verb par_ict of
+oracle/ref_driver.cpp).  Wherever that driver is, it runs again and the fixture is compared with what it gives, so the
+fixture cannot go stale.  Then the C ABI's argument checks and the Python layer's, none of which needs a device; the mirror
 example builds and the shim compiles against the mirror prelude and links with shims/test/shim_smoke9.cpp."""
 import ctypes
 import functools
-import glob
 import json
 import math
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,6 +17,7 @@ import pytest
 import ilu_exact_util as xu
 import par_ict_util as iu
 import par_ilut_util as pu
+import ref_exec
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -107,21 +106,12 @@ def generated(name, select, limit):
     return l, traces
 
 
-def as_record(m):
-    return dict(zip(("row_ptrs", "col_idxs", "vals"), m))
-
-
-def matches(rec, got):
-    """a record of the fixture against an array or a CSR matrix: the digest, and the items where the fixture has them"""
-    got = as_record(got) if isinstance(got, tuple) else got
-    if iu.digest(got) != rec["sha256"]:
-        return False
-    return "items" not in rec or iu.fixture_record(0, "generate/approx/2/5/", got)["items"] == rec["items"]
+matches = ref_exec.matches     # an array or a CSR matrix is the recorded one: the digest, and the items where kept
 
 
 def test_the_fixture_describes_the_cases_of_the_restatement():
     assert sorted(REF["cases"]) == sorted(iu.RECORDED_CASES)
-    assert "tools/par_ict_ref_record.cpp" in REF["source"]
+    assert "RECORDED_CASES of tests/par_ict_util.py" in REF["source"]
     for name, c in REF["cases"].items():
         m = recorded_case(name)
         assert (c["n"], c["nnz"]) == (len(m[0]) - 1, len(m[1])), name
@@ -195,26 +185,13 @@ def test_recorded_cases_make_both_sweeps_reject_values_that_are_not_finite():
             assert counts == [(0, 0), second_iteration, (0, 0), (0, 0), (0, 0)], (select, limit, counts)
 
 
-def test_the_recorder_reproduces_the_fixture(tmp_path):
-    """tools/par_ict_ref_record.cpp, built against the reference executor's objects where they and a compiler are
-    present, writes the fixture as it is committed"""
-    objs = sorted(glob.glob(os.path.join(ROOT, "oracle", "_ref", "obj", "**", "*.o"), recursive=True))
-    inc = os.path.join(ROOT, "oracle", "_ref", "include")
-    where = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "-f", "ref.mk", "ref-where"],
-                           capture_output=True, text=True)
-    ref_src = where.stdout.strip()
-    if not objs or shutil.which("g++") is None or not os.path.isdir(os.path.join(ref_src, "core", "factorization")):
-        pytest.skip("the reference executor's objects or its headers are not on this machine")
-    exe = tmp_path / "par_ict_ref_record"
-    r = subprocess.run(["g++", "-std=c++14", "-O1", "-fPIC", "-ffp-contract=off", "-pthread", "-w", f"-I{inc}",
-                        f"-I{ref_src}/include", f"-I{ref_src}", os.path.join(ROOT, "tools", "par_ict_ref_record.cpp"), *objs,
-                        "-o", str(exe), "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    cases = {name: recorded_case(name) for name in iu.RECORDED_CASES}
-    run = subprocess.run([str(exe)], input=iu.recorder_input(cases), capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-3000:]
-    fresh = iu.fixture_from(iu.parse_recorder_output(run.stdout), cases)
-    assert json.loads(json.dumps(fresh)) == REF
+def test_the_driver_reproduces_the_fixture():
+    """oracle/_ref/ref_driver, the reference executor itself, gives the fixture as it is committed: every recorded array
+    of every case, the keys compared both ways.  One driver process; a missing driver fails wherever the reference or
+    oracle/_ref/ is."""
+    if ref_exec.may_skip():
+        pytest.skip("neither the reference nor oracle/_ref/ is on this machine")
+    assert ref_exec.difference_from_driver("par_ict", REF) is None
 
 
 # ---- the mirror and the shims build ------------------------------------------------------------------------------

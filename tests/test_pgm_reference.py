@@ -1,22 +1,20 @@
 """multigrid::Pgm without a device: the sequential numpy restatement (tests/pgm_util.py) against what the reference
-executor computed (tests/golden/pgm_ref.json, written by tools/pgm_ref_record.cpp) and against the known answers
-transcribed from the reference's own tests (tests/golden/pgm.json); the parallel form the device kernels compute
+executor computed (tests/golden/pgm_ref.json, written by the verb pgm of oracle/ref_driver.cpp, which runs again
+wherever it is, so the fixture cannot go stale) and against the known answers transcribed from the reference's own
+tests (tests/golden/pgm.json); the parallel form the device kernels compute
 against the sequential one, on every case and on seeded random matrices -- the order-independence argument, tested;
 the conditions on the cases that keep the GPU tests from hiding a branch; the reference's stencil solves met by the
 restated Multigrid over Pgm; and the C ABI's argument checks."""
 import ctypes
-import glob
 import json
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-import cb_gmres_util as cu
 import multigrid_util as mu
 import pgm_util as pu
+import ref_exec
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -41,25 +39,13 @@ def test_the_sequential_restatement_equals_the_reference_executor(restated):
         assert REF[name]["levels"] == [int(t) for t in restated[name]["levels"]]
 
 
-def test_the_recorder_reproduces_the_fixture(tmp_path):
-    """tools/pgm_ref_record.cpp, built against the reference executor's objects where they and a compiler are present,
-    writes the fixture as it is committed"""
-    objs = sorted(glob.glob(os.path.join(ROOT, "oracle", "_ref", "obj", "**", "*.o"), recursive=True))
-    inc = os.path.join(ROOT, "oracle", "_ref", "include")
-    where = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "-f", "ref.mk", "ref-where"],
-                           capture_output=True, text=True)
-    ref_src = where.stdout.strip()
-    if not objs or shutil.which("g++") is None or not os.path.isdir(os.path.join(ref_src, "core", "multigrid")):
-        pytest.skip("the reference executor's objects or its headers are not on this machine")
-    exe = tmp_path / "pgm_ref_record"
-    r = subprocess.run(["g++", "-std=c++14", "-O1", "-fPIC", "-ffp-contract=off", "-pthread", "-w", f"-I{inc}",
-                        f"-I{ref_src}/include", f"-I{ref_src}", os.path.join(ROOT, "tools", "pgm_ref_record.cpp"),
-                        *objs, "-o", str(exe), "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    run = subprocess.run([str(exe)], input=pu.recorder_input(), capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-3000:]
-    fresh = pu.fixture_from(cu.parse_recorder_output(run.stdout))
-    assert json.loads(json.dumps(fresh)) == REF
+def test_the_driver_reproduces_the_fixture():
+    """oracle/_ref/ref_driver, the reference executor itself, gives the fixture as it is committed: every recorded array
+    of every case, the keys compared both ways.  One driver process; a missing driver fails wherever the reference or
+    oracle/_ref/ is."""
+    if ref_exec.may_skip():
+        pytest.skip("neither the reference nor oracle/_ref/ is on this machine")
+    assert ref_exec.difference_from_driver("pgm", REF) is None
 
 
 # ---- known answers transcribed from the reference's tests --------------------------------------------------------

@@ -1,9 +1,13 @@
 """Completeness of the reference-parity tests: every ref_* export of the C
-oracle and every public function of the five Python restatements is looked up
-in the table below.  An entry names the ref_driver verb whose cases pin it to
-the reference itself, or says why nothing does -- which only the distributed
-family, the cpu_baseline port and pure helpers (functions that compute nothing
-the reference computes: generators, packers, comparison helpers) may do.
+oracle and every public function of the eleven Python restatements is looked
+up in the table below.  An entry names the ref_driver verb whose cases pin it
+to the reference itself, or says why nothing does -- which only the distributed
+family, the cpu_baseline port, pure helpers (functions that compute nothing
+the reference computes: generators, packers, comparison helpers) and second
+forms may do.  A second form restates the device's way to something the
+reference computes in another order; its entry names the pinned function it
+is a form of and the CPU test that holds the two equal, or within a stated
+bound of each other.
 
 The table is checked mechanically as far as text can be: the verb exists in
 oracle/ref_driver.cpp and is used by the parity modules; a pinned name is
@@ -13,28 +17,43 @@ import inspect
 import os
 import re
 
+import cb_gmres_util
 import fbcsr_util
 import idr_util
 import ilu_exact_util
+import isai_util
 import lu_util
+import multigrid_util
 import oracle_lib
+import par_ict_util
+import par_ilut_util
+import pgm_util
 import spgemm_util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PARITY = ["test_ref_oracle_parity.py", "test_ref_oracle_parity_solvers.py"]
+# a family pinned through a JSON fixture has a parity module of its own: the restatement against the fixture, the
+# fixture against the driver.  Its functions are looked up there, under the name the module imports it by.
+OWN = {"par_ilut_util": ("test_par_ilut_reference.py", "pu"), "par_ict_util": ("test_par_ict_reference.py", "iu"),
+       "isai_util": ("test_isai_reference.py", "iu"), "cb_gmres_util": ("test_cb_gmres_reference.py", "cu"),
+       "multigrid_util": ("test_multigrid_reference.py", "mu"), "pgm_util": ("test_pgm_reference.py", "pu")}
+SHARED = ["test_ref_oracle_parity.py", "test_ref_oracle_parity_solvers.py"]
+PARITY = SHARED + [f for f, _ in OWN.values()]
 # modules through which the parity tests call the oracle
 GLUE = ["formats_util.py", "ilu_util.py"]
 UTILS = {"fbcsr_util": fbcsr_util, "spgemm_util": spgemm_util, "idr_util": idr_util,
-         "ilu_exact_util": ilu_exact_util, "lu_util": lu_util}
+         "ilu_exact_util": ilu_exact_util, "lu_util": lu_util, "par_ilut_util": par_ilut_util,
+         "par_ict_util": par_ict_util, "isai_util": isai_util, "cb_gmres_util": cb_gmres_util,
+         "multigrid_util": multigrid_util, "pgm_util": pgm_util}
 
 
 def V(verb, via=None):
     return ("verb", verb, via)
 
 
-def R(kind, why):
-    assert kind in ("distributed", "cpu_baseline", "helper")
-    return ("reason", kind, why)
+def R(kind, why, of=None, test=None):
+    """of, test: the pinned function a second form is a form of, and the test of its parity module that relates them"""
+    assert kind in ("distributed", "cpu_baseline", "helper", "second_form") and (kind == "second_form") == (of is not None)
+    return ("reason", kind, why, of, test)
 
 
 DIST = R("distributed", "the reference's distributed classes need MPI; oracle/distributed.c stays on its golden vectors")
@@ -105,6 +124,7 @@ ORACLE = {
 }
 
 GEN = lambda what: R("helper", "generator: " + what)
+DRIVER_END = R("helper", "packs the cases for ref_driver or its results into the fixture's layout")
 PYTHON = {
     "fbcsr_util": {
         "spmv": V("spmv"), "csr_to_fbcsr": V("convert"), "to_csr": V("convert"), "fill_in_dense": V("fbcsr_op"),
@@ -148,6 +168,87 @@ PYTHON = {
             "symmetrize_pattern", "diagonal", "tridiagonal_with_corners", "grid_5pt", "repeated_separable",
             "unsymmetric_values", "with_zero_pivot", "new_values")},
     },
+    "par_ilut_util": {
+        **{n: V("par_ilut") for n in ("generate", "add_candidates", "compute_l_u_factors", "threshold_select",
+                                      "threshold_filter", "threshold_filter_approx", "transpose")},
+        "iterate": V("par_ilut", via="generate"), "approx_threshold": V("par_ilut", via="threshold_filter_approx"),
+        "dense_to_csr": GEN("a matrix of the reference's tests"), "made_cases": GEN("the recorded matrices"),
+        **{n: DRIVER_END for n in ("queue_cases", "case_arrays", "group_records", "fixture_record", "fixture_from")},
+    },
+    "par_ict_util": {
+        **{n: V("par_ict") for n in ("generate", "add_candidates", "compute_factor", "initialize_l")},
+        "iterate": V("par_ict", via="generate"), "transpose": V("par_ict", via="iterate"),
+        "dense_to_csr": GEN("a matrix of the reference's tests"), "made_cases": GEN("the recorded matrices"),
+        **{n: DRIVER_END for n in ("queue_cases", "group_records", "fixture_from")},
+    },
+    "isai_util": {
+        **{n: V("isai") for n in ("generate_inverse", "generic_generate", "generate_excess_system",
+                                  "scatter_excess_solution", "row_lengths", "long_rows")},
+        **{n: V("isai", via="generate_inverse") for n in ("extend_sparsity", "excess_blocks", "dense_block_solve",
+                                                          "scale_excess_solution")},
+        **{n: V("isai", via="generic_generate") for n in ("trs_solve", "general_solve", "forall_matching")},
+        **{n: GEN("a test matrix") for n in ("golden_mtx", "ilu0_factors", "ic0_factor", "banded", "alternating",
+                                             "general_banded", "spd_banded", "made_cases")},
+        **{n: DRIVER_END for n in ("queue_cases", "case_arrays", "fixture_record", "fixture_from")},
+    },
+    "cb_gmres_util": {
+        **{n: V("cb_gmres") for n in ("initialize", "restart", "arnoldi", "solve_krylov", "restated_solve",
+                                      "float_to_half_bits", "half_bits_to_double")},
+        "solve": V("cb_gmres", via="restated_solve"), "jacobi_apply": V("cb_gmres", via="restated_solve"),
+        "finish_arnoldi": V("cb_gmres", via="arnoldi"), "givens": V("cb_gmres", via="arnoldi"),
+        "correction": V("cb_gmres", via="restart"), "ssum": V("cb_gmres", via="restart"),
+        "residual_norm_check": V("cb_gmres", via="solve"),
+        "device_sum": R("second_form", "the order in which the device adds", of="ssum",
+                        test="test_the_device_s_sum_is_a_reordering_of_the_sequential_one"),
+        "reordered_counts": R("second_form", "iteration counts with grouped and device-order sums, rne halves",
+                              of="restated_solve",
+                              test="test_the_fixture_knows_which_iteration_counts_survive_a_reordered_sum"),
+        "compress": R("second_form", "what the device's write of a vector stores (rne halves)", of="float_to_half_bits",
+                      test="test_compress_stores_what_a_basis_write_stores"),
+        "is_scaled": R("helper", "names the storages with scalars"),
+        "count_is_stable": R("helper", "compares the iteration counts of a fixture record"),
+        "solve_problem": GEN("the system of a case"), "right_hand_side": GEN("right-hand sides"),
+        **{n: DRIVER_END for n in ("queue_cases", "case_arrays", "fixture_from", "dump_fixture")},
+    },
+    "multigrid_util": {
+        **{n: V("multigrid") for n in ("restated_records", "restated", "fixed_coarsening", "spmv", "advanced_spmv",
+                                       "preconditioned_cg")},
+        **{n: V("multigrid", via="restated_records") for n in ("restated_kcycle", "restated_coarsening",
+                                                               "restated_smoother", "restated_solve")},
+        **{n: V("multigrid", via="restated_kcycle") for n in ("kcycle_step_1", "kcycle_step_2", "kcycle_check_stop")},
+        **{n: V("multigrid", via="fixed_coarsening") for n in ("sort_by_column_index", "transpose", "spgemm")},
+        **{n: V("multigrid", via="restated_smoother") for n in ("jacobi_sweeps", "inverted_diagonal")},
+        **{n: V("multigrid", via="preconditioned_cg") for n in ("dot", "norm2")},
+        **{n: R("helper", "a level factory over fixed_coarsening") for n in ("every_second", "no_reduction")},
+        **{n: R("helper", "a call trace against the sequences transcribed from the reference's tests")
+           for n in ("cycle_steps", "steps_of", "expected_steps", "steps_match")},
+        "csr": R("helper", "packs a matrix"), "record_matches": R("helper", "compares with a fixture record"),
+        **{n: GEN("a matrix or the vectors of a case") for n in (
+            "read_mtx", "case_matrix", "unsorted_5x5", "shuffled_rows", "right_hand_side", "initial_guess",
+            "kcycle_operands")},
+        **{n: DRIVER_END for n in ("solve_arguments", "queue_cases", "case_arrays", "fixture_from", "dump_fixture")},
+    },
+    "pgm_util": {
+        **{n: V("pgm") for n in ("generate", "restated", "restated_records", "weight_matrix", "find_strongest_neighbor",
+                                 "match_edge", "count_unagg", "assign_to_exist_agg", "renumber", "pgm_level_factory")},
+        **{n: V("pgm", via="restated_records") for n in ("level_records", "restated_solve")},
+        **{n: V("pgm", via="generate") for n in ("agg_to_restrict", "generate_coarse")},
+        **{n: V("pgm", via="weight_matrix") for n in ("compute_absolute", "extract_diagonal", "spgeam")},
+        **{n: V("pgm", via="generate_coarse") for n in ("sort_row_major", "compute_coarse_coo")},
+        "solve_parts": V("pgm", via="restated_solve"),
+        "assign_to_exist_agg_parallel": R("second_form", "the device's static choice followed by pointer jumping",
+                                          of="assign_to_exist_agg", test="test_kernel_known_answers"),
+        "jump_rounds": R("helper", "counts the rounds of pointer jumping"),
+        **{n: R("helper", "the lanes per row the device kernels pick: a condition on the cases")
+           for n in ("subwave_width", "case_subwave_width")},
+        "record_matches": R("helper", "compares with a fixture record"),
+        **{n: GEN("a test matrix") for n in (
+            "from_dense_pattern", "reference_5x5", "grid", "grid27", "path", "diagonal", "blocks_2x2", "random_matrix",
+            "star_plus_ring", "stencil3", "case_matrix", "solve_matrix")},
+        **{n: R("helper", "the cases as text for the mirror's example and its output as arrays")
+           for n in ("recorder_input", "parse_example_output", "arrays_from_text")},
+        **{n: DRIVER_END for n in ("queue_cases", "fixture_from")},
+    },
 }
 
 
@@ -162,7 +263,7 @@ def _called_in(name, text):
 
 
 def _parity_text():
-    return "".join(_read("tests", f) for f in PARITY + GLUE)
+    return "".join(_read("tests", f) for f in SHARED + GLUE)
 
 
 def _parity_names():
@@ -194,14 +295,32 @@ def _c_definition(name):
     raise AssertionError(name + " is not defined in oracle/*.c")
 
 
-def _check_entry(name, entry, direct, via_text):
+def _test_text(text, test):
+    """the code of one test function of a module: its docstring and its comments say nothing"""
+    m = re.search(r"^def " + re.escape(test) + r"\(.*?(?=^\S|\Z)", text, re.S | re.M)
+    if m is None:
+        return None
+    code = re.sub(r'""".*?"""', "", m.group(0), count=1, flags=re.S)
+    return re.sub(r"#[^\n]*", "", code)
+
+
+def _check_entry(name, entry, direct, via_text, table=None, text="", queues=None):
+    """text: the parity module in which a second form's test is looked up; queues: the text that must queue the verb
+    on the driver (default: the shared parity modules and their glue)"""
     kind = entry[0]
     if kind == "reason":
-        assert entry[1] in ("distributed", "cpu_baseline", "helper") and entry[2].strip(), name
+        assert entry[1] in ("distributed", "cpu_baseline", "helper", "second_form") and entry[2].strip(), name
+        if entry[1] == "second_form":
+            _, _, _, of, test = entry
+            short = name.split(".")[-1]
+            assert table[of][0] == "verb", f"{name}: {of} is not pinned itself"
+            body = _test_text(text, test)
+            assert body is not None, f"{name}: no test {test} in its parity module"
+            assert _called_in(short, body) and _called_in(of, body), f"{name}: {test} does not call it and {of}"
         return
     _, verb, via = entry
     assert verb in _driver_verbs(), f"{name}: ref_driver has no verb {verb}"
-    assert f'"{verb}"' in _parity_text(), f"{name}: no parity case uses the verb {verb}"
+    assert f'"{verb}"' in (_parity_text() if queues is None else queues), f"{name}: no parity case uses the verb {verb}"
     if via is None:
         assert direct(name), f"{name}: said to be pinned by {verb}, but no parity module calls it"
     else:
@@ -225,8 +344,12 @@ def test_every_oracle_export_is_pinned_or_explained():
 
 
 def test_every_restatement_function_is_pinned_or_explained():
-    text = _parity_text()
     for modname, mod in UTILS.items():
+        text = _read("tests", OWN[modname][0]) if modname in OWN else _parity_text()
+        # a family's own module queues its verb where it calls Batch.add: in its queue_cases
+        queues = inspect.getsource(mod.queue_cases) if modname in OWN else None
+        if modname in OWN:      # and its parity module runs them through the driver under the one skip rule
+            assert OWN[modname][0] in PARITY and "ref_exec.may_skip()" in text and "difference_from_driver(" in text
         public = sorted(n for n, f in vars(mod).items()
                         if inspect.isfunction(f) and f.__module__ == mod.__name__ and not n.startswith("_"))
         table = PYTHON[modname]
@@ -234,9 +357,9 @@ def test_every_restatement_function_is_pinned_or_explained():
         assert not missing, f"{modname}: functions without a table entry: {missing}"
         stale = [n for n in table if n not in public]
         assert not stale, f"{modname}: table entries for functions that are gone: {stale}"
-        alias = {"ilu_exact_util": "xu"}.get(modname, modname)
+        alias = OWN[modname][1] if modname in OWN else {"ilu_exact_util": "xu"}.get(modname, modname)
 
-        def direct(n, alias=alias):
+        def direct(n, alias=alias, text=text):
             return re.search(r"\b" + alias + r"\." + n + r"\b", text) is not None
 
         def via_text(n, mod=mod):
@@ -246,7 +369,7 @@ def test_every_restatement_function_is_pinned_or_explained():
             entry = table[n]
             if entry[0] == "verb" and entry[2] is not None:
                 assert table[entry[2]][0] == "verb", f"{modname}.{n}"
-            _check_entry(f"{modname}.{n}" if entry[0] == "reason" else n, entry, direct, via_text)
+            _check_entry(f"{modname}.{n}" if entry[0] == "reason" else n, entry, direct, via_text, table, text, queues)
 
 
 def test_no_parity_case_may_skip_where_the_reference_is():
